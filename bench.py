@@ -2,8 +2,10 @@
 """Throughput of the masked-pretraining step (BASELINE.json configs[1]): 12-layer d=512 ViT over
 40x2048 synthetic uint8 lines, V=4096, bf16 MFMA, one process per GPU.
 
-  python bench.py                                   (1 GPU, SURVEY 8d protocol: 20 warm-up, 5 repeats of 100 steps, median)
-  python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5    (the headline alone: set-up, warm-up, exactly --steps timed steps, one JSON line)
+  python bench.py --full                            (+ every other measurement listed below)
+  python bench.py --full --repeats 5                (1 GPU, SURVEY 8d protocol: 20 warm-up, 5 repeats of 100 steps, median)
+  python bench.py --dump-outputs DIR ...            (+ the last timed step's outputs as DIR/*.npy, see dump_outputs)
   python bench.py --gpus N ...                      (no RANK in the environment: starts the N ranks itself, see self_launch)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W        (the driver's form; one rank per GPU over RCCL)
@@ -12,8 +14,9 @@ A step = BatchOperator.prepare_batch (host mask draw, labels / mask upload; the 
 zero_grad -> front end (u8 -> /255 -> mask tile -> patches) -> 12 encoder layers -> head -> masked CE -> backward of all of it ->
 [gradient all-reduce] -> fused Adam: the reference's Trainer.train_step (masked_pretraining/trainer.py:53-68).  ONE JSON line (rank 0).
 
-  value               whole-job lines/s of that step: the MEDIAN over `--repeats` repeats of exactly --steps steps, each bracketed by
-                      barrier + synchronize (max over ranks)
+  value               whole-job lines/s of that step: the MEDIAN over `--repeats` repeats (default 1) of exactly --steps steps, each
+                      bracketed by barrier + synchronize (max over ranks); ms_per_step is the same median as milliseconds per step
+Only with --full (the --no-* options below switch single ones off):
   resident_step       the same without prepare_batch in the timed region (labels and mask resident too: train_step_prepared only)
   with_h2d            prepare_batch INCLUDING the uint8 batch from pinned host memory over PCIe (copy stream, double-buffered) - never `value`
   roofline            the bf16 tile GEMM: algorithmic flops / HIP-event duration of every launch of two extra steps
@@ -166,6 +169,28 @@ def synthetic(rank, B, device, nbatches=2):
         mask._pero_host = mask_h   # what BatchOperator / DevicePrefetcher attach: the host original of an uploaded mask
         out.append({"images": images, "labels": labels_h, "labels_dev": torch.from_numpy(labels_h).to(device), "mask_dev": mask})
     return out
+
+
+DUMP_SAMPLE = 32768   # elements per parameter tensor: ~150 tensors x (gradient + parameter) x 128 KB stays well under 64 MB
+
+
+def dump_outputs(path, model, loss):
+    """--dump-outputs: what the last timed step handed back - its loss, and the gradients and updated parameters it left in the model -
+    as path/loss.npy (float64), path/grad_sample.npy and path/param_sample.npy (float32).  The samples concatenate, in named_parameters()
+    order, DUMP_SAMPLE elements of every larger tensor (positions from a fixed seed and the shapes only) and the whole of every smaller one,
+    so that two builds run with the same arguments can be compared element for element."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(0)
+    grads, params = [], []
+    for _, p in model.named_parameters():
+        n = p.numel()
+        idx = np.sort(rng.choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+        idx = torch.from_numpy(idx).to(p.device)
+        params.append(p.detach().reshape(-1)[idx].float())
+        grads.append(p.grad.reshape(-1)[idx].float() if p.grad is not None else torch.zeros(len(idx), device=p.device))
+    np.save(os.path.join(path, "loss.npy"), np.asarray(float(loss.detach()), dtype=np.float64))
+    np.save(os.path.join(path, "grad_sample.npy"), torch.cat(grads).cpu().numpy())
+    np.save(os.path.join(path, "param_sample.npy"), torch.cat(params).cpu().numpy())
 
 
 def cpu_baseline(budget_s=20.0, B=8):
@@ -531,7 +556,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)     # warm-up 20 steps, time >= 100 steps, median of 5 repeats
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="headline: median of this many runs of --steps timed steps (default 1); the --full side measurements take at most 3 (default 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other measurement (side steps, roofline, batch sweep, bandwidth kernels, legs, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and sampled gradients / parameters to DIR/*.npy (dump_outputs)")
     ap.add_argument("--batch", type=int, default=int(os.environ.get("PERO_BENCH_BATCH", 2048)), help="lines per GPU")
     ap.add_argument("--no-side-stream", action="store_true", help="weight gradients on the main stream (the default since round 3; kept for the profiling scripts)")
     ap.add_argument("--side-stream", action="store_true", help="weight gradients on a second HIP stream (rounds 1-2's default; measured slower now)")
@@ -556,6 +586,12 @@ def main():
     ap.add_argument("--spawn", action="store_true", help="start the rank(s) through torch.distributed.run even for --gpus 1 (RCCL with one rank)")
     ap.add_argument("--plumbing-test", action="store_true", help=argparse.SUPPRESS)   # CPU / gloo rehearsal of launch + timing + relay (tests)
     args = ap.parse_args()
+    if args.legs_only and not args.full:
+        ap.error("--legs-only measures legs, which only run with --full")
+    if args.legs_only and args.dump_outputs:
+        ap.error("--dump-outputs writes the headline step's outputs, which --legs-only does not run")
+    side_reps = min(args.repeats or 3, 3)
+    args.repeats = args.repeats or 1
 
     if "RANK" not in os.environ and (args.gpus > 1 or args.spawn):
         self_launch(args, sys.argv[1:])     # never returns
@@ -645,6 +681,8 @@ def main():
             step(i)
         elapsed, repeats, loss = timer.median(step, args.steps, args.repeats, first=args.warmup)
         final_loss = float(loss.detach()) if hasattr(loss, "detach") else float(loss)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, model, loss)
         lines_per_s = world * args.batch * args.steps / elapsed
         step_flops = flops_per_line()
         exec_flops = flops_per_line(masked_frac=0.15, last_layer_rows=F.ROW_SPARSE_LAST_LAYER) if (args.head_backward == "masked" and not args.masked_head) else step_flops
@@ -671,8 +709,8 @@ def main():
             "step_mfma_frac_formula_flops": round(lines_per_s / world * step_flops / (BF16_MFMA_PEAK_TFLOPS * 1e12), 4),
             "final_loss": round(final_loss, 5)})
 
-        if not args.no_options and not args.masked_head:
-            reps = min(args.repeats, 3)
+        if args.full and not args.no_options and not args.masked_head:
+            reps = side_reps
             osteps = min(args.steps, 30)   # the side legs: three repeats of at most 30 steps each (the headline keeps the full protocol)
             # ---- the same step with labels and mask resident too (train_step_prepared only: rounds 1-2's `value`)
             for i in range(2):
@@ -726,22 +764,22 @@ def main():
                                                       "head's backward has since round 2"}
             Fn.ROW_SPARSE_LAST_LAYER = not args.dense_last_layer
 
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             per = timed_gemms(lambda n: [step(args.warmup + 7 + k) for k in range(n)], 2)
             traffic, src = pmc_traffic(args.batch)
             out["roofline"] = gemm_roofline(per, 2, elapsed / args.steps, traffic)
             out["roofline"]["traffic_source"] = f"profiles/{src} (csrc_sha256 {csrc_hash()})" if src else None
         del batches
-        if not args.no_sweep and not args.masked_head:
+        if args.full and not args.no_sweep and not args.masked_head:
             out["batch_sweep"] = batch_sweep(device, model, opt, sched, bf16, rank, timer, world)
         del model, opt, trainer
         torch.cuda.empty_cache()   # the masked model's 48 GB of saved activations
-        if not args.no_sweep and rank == 0:
+        if args.full and not args.no_sweep and rank == 0:
             out["hbm_kernels"] = hbm_kernels(device, args.batch)
             torch.cuda.empty_cache()
 
-    if not args.no_legs:
-        reps = min(args.repeats, 3)
+    if args.full and not args.no_legs:
+        reps = side_reps
         legs = {}
         vp, npairs = (int(v) for v in args.leg_pairs.split(","))
         if world == 1:
@@ -761,7 +799,7 @@ def main():
             legs["config5_ntxent_dp_cross_rank_negatives"] = leg_joint(timer, device, "ntxent", npairs, 3, reps, world, rank, variant="cross")
         out["legs"] = legs
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.legs_only:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.legs_only:
         out["cpu_baseline"] = cpu_baseline()
     emit(out)
     if dist.is_initialized():

@@ -400,7 +400,7 @@ def test_bench_two_ranks_rehearsal_emits_the_world_gt_1_legs():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "1", "--batch", "32",
-                        "--leg-pairs", "8,16", "--no-cpu-baseline", "--no-sweep", "--no-options", "--no-roofline"],
+                        "--full", "--leg-pairs", "8,16", "--no-cpu-baseline", "--no-sweep", "--no-options", "--no-roofline"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -413,3 +413,42 @@ def test_bench_two_ranks_rehearsal_emits_the_world_gt_1_legs():
     for k in want:
         leg = d["legs"][k]
         assert leg["distributed"]["world_size"] == 2 and np.isfinite(leg["loss"]) and leg["ms_per_step"] > 0, (k, leg)
+
+
+def test_bench_plain_run_dumps_the_last_timed_steps_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the headline alone (none of the --full measurements in its line),
+    one timed run of exactly K steps; --dump-outputs writes that run's last step - loss, sampled gradients and parameters, float32 / float64,
+    at most 64 MB - and two runs with the same arguments start from the same inputs, so their outputs agree."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    full_only = {"resident_step", "with_h2d", "option_masked_head", "option_dense_last_layer", "roofline", "batch_sweep", "hbm_kernels", "legs",
+                 "cpu_baseline"}
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32",
+                            "--dump-outputs", str(out)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout.decode()[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["protocol"]["repeats"] == 1 and len(d["protocol"]["repeats_ms_per_step"]) == 1
+        assert d["unit"] == "lines/s" and d["higher_is_better"] is True and d["dtype"] == "bf16" and d["value"] > 0 and d["ms_per_step"] > 0
+        assert not full_only & set(d), full_only & set(d)
+        files = {f.name: np.load(f) for f in out.iterdir()}
+        assert set(files) == {"loss.npy", "grad_sample.npy", "param_sample.npy"}
+        assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+        assert files["loss.npy"].dtype == np.float64 and files["grad_sample.npy"].dtype == files["param_sample.npy"].dtype == np.float32
+        assert all(np.isfinite(a).all() for a in files.values())
+        assert abs(float(files["loss.npy"]) - d["final_loss"]) <= 1e-5
+        assert np.abs(files["grad_sample.npy"]).max() > 0
+        dumps.append(files)
+    a, b = dumps
+    assert a["grad_sample.npy"].shape == b["grad_sample.npy"].shape == a["param_sample.npy"].shape
+    assert abs(float(a["loss.npy"]) - float(b["loss.npy"])) <= 1e-4 * abs(float(a["loss.npy"]))
+    ga, gb = a["grad_sample.npy"], b["grad_sample.npy"]
+    assert np.abs(ga - gb).max() <= 1e-3 * np.abs(ga).max()
+    assert np.abs(a["param_sample.npy"] - b["param_sample.npy"]).max() <= 1e-5
