@@ -94,6 +94,48 @@ def layer_norm(x, w, b, eps=1e-5):
     return xc / torch.sqrt(var + eps) * w + b
 
 
+def layer_norm_bwd_f64(x, dy, w, eps=1e-5):
+    """LayerNorm backward in f64 from the input rows x: (dx, dgamma, dbeta, column sums of dx), plus the per-column scales
+    sqrt(sum_i (dy xhat)^2) and sqrt(sum_i dx^2) that dgamma's and the column sums' rounding errors are measured against."""
+    x, dy, w = x.double(), dy.double(), w.double()
+    mu = x.mean(-1, keepdim=True)
+    rs = 1.0 / torch.sqrt(((x - mu) ** 2).mean(-1, keepdim=True) + eps)
+    xh = (x - mu) * rs
+    g = dy * w
+    dx = rs * (g - g.mean(-1, keepdim=True) - xh * (g * xh).mean(-1, keepdim=True))
+    return dx, (dy * xh).sum(0), dy.sum(0), dx.sum(0), (dy * xh).pow(2).sum(0).sqrt(), dx.pow(2).sum(0).sqrt()
+
+
+def layer_norm_bwd_column_errors(dx, dgamma, dbeta, dxsum, ref):
+    """Per-column errors of a LayerNorm backward against layer_norm_bwd_f64's `ref`: dx as the column's largest error over the RMS of the
+    whole reference dx; dgamma and the dx column sums over their column's scale (ref[4], ref[5]), dbeta over sqrt(rows) (unit dy)."""
+    rdx, rdg, rdb, rdxs, sg, sxs = ref
+    dx, dgamma, dbeta, dxsum = (v.double().cpu() for v in (dx, dgamma, dbeta, dxsum))
+    return {"dx": (dx - rdx).abs().max(0).values / rdx.pow(2).mean().sqrt(), "dgamma": (dgamma - rdg).abs() / sg,
+            "dbeta": (dbeta - rdb).abs() / rdx.shape[0] ** 0.5, "dxsum": (dxsum - rdxs).abs() / sxs}
+
+
+def trained_layernorm_columns(d, seed):
+    """LayerNorm gamma / beta as training leaves them: most columns |gamma| in [0.5, 1.5] (every 7th negative), beta ~ 0.3 N(0, 1);
+    mixed in, columns with |gamma| in {1e-3, 1e-2, 0.1} of both signs crossed with |beta| in {0, 1, 4}, two at |beta / gamma| = 4,
+    and one with gamma = 0, beta = 0.5 (d >= 64)."""
+    g = torch.Generator().manual_seed(seed)
+    gamma = torch.rand(d, generator=g) + 0.5
+    gamma[1::7] *= -1.0
+    beta = torch.randn(d, generator=g) * 0.3
+    cols = []
+    for gm in (1e-3, 1e-2, 0.1):
+        for sg in (1.0, -1.0):
+            for bm in (0.0, 1.0, 4.0):
+                cols.append((sg * gm, bm if len(cols) % 2 == 0 else -bm))
+    cols += [(0.25, 1.0), (-0.25, 1.0), (0.0, 0.5)]
+    stride = d // len(cols)
+    for k, (gv, bv) in enumerate(cols):
+        gamma[3 + k * stride] = gv
+        beta[3 + k * stride] = bv
+    return gamma, beta
+
+
 def add_positional(t, n, s, pe, offsets=None):
     """t: (N*S, d) rows ordered (line, position).  eval: + pe[0:S]; train with random_shift:
     line i gets pe[offset_i : offset_i + S].  models/transformers.py:174-188."""

@@ -127,8 +127,10 @@ __global__ __launch_bounds__(256) void layernorm_fwd4_k(const bf16raw* x, const 
 // LayerNorm backward: dx per row; dgamma / dbeta / column sums of dx accumulated per lane over the rows
 // a wave visits, combined across the block's 4 waves through LDS, then one f32 atomic per column.
 // FROM_OUT (round 4, "memory-efficient" LayerNorm): `x` is the layer's OUTPUT t = xhat * gamma + beta and `mean` is the BETA vector (per
-// column, not per row): xhat is recovered as (t - beta) / gamma, so the forward pass need not keep its input rows for the backward (in bf16
-// mode the stored t carries the same 2^-9 relative rounding the stored input rows had; columns with gamma == 0 lose their gamma gradient).
+// column, not per row): xhat is recovered as (t - beta) / gamma, so the forward pass need not keep its input rows for the backward.  In bf16
+// mode t's 2^-9 |t| rounding comes back as an xhat error of ~2^-9 (|xhat| + |beta / gamma|), and a column with gamma == 0 has no xhat at all
+// (its gamma gradient would be dropped): the callers run this form only where every column has |beta| <= R |gamma|, gamma != 0
+// (functional.ln_keep_rows), and keep the input rows otherwise.
 template <typename T, int NCH, bool FROM_OUT>
 __global__ __launch_bounds__(256) void layernorm_bwd_k(const T* dy, const T* x, const float* mean, const float* rstd,
                                                        const float* gamma, T* dx, float* work, const float* dxsum,

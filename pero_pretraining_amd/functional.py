@@ -13,6 +13,7 @@ buffers - partial tiles summed in slice order through a caller-owned workspace (
 reproducible), f32 atomics only for short reductions.
 """
 import math
+import weakref
 
 import torch
 
@@ -217,6 +218,30 @@ def ln_from_out(dtype):
     return LN_BWD_FROM_OUT and dtype == torch.bfloat16
 
 
+LN_FROM_OUT_MAX_RATIO = 4.0   # the backward from the output rebuilds xhat = (t - beta) / gamma: t's bf16 rounding (2^-9 |t|, |t| <= |gamma xhat| + |beta|)
+                              # comes back amplified by |beta / gamma|.  A layer whose norm1 or norm2 has a column with |beta| > R |gamma| (or gamma == 0,
+                              # where xhat is lost) keeps its input rows y instead (ln_keep_rows); at R = 4 the from-output error stays within 1.5 x the
+                              # rows-kept error + a floor (tests/test_gpu_ops.py, DESIGN.md "LayerNorm backward from the output")
+
+
+def ln_fragile_columns(gamma, beta):
+    """Columns whose xhat the backward from the output cannot rebuild to bf16 accuracy: |beta| > LN_FROM_OUT_MAX_RATIO |gamma|, or gamma == 0."""
+    return (beta.abs() > LN_FROM_OUT_MAX_RATIO * gamma.abs()) | (gamma == 0)
+
+
+def ln_keep_rows(mod, dtype):
+    """Per encoder layer: True where the layer must keep its LayerNorms' input rows y because norm1 or norm2 has a fragile column
+    (ln_fragile_columns).  Computed on the device for all layers at once and read with ONE small device-to-host copy; None when the
+    mode keeps y anyway (f32) or there are no layers."""
+    layers = list(mod.encoder_layers.layers)
+    if not ln_from_out(dtype) or not layers:
+        return None
+    g = torch.stack([n.weight.detach() for L in layers for n in (L.norm1, L.norm2)])
+    b = torch.stack([n.bias.detach() for L in layers for n in (L.norm1, L.norm2)])
+    bad = ln_fragile_columns(g, b).any(1).view(len(layers), 2).any(1)
+    return tuple(bool(v) for v in bad.cpu().tolist())
+
+
 def linear_resid_ln_fwd(x, lin_w, lin_b, resid, norm, dtype, keep_y=True):
     """y = x @ W^T + b + resid ; t, mean, rstd = LayerNorm(y): fused where the shape and the reduction length allow, else the pair.
     keep_y=False: y is not needed afterwards (returned as None; the fused launch does not even store it)."""
@@ -251,14 +276,15 @@ def ln_bwd(dt, y, t, mean, rstd, norm, dxsum):
     return ops.layernorm_bwd(dt, y, mean, rstd, norm.weight.detach(), ensure_grad(norm.weight), ensure_grad(norm.bias), dxsum)
 
 
-def layer_fwd(t, L, n, s, h, dtype, save):
+def layer_fwd(t, L, n, s, h, dtype, save, force_keep_y=False):
+    """force_keep_y: the LayerNorms keep their input rows for the backward even where the mode would run it from the output (ln_keep_rows)."""
     at = L.self_attn
     qkv = linear_fwd(t, at.in_proj_weight, at.in_proj_bias, dtype)
     if FUSED_ATTENTION and ops.attention_fused_ok(qkv, s, h):
         a, p = ops.attention_fwd_fused(qkv, n, s, h)   # p = base-2 log-sum-exp rows (N*h, S)
     else:
         a, p = attention_fwd(qkv, n, s, h)             # p = probabilities (N*h, S, S)
-    keep_y = not (save and ln_from_out(dtype))
+    keep_y = force_keep_y or not (save and ln_from_out(dtype))
     y1, t1, mean1, rstd1 = linear_resid_ln_fwd(a, at.out_proj.weight, at.out_proj.bias, t, L.norm1, dtype, keep_y=keep_y)
     bits = None
     if save and DX_ON_WT and relu_bits_ok(t1.shape[0], L.linear1.weight.shape[0], t1.shape[1], dtype) and \
@@ -333,7 +359,7 @@ def set_row_grad_hint(dense, index, compact, nrows):
     """The producer of a row-sparse gradient announces it: `dense` (the tensor it returns to autograd) is zero outside the rows `index` (int64, device), whose
     values are compact[:nrows] (rows nrows.. of compact are zero)."""
     global _row_grad_hint
-    _row_grad_hint = (dense.data_ptr(), dense.numel(), index, compact, nrows)
+    _row_grad_hint = (weakref.ref(dense), dense._version, index, compact, nrows)
 
 
 def drop_row_grad_hint():
@@ -342,10 +368,12 @@ def drop_row_grad_hint():
 
 
 def take_row_grad_hint(dense):
-    """(index, compact, nrows) if `dense` is the announced tensor, else None; the announcement is consumed either way."""
+    """(index, compact, nrows) if `dense` is the announced tensor, unmodified, else None; the announcement is consumed either way.  The same tensor
+    OBJECT with the same version counter: a sum autograd formed with a second consumer's gradient may reuse the announced storage (out of place at
+    a recycled address, or in place), and is not row-sparse."""
     global _row_grad_hint
     h, _row_grad_hint = _row_grad_hint, None
-    if h is None or not ROW_SPARSE_LAST_LAYER or h[0] != dense.data_ptr() or h[1] != dense.numel():
+    if h is None or not ROW_SPARSE_LAST_LAYER or h[0]() is not dense or h[1] != dense._version:
         return None
     return h[2], h[3], h[4]
 
@@ -409,6 +437,13 @@ def layer_bwd_rows(dtc, index, nrows, L, saved, n, s, h, dtype, side=None, prev=
 def backbone_fwd(mod, x, mask, offsets, dtype, save):
     """x: uint8 (N,H,W,C) line images, or float32 (N,C,H,W) (the reference's model input).
     Returns (tokens (N*S, d) in `dtype`, saved activations or None)."""
+    keep = None
+    if save and ln_from_out(dtype):
+        # per-layer fallback to the input rows (ln_keep_rows), decided before the first launch; a captured step (Trainer(hip_graph=True))
+        # decides before capture / replay and pins the flags on the module
+        keep = getattr(mod, "ln_keep_rows_pinned", None)
+        if keep is None:
+            keep = ln_keep_rows(mod, dtype)
     P = mod.patch_size[1]
     tile = mod.mask_tile_device(x.device)
     if mask is not None:
@@ -434,8 +469,8 @@ def backbone_fwd(mod, x, mask, offsets, dtype, save):
     t, mean0, rstd0 = ops.layernorm_fwd(y0, mod.intermediate_norm.weight.detach(), mod.intermediate_norm.bias.detach(),
                                         mod.intermediate_norm.eps, pe=pe, offsets=offsets, S=s)
     layers = []
-    for L in mod.encoder_layers.layers:
-        t, sv = layer_fwd(t, L, n, s, mod.num_heads, dtype, save)
+    for i, L in enumerate(mod.encoder_layers.layers):
+        t, sv = layer_fwd(t, L, n, s, mod.num_heads, dtype, save, force_keep_y=keep is not None and keep[i])
         layers.append(sv)
     saved = (a0, y0, mean0, rstd0, layers, n, s) if save else None
     return t, saved

@@ -4,6 +4,7 @@ import time
 
 import torch
 
+from .. import functional as F
 from ..precision import autocast
 
 
@@ -103,11 +104,18 @@ class Trainer:
         """rows (optional, model.head_rows == "masked"): int64 device tensor of the flat positions with mask == 1."""
         if self.hip_graph and self.data_parallel is None and rows is None:
             tensors = [images, torch.as_tensor(labels).to(images.device), torch.as_tensor(mask).to(images.device)]
-            key = tuple((tuple(t.shape), t.dtype) for t in tensors) + (self.model.training,)
-            g = self._graphs.get(key)
-            if g is None:
-                g = self._graphs[key] = _StepGraph(self, tensors)
-            loss = g.replay(tensors)
+            # which layers keep their LayerNorm input rows (functional.ln_keep_rows) is baked into a captured graph: decided here, one graph each
+            bb = self.model.backbone
+            keep = F.ln_keep_rows(bb, torch.bfloat16 if self.bfloat16 else torch.float32)
+            key = tuple((tuple(t.shape), t.dtype) for t in tensors) + (self.model.training, keep)
+            bb.ln_keep_rows_pinned = keep
+            try:
+                g = self._graphs.get(key)
+                if g is None:
+                    g = self._graphs[key] = _StepGraph(self, tensors)
+                loss = g.replay(tensors)
+            finally:
+                bb.ln_keep_rows_pinned = None
         else:
             loss = self._forward_backward(images, labels, mask, rows)
         self.optimizer.step()

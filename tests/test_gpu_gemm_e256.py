@@ -445,6 +445,57 @@ def test_fused_input_gradient_layernorm_backward(e256, M, K):
         assert torch.equal(again, dx) and torch.equal(dg2, dg) and torch.equal(db2, db) and torch.equal(dxs2, dxs)
 
 
+def test_fused_layernorm_epilogues_with_trained_weights_within_rows_kept(e256):
+    """The n512 LayerNorm epilogues at weights as training leaves them (O.trained_layernorm_columns: |gamma| down to 1e-3 and 0 next to |beta| up
+    to 4).  Forward (pero_gemm_resid_layernorm): t within bf16 rounding of an f64 LayerNorm of the f64 product.  Backward: the fused input-gradient
+    + LayerNorm-backward launch (pero_gemm_resid_layernorm_bwd, from the output t) and the pair product + pero_layernorm_bwd_out, against the
+    rows-kept pair (product + pero_layernorm_bwd on the stored y), each against the f64 backward of the f64 rows, column by column: within
+    1.5 x the rows-kept error + the floors of tests/test_gpu_ops.py, except on columns for which the layer keeps its rows
+    (functional.ln_fragile_columns)."""
+    from oracle import pero_oracle as O
+    from pero_pretraining_amd import functional as F
+    ops = e256
+    M, K = 4096, 512
+    g = torch.Generator().manual_seed(31)
+    x = (torch.randn(M, K, generator=g) * 0.5).bfloat16()
+    w = (torch.randn(512, K, generator=g) * 0.05).bfloat16()
+    bias = torch.randn(512, generator=g) * 0.1
+    res = (torch.randn(M, 512, generator=g) * 2 + 0.3).bfloat16()
+    a = (torch.randn(M, K, generator=g) * 0.5).bfloat16()            # the upstream gradient's product: dt = a @ wt^T + res2
+    wt = (torch.randn(512, K, generator=g) * 0.05).bfloat16()
+    res2 = torch.randn(M, 512, generator=g).bfloat16()
+    gamma, beta = O.trained_layernorm_columns(512, 31)
+    y_ref = x.double() @ w.double().t() + bias.double() + res.double()
+    dt_ref = a.double() @ wt.double().t() + res2.double()
+    t_ref = O.layer_norm(y_ref, gamma.double(), beta.double())
+    ref = O.layer_norm_bwd_f64(y_ref, dt_ref, gamma)
+    cu = [t.cuda() for t in (x, w, bias, res, a, wt, res2, gamma, beta)]
+    xc, wc, bc, rc, ac, wtc, r2c, gc, btc = cu
+    y, t, mean, rstd = ops.gemm_resid_layernorm(xc, wc, bc, rc, gc, btc, 1e-5)
+    assert bool(((t.double().cpu() - t_ref).abs() <= 2 ** -8 * t_ref.abs() + 2 ** -6 * gamma.double().abs()).all())
+    dt = ops.gemm(ac, wtc, residual=r2c)
+    errs = {}
+    for path in ("rows_kept", "from_output", "fused_from_output"):
+        dg, db, dxs = (torch.zeros(512, device="cuda") for _ in range(3))
+        if path == "rows_kept":
+            dx = ops.layernorm_bwd(dt, y, mean, rstd, gc, dg, db, dxs)
+        elif path == "from_output":
+            dx = ops.layernorm_bwd_out(dt, t, rstd, gc, btc, dg, db, dxs)
+        else:
+            dx = ops.gemm_resid_layernorm_bwd(ac, wtc, r2c, t, rstd, gc, btc, dg, db, dxs)
+        assert bool(torch.isfinite(dx.float()).all()), path
+        errs[path] = O.layer_norm_bwd_column_errors(dx, dg, db, dxs, ref)
+    # (the rows-kept pair's own error: dt's and y's bf16 rounding against the f64 rows)
+    assert float(errs["rows_kept"]["dx"].max()) < 2 ** -4 and float(errs["rows_kept"]["dgamma"].max()) < 1e-2
+    floors = {"dx": 6e-3, "dgamma": 1.2e-2, "dbeta": 1e-4, "dxsum": 8e-3}   # = tests/test_gpu_ops.py LN_TRAINED_FLOORS
+    fragile = F.ln_fragile_columns(gamma, beta)
+    for path, e in errs.items():
+        for k, floor in floors.items():
+            cols = torch.nonzero((e[k] > 1.5 * errs["rows_kept"][k] + floor) & ~fragile).reshape(-1).tolist()
+            assert not cols, (path, k, [(j, round(float(gamma[j]), 4), round(float(beta[j]), 3), float(e[k][j]), float(errs["rows_kept"][k][j]))
+                                        for j in cols[:6]])
+
+
 def test_fused_linear_residual_layernorm_on_strided_operands(e256):
     """pero_gemm_resid_layernorm through the C ABI with every leading dimension larger than its row: A and the residual as column slices of
     wider matrices, Y and T written into column slices of wider buffers - the same bits as the contiguous call, the neighbouring columns

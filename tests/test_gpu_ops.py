@@ -382,6 +382,55 @@ def test_layernorm_bwd_from_output(ops, dtype, rows, d):
         assert rel_err(dg[keep.cuda()], dg2[keep.cuda()].cpu()) < 1e-4 and float(dg[3]) == 0.0
 
 
+# the from-output backward against the rows-kept one, per column: error <= 1.5 x the rows-kept error + these floors (dx: of the reference's RMS;
+# dgamma, dxsum: of the column's own scale - O.layer_norm_bwd_column_errors).  At |beta / gamma| <= functional.LN_FROM_OUT_MAX_RATIO the
+# from-output form stays inside them (worst 0.5 of the floor in an f32 emulation); a column beyond the ratio must be one the library routes to
+# the rows-kept backward (functional.ln_fragile_columns)
+LN_TRAINED_FLOORS = {"dx": 6e-3, "dgamma": 1.2e-2, "dbeta": 1e-4, "dxsum": 8e-3}
+
+
+def assert_ln_paths_within_rows_kept(errs, gamma, beta, what):
+    """errs: {path: per-column errors}, "rows_kept" among them.  Every column of every path within 1.5 x rows_kept + floor, unless the
+    library does not run that path for those weights (the layer keeps its input rows)."""
+    from pero_pretraining_amd import functional as F
+    fragile = F.ln_fragile_columns(gamma.cpu(), beta.cpu())
+    base = errs["rows_kept"]
+    for path, e in errs.items():
+        for k, floor in LN_TRAINED_FLOORS.items():
+            bad = (e[k] > 1.5 * base[k] + floor) & ~fragile
+            cols = torch.nonzero(bad).reshape(-1).tolist()
+            assert not cols, (what, path, k, [(j, round(float(gamma[j]), 4), round(float(beta[j]), 3), float(e[k][j]), float(base[k][j])) for j in cols[:6]])
+
+
+@pytest.mark.parametrize("rows,d", [(1024, 64), (300, 64), (4096, 512)])
+def test_layernorm_trained_weights_backward_from_output_within_rows_kept(ops, rows, d):
+    """LayerNorm weights as training leaves them (O.trained_layernorm_columns: |gamma| down to 1e-3 and 0 next to |beta| up to 4): forward
+    rows within bf16 rounding of an f64 LayerNorm of the f32 input rows; the bf16 backward from the output rows (pero_layernorm_bwd_out, what
+    the encoder layers run by default) against the rows-kept one (pero_layernorm_bwd), both against the f64 backward from the f32 rows,
+    column by column.  xhat = (t - beta) / gamma turns t's 2^-9 rounding into 2^-9 |beta / gamma|: a column past
+    functional.LN_FROM_OUT_MAX_RATIO must be one for which the layer keeps its rows, and the gamma == 0 column (whose dgamma the form drops) too."""
+    g = torch.Generator().manual_seed(7 * rows + d)
+    x = torch.randn(rows, d, generator=g) * 2 + 0.3
+    dy = torch.randn(rows, d, generator=g).bfloat16()
+    gamma, beta = O.trained_layernorm_columns(d, 7 * rows + d)
+    ref = O.layer_norm_bwd_f64(x, dy.float(), gamma)
+    t_ref = O.layer_norm(x.double(), gamma.double(), beta.double())
+    t, mean, rstd = ops.layernorm_fwd(dev(x.bfloat16()), dev(gamma), dev(beta), 1e-5)
+    # forward: t's rounding + the input rows' (2^-9 |x| rstd <= 2^-6 of xhat here) times |gamma|
+    assert bool(((t.double().cpu() - t_ref).abs() <= 2 ** -8 * t_ref.abs() + 2 ** -6 * gamma.double().abs()).all())
+    errs = {}
+    for path in ("rows_kept", "from_output"):
+        dg, db, dxs = (torch.zeros(d, device="cuda") for _ in range(3))
+        if path == "rows_kept":
+            dx = ops.layernorm_bwd(dev(dy), dev(x.bfloat16()), mean, rstd, dev(gamma), dg, db, dxs)
+        else:
+            dx = ops.layernorm_bwd_out(dev(dy), t, rstd, dev(gamma), dev(beta), dg, db, dxs)
+        assert bool(torch.isfinite(dx.float()).all())
+        errs[path] = O.layer_norm_bwd_column_errors(dx, dg, db, dxs, ref)
+    assert float(errs["rows_kept"]["dx"].max()) < 2 ** -5 and float(errs["rows_kept"]["dgamma"].max()) < 1e-2
+    assert_ln_paths_within_rows_kept(errs, gamma, beta, (rows, d))
+
+
 @pytest.mark.parametrize("rows,d", [(4096 + 13, 512), (8192, 256), (5000, 504)])
 def test_layernorm_fwd_four_rows_per_wave_equals_one_row_per_wave(ops, rows, d):
     """bf16, d <= 512, >= 4096 rows, no positional table: the four-rows-per-wave kernel - the rows, means and rstds it writes are those
