@@ -16,21 +16,8 @@
 #include "common.hpp"
 
 #define AT_HALF_BYTES 16384   // 64 rows x 256 B
-#ifndef AT_NO_PRIO
 #define AT_PRIO(n_) __builtin_amdgcn_s_setprio(n_)
-#else
-#define AT_PRIO(n_)
-#endif
 #define AT_SUB_BYTES 8192     // 32 rows x 256 B
-// Timing-only ablation builds of the backward kernels (tools/attn_ablate.sh; -DAT_ABL=mask, results wrong by design):
-//   1 no LDS-DMA inside the loops (the prologue's tiles are reused), 2 no exponentials, 4 no gradient MFMAs (dQ / dK / dV products),
-//   8 no output tiles (attn_store_tile), 16 no score MFMAs (S / dP), 32 output tiles staged but not stored, 64 no column sums (bias gradient)
-#ifndef AT_COLSUM_MFMA
-#define AT_COLSUM_MFMA 1   // column sums of the backward's output tiles by MFMA (0: round 3's vector-ALU sums + LDS reduction)
-#endif
-#ifndef AT_ABL
-#define AT_ABL 0
-#endif
 #define AT_DKV2_LDS (4 * AT_SUB_BYTES + 128 * 128 * 2 + 512)  // Q / dO stages x 2, V tile, row statistics x 2
 #define AT_TILE_BYTES (128 * 128 * 2)  // 32 KiB: 128 keys x 128 head-dim bf16
 
@@ -335,7 +322,7 @@ __device__ __forceinline__ bf8v img_tr_frag(const unsigned char* img, int rb, in
 // Software-pipelined operand reads (round 3).  hipcc compiles the loops above to  read -> s_waitcnt lgkmcnt(0) -> MFMA  pairs - one LDS
 // round trip exposed per one or two 32-cycle MFMAs - and, worse, puts an `s_waitcnt vmcnt(0)` in front of the first LDS read that
 // follows an LDS-DMA (it cannot tell the DMA's destination from the tile being read), which makes the "prefetch" of the next tile a
-// wait in the middle of the current one (ablation, tools/attn_ablate.py: the loop's DMA cost 24 % of the backward).  The `_p` bodies
+// wait in the middle of the current one (an ablation build: the loop's DMA cost 24 % of the backward).  The `_p` bodies
 // below issue every fragment read by inline asm the compiler neither waits for nor orders, SEVEN fragments ahead of the MFMA that
 // consumes them, each MFMA tied to a counted `s_waitcnt lgkmcnt(n)` through its fragment register (LDS operations retire in order,
 // so n = the LDS instructions issued after the fragment's own).  One sequence of reads runs through a whole LDS stage: the
@@ -419,13 +406,6 @@ __device__ __forceinline__ void at_wait_lgkm2(T& f, T& g) {
 // Image: 128 rows x 256 B, 8-byte granule index XORed with (row & 31): conflict-free ds_write_b64 and ds_read_b128.
 __device__ __forceinline__ void attn_store_tile(const f16v (&acc)[4], unsigned char* stg, bf16raw* out_base, long long ld,
                                                 float* colsum, int tid, int wave, int r, int h5) {
-  if (AT_ABL & 8) {  // timing-only: keep the accumulators alive, write nothing
-    float keep = 0.f;
-#pragma unroll
-    for (int dt = 0; dt < 4; dt++) keep += acc[dt][0] + acc[dt][15];
-    if (keep == 1.2345e-33f) out_base[0] = 1;
-    return;
-  }
   __syncthreads();  // the staging region is free (every wave is past its last tile read)
   const int row_w = wave * 32 + r;
 #pragma unroll
@@ -439,7 +419,6 @@ __device__ __forceinline__ void attn_store_tile(const f16v (&acc)[4], unsigned c
       *(uint2*)(stg + row_w * 256 + ((g ^ (row_w & 31)) << 3)) = w;
     }
   __syncthreads();
-#if AT_COLSUM_MFMA
   const int ch = tid & 15;
 #pragma unroll 2
   for (int i = 0; i < 8; i++) {
@@ -447,16 +426,15 @@ __device__ __forceinline__ void attn_store_tile(const f16v (&acc)[4], unsigned c
     const int x = row & 31;
     uint4 v = *(const uint4*)(stg + row * 256 + ((ch ^ (x >> 1)) << 4));
     if (x & 1) { const unsigned t0 = v.x, t1 = v.y; v.x = v.z; v.y = v.w; v.z = t0; v.w = t1; }
-    if (!(AT_ABL & 32)) *(uint4*)(out_base + (long long)row * ld + ch * 8) = v;
-    else if (v.x == 0x12345678u) out_base[0] = 1;   // timing-only build: the staged values stay live, nothing is stored
+    *(uint4*)(out_base + (long long)row * ld + ch * 8) = v;
   }
-  if (colsum && !(AT_ABL & 64)) {
+  if (colsum) {
     // Column sums of the staged tile (this (line, head) block's share of in_proj's bias gradient) on the MATRIX pipe, which idles through
     // the epilogue (round 4; lh_store_matrix's trick): wave w takes the 32 columns 32 w .., ones (32 x 16) times the 16 x 32 block of the
     // image read back TRANSPOSED (ds_read_b64_tr_b16: the row index becomes the MFMA's k - any order of the rows inside a k-step gives the
     // same sum), accumulated over the eight row blocks: every lane n then holds the sum of column 32 w + (n & 31), exact in f32, and writes
     // it - no cross-lane shuffles, no second pass through LDS, no barriers.  (As 128 vector adds + 16 shuffles per thread + an LDS
-    // reduction over the four waves behind two barriers the sums were 7 % of the backward: tools/attn_ablate.py, mask 64.)
+    // reduction over the four waves behind two barriers the sums were 7 % of the backward, measured by an ablation build.)
     const int lane = tid & 63;
     const int ti = lane & 15, tg = (lane >> 4) & 1;
     const int g = 8 * wave + 4 * tg + (ti & 3);                 // 8-byte granule (4 columns) this lane supplies
@@ -472,44 +450,6 @@ __device__ __forceinline__ void attn_store_tile(const f16v (&acc)[4], unsigned c
     }
     if (lane < 32) colsum[32 * wave + lane] = cs[0];
   }
-#else   // round 3: vector-ALU column sums (kept for the A/B: -DAT_COLSUM_MFMA=0)
-  const int ch = tid & 15;
-  float cs[8];  // column sums of this thread's 8 columns (chunk ch) over its 8 rows, taken from the values on their way out
-#pragma unroll
-  for (int e = 0; e < 8; e++) cs[e] = 0.f;
-#pragma unroll 2
-  for (int i = 0; i < 8; i++) {
-    const int row = (tid >> 4) + 16 * i;
-    const int x = row & 31;
-    uint4 v = *(const uint4*)(stg + row * 256 + ((ch ^ (x >> 1)) << 4));
-    if (x & 1) { const unsigned t0 = v.x, t1 = v.y; v.x = v.z; v.y = v.w; v.z = t0; v.w = t1; }
-    if (!(AT_ABL & 32)) *(uint4*)(out_base + (long long)row * ld + ch * 8) = v;
-    else if (v.x == 0x12345678u) out_base[0] = 1;   // timing-only build: the staged values stay live, nothing is stored
-    if (colsum && !(AT_ABL & 64)) {
-      const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int k = 0; k < 4; k++) { cs[2 * k] += __uint_as_float(w[k] << 16); cs[2 * k + 1] += __uint_as_float(w[k] & 0xffff0000u); }
-    }
-  }
-  if (colsum && !(AT_ABL & 64)) {
-    // the 16 threads with this chunk: lanes l, l ^ 16, l ^ 32, l ^ 48 of each wave (two exchanges per value), then the four waves
-    // through LDS; one partial row per workgroup and gradient, summed by attn_bias_reduce_k (atomics into the 128 addresses of a
-    // head from its 512 workgroups ran ~50 us longer per kernel than this)
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      cs[e] += __shfl_xor(cs[e], 16, 64);
-      cs[e] += __shfl_xor(cs[e], 32, 64);
-    }
-    __syncthreads();  // every thread is done reading the staged tile
-    float* red = (float*)stg;
-    if ((tid & 63) < 16) {
-#pragma unroll
-      for (int e = 0; e < 8; e++) red[wave * 128 + ch * 8 + e] = cs[e];
-    }
-    __syncthreads();
-    if (tid < 128) colsum[tid] = (red[tid] + red[128 + tid]) + (red[256 + tid] + red[384 + tid]);
-  }
-#endif
 }
 
 // dbias[which * d + head * 128 + c] += sum over the workgroups (line, block) of partial[which][(lh, blk)][c], lh = line * nh + head.
@@ -592,7 +532,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(unsigned char* smem, int lh, in
     __syncthreads();  // half hk landed; every wave is done with the other buffer
     const unsigned char* kimg = smem + (hk & 1) * 2 * AT_HALF_BYTES;
     const unsigned char* vimg = kimg + AT_HALF_BYTES;
-    if (hk + 1 < nhalf && !(AT_ABL & 1)) {
+    if (hk + 1 < nhalf) {
       unsigned char* nb = smem + ((hk + 1) & 1) * 2 * AT_HALF_BYTES;
       attn_glds_half(Kg + (long long)(hk + 1) * 64 * ld, ld, nb, wave, lane);
       attn_glds_half(Vg + (long long)(hk + 1) * 64 * ld, ld, nb + AT_HALF_BYTES, wave, lane);
@@ -602,14 +542,14 @@ __device__ __forceinline__ void attn_bwd_dq_body(unsigned char* smem, int lh, in
       f16v s = {0}, dp = {0};
       AT_PRIO(1);
 #pragma unroll
-      for (int ks = 0; ks < ((AT_ABL & 16) ? 1 : 8); ks++) {
+      for (int ks = 0; ks < 8; ks++) {
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_row_frag(kimg, t * 32 + r, ks, h5), qf[ks], s, 0, 0, 0);
         dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_row_frag(vimg, t * 32 + r, ks, h5), gf[ks], dp, 0, 0, 0);
       }
       AT_PRIO(0);
 #pragma unroll
       for (int e = 0; e < 16; e++) {
-        const float p = (AT_ABL & 2) ? fmaf(s[e], c, -lq) : __builtin_amdgcn_exp2f(fmaf(s[e], c, -lq));
+        const float p = __builtin_amdgcn_exp2f(fmaf(s[e], c, -lq));
         s[e] = p * (dp[e] - dsum) * scale;  // dS^T
       }
       AT_PRIO(1);
@@ -617,7 +557,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(unsigned char* smem, int lh, in
       for (int sub = 0; sub < 2; sub++) {
         const bf8v dsf = pack8(s, sub);
 #pragma unroll
-        for (int dt = 0; dt < ((AT_ABL & 4) ? 1 : 4); dt++)
+        for (int dt = 0; dt < 4; dt++)
           dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_tr_frag(kimg, t * 32 + sub * 16, dt, lane), dsf, dq[dt], 0, 0, 0);
       }
       AT_PRIO(0);
@@ -705,7 +645,7 @@ __device__ __forceinline__ void attn_bwd_dq_body_p(unsigned char* smem, int lh, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // half hk landed; every wave is done with the other buffer
     const unsigned stage = s0 + (hk & 1) * 2 * AT_HALF_BYTES;
-    if (hk + 1 < nhalf && !(AT_ABL & 1)) {
+    if (hk + 1 < nhalf) {
       unsigned char* nb = smem + ((hk + 1) & 1) * 2 * AT_HALF_BYTES;
       attn_glds_half(Kg + (long long)(hk + 1) * 64 * ld, ld, nb, wave, lane);
       attn_glds_half(Vg + (long long)(hk + 1) * 64 * ld, ld, nb + AT_HALF_BYTES, wave, lane);
@@ -815,7 +755,7 @@ __device__ __forceinline__ void attn_bwd_dkv2_body(unsigned char* smem, int lh, 
     const float* lds_l = lds_ld + (sq & 1) * 64;
     const float* lds_d = lds_l + 32;
     float nstat = 0.f;
-    if (sq + 1 < nsub && !(AT_ABL & 1)) {
+    if (sq + 1 < nsub) {
       if (tid < 64) nstat = stat[(sq + 1) * stat_step];  // before the DMA: vmcnt is in-order
       unsigned char* nb = smem + ((sq + 1) & 1) * 2 * AT_SUB_BYTES;
       attn_glds_sub(base + (long long)(sq + 1) * 32 * ld, ld, nb, wave, lane);
@@ -825,7 +765,7 @@ __device__ __forceinline__ void attn_bwd_dkv2_body(unsigned char* smem, int lh, 
     f16v s = {0}, dp = {0};
     AT_PRIO(1);
 #pragma unroll
-    for (int ks = 0; ks < ((AT_ABL & 16) ? 1 : 8); ks++) {
+    for (int ks = 0; ks < 8; ks++) {
       s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_row_frag(qimg, r, ks, h5), kf[ks], s, 0, 0, 0);
       dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_row_frag(gimg, r, ks, h5), img_row_frag(vimg, wave * 32 + r, ks, h5), dp, 0, 0, 0);
     }
@@ -836,7 +776,7 @@ __device__ __forceinline__ void attn_bwd_dkv2_body(unsigned char* smem, int lh, 
       const f4v d4 = *(const f4v*)(lds_d + 8 * g4 + 4 * h5);
 #pragma unroll
       for (int e = 0; e < 4; e++) {
-        const float p = (AT_ABL & 2) ? fmaf(s[4 * g4 + e], c, -l4[e]) : __builtin_amdgcn_exp2f(fmaf(s[4 * g4 + e], c, -l4[e]));
+        const float p = __builtin_amdgcn_exp2f(fmaf(s[4 * g4 + e], c, -l4[e]));
         s[4 * g4 + e] = p;                                         // P
         dp[4 * g4 + e] = p * (dp[4 * g4 + e] - d4[e]) * scale;     // dS
       }
@@ -846,7 +786,7 @@ __device__ __forceinline__ void attn_bwd_dkv2_body(unsigned char* smem, int lh, 
     for (int sub = 0; sub < 2; sub++) {
       const bf8v pf = pack8(s, sub), dsf = pack8(dp, sub);
 #pragma unroll
-      for (int dt = 0; dt < ((AT_ABL & 4) ? 1 : 4); dt++) {
+      for (int dt = 0; dt < 4; dt++) {
         dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_tr_frag(gimg, sub * 16, dt, lane), pf, dv[dt], 0, 0, 0);   // dV^T += dO^T P
         dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_tr_frag(qimg, sub * 16, dt, lane), dsf, dk[dt], 0, 0, 0);  // dK^T += Q^T dS
       }
@@ -923,7 +863,7 @@ __device__ __forceinline__ void attn_bwd_dkv2_body_p(unsigned char* smem, int lh
     const float* lds_l = lds_ld + (sq & 1) * 64;
     const float* lds_d = lds_l + 32;
     float nstat = 0.f;
-    if (sq + 1 < nsub && !(AT_ABL & 1)) {
+    if (sq + 1 < nsub) {
       if (tid < 64) nstat = stat[(sq + 1) * stat_step];  // before the DMA: vmcnt is in-order
       unsigned char* nb = smem + ((sq + 1) & 1) * 2 * AT_SUB_BYTES;
       attn_glds_sub(base + (long long)(sq + 1) * 32 * ld, ld, nb, wave, lane);
@@ -1068,7 +1008,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pair_k(const bf16raw* qkv, co
 // Backward of ONE (line, head) per workgroup pass, S = 256: persistent, eight waves, one workgroup per CU (round 3).
 //
 // What the two-workgroups-per-CU kernels above are bound by is neither MFMA nor LDS nor HBM bandwidth: with every MFMA or every
-// exponential compiled out they run at the same speed (tools/attn_ablate.py, realistic inputs: -1 %), while without the loop's LDS-DMA
+// exponential compiled out they run at the same speed (ablation builds, realistic inputs: -1 %), while without the loop's LDS-DMA
 // or without the output tiles they gain 11 % / 20 %.  They move 2.0 GB in ~740 us (2.7 TB/s) with at most one 32 KiB stage in flight per
 // workgroup, and every workgroup pays its first loads and its last stores in full: memory-level parallelism is the bound.  Here a
 // workgroup owns 128 KiB of LDS as a ring of four 32 KiB slots and streams a whole (line, head) through it with the loads THREE items
@@ -1183,7 +1123,7 @@ __device__ __forceinline__ void lh_wait_lgkm_plain() {
 //   * the column sums are MFMAs: ones (32 x 16) times the staged 16 x 32 tile read back TRANSPOSED (ds_read_b64_tr_b16: the row index
 //     becomes the MFMA's k), accumulated over the two row halves - every lane n then holds the sum of column n, exact in f32.  As
 //     cross-lane sums they cost 384 ds_bpermute per wave and unit through the CU's one LDS crossbar (10 us of a 52 us unit,
-//     tools/attn_lh_stamps.py), as DPP / v_permlane*_swap arithmetic ~450 vector instructions per matrix (8 us).
+//     in-kernel stamps), as DPP / v_permlane*_swap arithmetic ~450 vector instructions per matrix (8 us).
 __device__ __forceinline__ void lh_store_matrix(const f16v (&acc)[4], unsigned stg, unsigned part, void* obase, unsigned pitch_b, int lane) {
   // (every address below derives from this opaque copy of the lane index: otherwise the compiler computes them once in front of the unit
   //  loop, finds no registers for them and reloads them from scratch inside the epilogue - behind an `s_waitcnt vmcnt(0)` that also waits
@@ -1230,12 +1170,8 @@ __device__ __forceinline__ void lh_store_matrix(const f16v (&acc)[4], unsigned s
     constexpr int rd = decltype(rc_)::value;
     constexpr int ch = rd >> 1, rh = rd & 1;
     void* ob = (unsigned char*)obase + (long long)(16 * rh) * pitch_b;
-#ifndef LH_ABL_NOSTORE   // (timing-only ablation: tools/attn_lh_stamps.py)
     lh_gstore16<ch * 128>(v0[rd], ob, go);
     lh_gstore16<ch * 128>(v1[rd], (unsigned char*)ob + 8LL * pitch_b, go);
-#else
-    asm volatile("" :: "v"(v0[rd]), "v"(v1[rd]), "s"(ob), "v"(go));
-#endif
     if constexpr (rh == 0) {
       cs0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, t0[rd], (f16v){0}, 0, 0, 0);
       cs1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, t1[rd], (f16v){0}, 0, 0, 0);
@@ -1282,16 +1218,6 @@ __device__ __forceinline__ constexpr int lh_q_after(int j) {   // LDS instructio
   for (int k = j + 1; k <= j + LH_QPOOL - 1 && k < 48; k++) n += dq_ninstr(k);
   return n;
 }
-// timing-only ablation builds of attn_bwd_lh_k (tools/attn_lh_stamps.py; results wrong by design): -DLH_ABL=mask: 1 no LDS-DMA, 2 no MFMAs,
-// 4 no fragment loads from global memory; -DLH_ABL_NOSTORE: no output stores
-#ifndef LH_ABL
-#define LH_ABL 0
-#endif
-#if LH_ABL & 2
-#define LH_MFMA(a_, b_, c_, x_, y_, z_) (c_)
-#else
-#define LH_MFMA(a_, b_, c_, x_, y_, z_) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_, b_, c_, x_, y_, z_)
-#endif
 __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, const bf16raw* dout, const float* lse2, const float* dvec, bf16raw* dqkv,
                                                         float* work, int nunits, int nh, float c, float scale) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1339,8 +1265,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
   float lq, dsum;
   // F: this lane's Q / dO row fragments, lse and D of unit u  [18]
   auto issue_F = [&](const bf16raw* q_, const bf16raw* g_, const float* l_, const float* d_) {
-    if (LH_ABL & 4) { asm volatile("" : "=v"(qf[0]), "=v"(qf[1]), "=v"(qf[2]), "=v"(qf[3]), "=v"(qf[4]), "=v"(qf[5]), "=v"(qf[6]), "=v"(qf[7]));
-                      asm volatile("" : "=v"(gf[0]), "=v"(gf[1]), "=v"(gf[2]), "=v"(gf[3]), "=v"(gf[4]), "=v"(gf[5]), "=v"(gf[6]), "=v"(gf[7]), "=v"(lq), "=v"(dsum)); return; }
     at_static_for<0, 8>([&](auto kc) __attribute__((always_inline)) { constexpr int ks = decltype(kc)::value; lh_gload16<32 * ks>(qf[ks], q_, fq_off); });
     at_static_for<0, 8>([&](auto kc) __attribute__((always_inline)) { constexpr int ks = decltype(kc)::value; lh_gload16<32 * ks>(gf[ks], g_, fg_off); });
     lh_gload4(lq, l_, (unsigned)(32 * wave + r) * 4);
@@ -1348,7 +1272,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
   };
   // H_h: K rows 64h..64h+63 -> slot h + 0, V rows -> slot h + 16384  [4]
   auto issue_H = [&](const bf16raw* q_, int h) {
-    if (LH_ABL & 1) return;
     const unsigned char* kb = (const unsigned char*)(q_ + d) + (long long)h * 64 * pq;
     const unsigned char* vb = (const unsigned char*)(q_ + 2 * d) + (long long)h * 64 * pq;
     const unsigned dst = s0 + h * LH_SLOT + ddst;
@@ -1359,7 +1282,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
   };
   // V_i: V rows 128i..128i+127 -> slot i  [4]
   auto issue_V = [&](int i) {
-    if (LH_ABL & 1) return;
     const unsigned char* vb = (const unsigned char*)(uq + 2 * d) + (long long)i * 128 * pq;
     const unsigned dst = s0 + i * LH_SLOT + ddst;
 #pragma unroll
@@ -1368,7 +1290,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
   // T_j: Q rows 32j..32j+31 -> sub-slot j & 3, dO rows -> + 8192, statistics -> LH_STATS + 256 (j & 3)  [3]
   const float* stat_lane = nullptr;   // set per unit: lanes 0-31 -> lse2[q], lanes 32-63 -> D[q]
   auto issue_T = [&](int j) {
-    if (LH_ABL & 1) return;
     const long long stat_step = lane < 32 ? 32 : 32LL * nh;
     const unsigned sub = s0 + 2 * LH_SLOT + (j & 3) * 16384;
     lh_dma16((const unsigned char*)uq + (long long)j * 32 * pq, dq_off, sub + ddst);
@@ -1376,22 +1297,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
     lh_dma4(stat_lane + j * stat_step, s0 + LH_STATS + (j & 3) * 256);
   };
   auto issue_KF = [&]() {   // K row fragments of this lane's key  [8]
-    if (LH_ABL & 4) { asm volatile("" : "=v"(kf[0]), "=v"(kf[1]), "=v"(kf[2]), "=v"(kf[3]), "=v"(kf[4]), "=v"(kf[5]), "=v"(kf[6]), "=v"(kf[7])); return; }
     at_static_for<0, 8>([&](auto kc) __attribute__((always_inline)) { constexpr int ks = decltype(kc)::value; lh_gload16<32 * ks>(kf[ks], uq + d, fq_off); });
   };
 
-  // Diagnostic build (-DLH_STAMP, tools/attn_lh_stamps.py): s_memtime of wave 0 at up to 64 points of the workgroup's THIRD unit, through LDS
-  // (a global store would enter the counted vmcnt stream) -> the upper half of `work` as u64 [workgroup][64] at the end of the kernel
-#ifdef LH_STAMP
-  int stamp_unit = 0;
-#define LH_ST(n_)                                                                                                   \
-  if (stamp_unit == 2 && tid == 0) {                                                                                \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                                     \
-    lh_ds_write8(s0 + LH_LDS_BYTES + 8 * (n_), __builtin_bit_cast(at_u2v, t_));                                     \
-  }
-#else
-#define LH_ST(n_)
-#endif
   // bias-gradient partials of a finished unit: the eight waves' rows summed in wave order -> work[which][unit][128]; called behind a barrier
   // that every wave passes after its epilogue K.  One store per thread (threads 384..511 repeat the first 128: one count for all waves).
   auto reduce_partials = [&](int un) {
@@ -1424,7 +1332,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
     for (int t = 0; t < 4; t++) dq[t] = (f16v){0};
     at_static_for<0, 4>([&](auto hc) __attribute__((always_inline)) {
       constexpr int h = decltype(hc)::value;
-      LH_ST(3 * h);
       if constexpr (h == 0) {
         // F and - older - H0..H3 (steady state: newer are the 8 dV stores; a workgroup's first unit issued H0..H3 behind F: wait for all)
         lh_wait_vm2<8, 0>(first);
@@ -1438,7 +1345,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
         // exponentials run under the other's MFMAs (s_setprio 1 inside the clusters keeps them apart)
         if (LH_STAGGER && wave >= 4) __builtin_amdgcn_s_sleep(LH_STAGGER);
       }
-      LH_ST(3 * h + 1);
       unsigned stage = s0 + h * LH_SLOT;
       asm volatile("" : "+s"(stage));       // (opaque: the address registers below belong to this half only)
       // the fragment addresses of this half in registers: computing them in front of every read (xor + add per LDS instruction) made the
@@ -1482,29 +1388,26 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
         at_wait_lgkm<lh_q_after(j)>(fr[j % LH_QPOOL]);
         if constexpr (qd < 16) {
           constexpr int ks = qd >> 1;
-          if constexpr (qd == 0) s = LH_MFMA(fr[j % LH_QPOOL], qf[0], (f16v){0}, 0, 0, 0);
-          else if constexpr (qd == 1) dp = LH_MFMA(fr[j % LH_QPOOL], gf[0], (f16v){0}, 0, 0, 0);
-          else if constexpr ((qd & 1) == 0) s = LH_MFMA(fr[j % LH_QPOOL], qf[ks], s, 0, 0, 0);
-          else dp = LH_MFMA(fr[j % LH_QPOOL], gf[ks], dp, 0, 0, 0);
+          if constexpr (qd == 0) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[j % LH_QPOOL], qf[0], (f16v){0}, 0, 0, 0);
+          else if constexpr (qd == 1) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[j % LH_QPOOL], gf[0], (f16v){0}, 0, 0, 0);
+          else if constexpr ((qd & 1) == 0) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[j % LH_QPOOL], qf[ks], s, 0, 0, 0);
+          else dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[j % LH_QPOOL], gf[ks], dp, 0, 0, 0);
         } else {
           constexpr int sub = (qd - 16) >> 2, dt = (qd - 16) & 3;
-          dq[dt] = LH_MFMA(fr[j % LH_QPOOL], dsf[sub], dq[dt], 0, 0, 0);
+          dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[j % LH_QPOOL], dsf[sub], dq[dt], 0, 0, 0);
         }
       });
       AT_PRIO(0);
-      LH_ST(3 * h + 2);
     });
     lh_barrier();                    // every wave is done with the four halves
-    LH_ST(12);
     // phase K's first items go out here, in front of the dQ epilogue (refilling the slots half by half would need a barrier per half:
-    // 0.9 us of wave skew each, tools/attn_lh_stamps.py)
+    // 0.9 us of wave skew each, measured by in-kernel stamps)
     issue_V(0); issue_V(1);
     issue_KF();
     issue_T(0); issue_T(1); issue_T(2); issue_T(3);
     // dQ rows of this wave: dqkv[(line * S + 32 * wave + row)][head * 128 ..]
     bf16raw* uo = dqkv + (uq - qkv);
     lh_store_matrix(dq, stg, part, (unsigned char*)uo + (long long)(32 * wave) * pq, pq, lane);   // [8]
-    LH_ST(13);
 
     // ============================== phase K ==============================
     f16v dv[4], dk[4];
@@ -1516,14 +1419,12 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
     asm volatile("" : "+v"(kf[0]), "+v"(kf[1]), "+v"(kf[2]), "+v"(kf[3]), "+v"(kf[4]), "+v"(kf[5]), "+v"(kf[6]), "+v"(kf[7]) :: "memory");
 #pragma unroll 1
     for (int j8 = 0; j8 < 8; j8++) {
-      LH_ST(14 + 3 * j8);
       if (j8 == 0) lh_wait_vm<17>();
       else if (j8 <= 3) lh_wait_vm<14>();
       else if (j8 <= 5) lh_wait_vm<6>();
       else if (j8 == 6) lh_wait_vm<3>();
       else lh_wait_vm<0>();
       lh_barrier();
-      LH_ST(15 + 3 * j8);
       if (j8 >= 1 && j8 <= 4) issue_T(j8 + 3);
       if (LH_STAGGER_K && wave >= 4) __builtin_amdgcn_s_sleep(LH_STAGGER_K);
       const unsigned stage = s0 + 2 * LH_SLOT + (j8 & 3) * 16384;
@@ -1546,13 +1447,13 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
         constexpr int after = (24 - 1 - j) < (LH_KPOOL - 2) ? (24 - 1 - j) : (LH_KPOOL - 2);
         if constexpr (kind == 0) {
           at_wait_lgkm<after>(fr[j % LH_KPOOL]);
-          if constexpr (ks == 0) s = LH_MFMA(fr[j % LH_KPOOL], kf[0], (f16v){0}, 0, 0, 0);
-          else s = LH_MFMA(fr[j % LH_KPOOL], kf[ks], s, 0, 0, 0);
+          if constexpr (ks == 0) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[j % LH_KPOOL], kf[0], (f16v){0}, 0, 0, 0);
+          else s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[j % LH_KPOOL], kf[ks], s, 0, 0, 0);
         } else if constexpr (kind == 2) {
           at_wait_lgkm<after>(fr[j % LH_KPOOL]);
           asm volatile("" : "+v"(fr[(j - 1) % LH_KPOOL]));
-          if constexpr (ks == 0) dp = LH_MFMA(fr[(j - 1) % LH_KPOOL], fr[j % LH_KPOOL], (f16v){0}, 0, 0, 0);
-          else dp = LH_MFMA(fr[(j - 1) % LH_KPOOL], fr[j % LH_KPOOL], dp, 0, 0, 0);
+          if constexpr (ks == 0) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[(j - 1) % LH_KPOOL], fr[j % LH_KPOOL], (f16v){0}, 0, 0, 0);
+          else dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[(j - 1) % LH_KPOOL], fr[j % LH_KPOOL], dp, 0, 0, 0);
         }
       });
       AT_PRIO(0);
@@ -1598,14 +1499,12 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
         if constexpr (m + (LH_KPOOL - 1) < 16) issue_t(std::integral_constant<int, m + (LH_KPOOL - 1)>{});
         constexpr int after = 2 * ((16 - 1 - m) < (LH_KPOOL - 1) ? (16 - 1 - m) : (LH_KPOOL - 1));
         at_wait_lgkm<after>(fr[m % LH_KPOOL]);
-        if constexpr (kind == 0) dv[dt] = LH_MFMA(fr[m % LH_KPOOL], pf[sub], dv[dt], 0, 0, 0);
-        else dk[dt] = LH_MFMA(fr[m % LH_KPOOL], dsf[sub], dk[dt], 0, 0, 0);
+        if constexpr (kind == 0) dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[m % LH_KPOOL], pf[sub], dv[dt], 0, 0, 0);
+        else dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[m % LH_KPOOL], dsf[sub], dk[dt], 0, 0, 0);
       });
       AT_PRIO(0);
-      LH_ST(16 + 3 * j8);
     }
     lh_barrier();                    // every wave is done with the ring
-    LH_ST(38);
     const int ucur = u;
     set_unit(has_next ? u + G : u);
     if (has_next) {
@@ -1616,16 +1515,10 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
     // are issued unconditionally (a workgroup's last unit re-reads its own rows): a definition under `if (has_next)` keeps the old
     // fragments alive through phase K in the register allocator's eyes - 64 registers spilled and reloaded per unit
     lh_store_matrix(dk, stg, part + 512, (unsigned char*)(uo + d) + (long long)(32 * wave) * pq, pq, lane);       // [8]
-    LH_ST(39);
     issue_F(uq, ug, ul, ud);
     lh_store_matrix(dv, stg, part + 1024, (unsigned char*)(uo + 2 * d) + (long long)(32 * wave) * pq, pq, lane);  // [8]
-    LH_ST(40);
     lh_wait_lgkm_plain<0>();         // this wave's partial rows are in LDS: the next barrier publishes them (reduce_partials)
     uprev = ucur;
-    LH_ST(41);
-#ifdef LH_STAMP
-    stamp_unit++;
-#endif
     if (!has_next) break;
     u += G;
     first = false;
@@ -1633,16 +1526,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_lh_k(const bf16raw* qkv, cons
   lh_barrier();
   reduce_partials(uprev);
   lh_wait_vm<0>();
-#ifdef LH_STAMP
-  if (tid < 64) {
-    float lo, hi;
-    lh_ds_read4(lo, s0 + LH_LDS_BYTES + 8 * tid);
-    lh_ds_read4(hi, s0 + LH_LDS_BYTES + 8 * tid + 4);
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi) :: "memory");
-    float* dbg = work + 3LL * nunits * 128 + ((long long)blockIdx.x * 64 + tid) * 2;
-    dbg[0] = lo; dbg[1] = hi;
-  }
-#endif
 }
 
 // ---- forward, pipelined operand reads (round 3; see the note in front of the `_p` backward bodies).  hipcc's schedule of attn_fwd_k
@@ -1858,15 +1741,10 @@ extern "C" int pero_attention_bwd(const void* qkv, const void* out, const void* 
   dim3 grid((unsigned)(N * num_heads * (S / 128))), block(256);
   if (!out && g_attn_bwd_pair && g_attn_lh && S == 256 && dbias && N * num_heads < (1LL << 20) && num_heads <= 1024) {   // (32-bit byte offsets inside a unit and inside the partial-sum workspace)
     // one persistent workgroup per CU, a (line, head) per pass (attn_bwd_lh_k); its bias partials: one row per unit
-#ifdef LH_STAMP
-#define LH_LAUNCH_LDS (LH_LDS_BYTES + 512)
-#else
-#define LH_LAUNCH_LDS LH_LDS_BYTES
-#endif
-    PERO_LDS_ATTR(attn_bwd_lh_k, LH_LAUNCH_LDS);
+    PERO_LDS_ATTR(attn_bwd_lh_k, LH_LDS_BYTES);
     const long long units = N * num_heads;
     const int cus = pero_num_cus();
-    hipLaunchKernelGGL(attn_bwd_lh_k, dim3((unsigned)(units < cus ? units : cus)), dim3(512), LH_LAUNCH_LDS, st, (const bf16raw*)qkv, (const bf16raw*)dout, lse,
+    hipLaunchKernelGGL(attn_bwd_lh_k, dim3((unsigned)(units < cus ? units : cus)), dim3(512), LH_LDS_BYTES, st, (const bf16raw*)qkv, (const bf16raw*)dout, lse,
                        (const float*)dvec, (bf16raw*)dqkv, work, (int)units, (int)num_heads, c, scale);
     hipLaunchKernelGGL(attn_bias_reduce_k, dim3((unsigned)num_heads, 3, N >= 4096 ? 128 : N >= 1024 ? 64 : 16), dim3(128), 0, st, work, dbias, (int)N, (int)num_heads, 1);
     PERO_CHECK_LAUNCH("pero_attention_bwd");

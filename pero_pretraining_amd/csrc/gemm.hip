@@ -365,7 +365,6 @@ __global__ __launch_bounds__(256) void gemm_generic(GemmP p) {
 //         * other stored products -> gemm_bf16_r256 (256x128x32, two workgroups per CU: small batches) when M is a multiple
 //           of 256, else the persistent 128x128x64 kernel of this file (also: batched products, PERO_GEMM_TILE128);
 //   forcing one family for A/B runs and tests: 1 = 128x128x64 persistent, 4 = o128, 7 = r256, 20 = e256 (any tile count).
-extern int g_gemm_e_var;
 extern int g_attn_bwd_pair;           // attention.hip
 extern int g_attn_pipe;
 extern int g_attn_order;
@@ -383,7 +382,6 @@ static int g_splitk_nearest = 0;
 int g_pero_splitk_xcd = 1;            // one k-slice per XCD where the slice count allows it (gemm_o.hip)
 extern "C" int pero_set_option(const char* name, int value) {
   if (name && !strcmp(name, "gemm_policy")) { g_gemm_policy = value; return PERO_OK; }
-  if (name && !strcmp(name, "gemm_e_var")) { g_gemm_e_var = value; return PERO_OK; }
   if (name && !strcmp(name, "attn_bwd_pair")) { g_attn_bwd_pair = value; return PERO_OK; }
   if (name && !strcmp(name, "attn_pipe")) { g_attn_pipe = value; return PERO_OK; }
   if (name && !strcmp(name, "attn_order")) { g_attn_order = value; return PERO_OK; }
@@ -536,7 +534,7 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const float* bia
     const bool auto_or = g_gemm_policy == 0;
     // the eight-phase persistent 256x256x64 kernel (gemm_e.hip): split-K weight gradients on long reductions ...
     if (atomic && out_dtype == PERO_F32 && batch == 1 && splitk_takes_e256(M, N, K, flags) &&
-        pero_launch_gemm_e256(p, batch, k_split_req, ta, tb, true, st, -1, workspace, workspace_bytes)) {
+        pero_launch_gemm_e256(p, batch, k_split_req, ta, tb, true, st, workspace, workspace_bytes)) {
       PERO_CHECK_LAUNCH("pero_gemm(e256 split-K)");
       return PERO_OK;
     }
@@ -554,12 +552,11 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const float* bia
     }
     // ... and stored bf16 products with every fused epilogue
     if (!atomic && can256 && (g_gemm_policy == 20 || (auto_or && (force256 || (g_gemm_e256_min > 0 && t256 >= g_gemm_e256_min)))) &&
-        pero_launch_gemm_e256(pc, batch, k_split, ta, tb, out_dtype == PERO_F32, st, -1)) {
+        pero_launch_gemm_e256(pc, batch, k_split, ta, tb, out_dtype == PERO_F32, st)) {
       *colsum_fused = want_cs;
       PERO_CHECK_LAUNCH("pero_gemm(e256)");
       return PERO_OK;
     }
-    PERO_REQUIRE(!(g_gemm_policy == 20 && (g_gemm_e_var & (8 | 64 | 128))), "pero_gemm: the stamp build did not take this product");  // its `gate` is a debug buffer
     if (atomic && k_split == 0) {
       long long ks = (g_splitk_items + t128 - 1) / t128;
       if (ks > K / 512) ks = K / 512;

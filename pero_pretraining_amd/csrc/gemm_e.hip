@@ -19,11 +19,12 @@
 //    stream, so the pipeline never refills.  vmcnt is ONE in-order counter for LDS-DMA, loads and stores: the last
 //    half tile the next tile needs before its second K-tile (A1 of K-tile 1) is issued AHEAD of the epilogue's stores, and
 //    the first K-tile's wait counts them out - the stores then have two K-tiles of main loop to drain.
-//  * Epilogue straight from the accumulators (no LDS memory): operands are swapped in the MFMA so that a lane owns 4 consecutive
+//  * Epilogue straight from the accumulators: operands are swapped in the MFMA so that a lane owns 4 consecutive
 //    output columns of one row; v_permlane16_swap between the two 16 x 16 tiles of a 32-column block gives it 8 consecutive
-//    columns (16 bytes), and ONE lane transpose (4 x ds_bpermute_b32) moves the four 16-byte pieces of a row from lanes 16 apart
-//    onto four ADJACENT lanes before the store: the memory pipeline merges adjacent lanes only, and a 1 KiB store whose adjacent
-//    lanes sit on different rows is 64 separate requests (64 instead of 16 cycles of the CU's store path; tools/probe_store3.hip).
+//    columns (16 bytes), and ONE lane transpose (through a wave-private LDS staging image) moves the four 16-byte pieces of a
+//    row from lanes 16 apart onto four ADJACENT lanes before the store: the memory pipeline merges adjacent lanes only, and a
+//    1 KiB store whose adjacent lanes sit on different rows is 64 separate requests (64 instead of 16 cycles of the CU's store
+//    path; tools/probe_store3.hip).
 //    Side inputs (residual rows, the second matrix of the row dots, the ReLU bit mask) are fetched in that transposed layout by
 //    inline-asm buffer loads the compiler does not count: half of them in phase 4 of the tile's last K-tile, half at the start
 //    of the epilogue, each waited for by a counted vmcnt.  The bias comes from a per-wave 1 KiB LDS copy of the tile's bias row,
@@ -32,7 +33,7 @@
 //    are bit-identical across kernels, i.e. across batch sizes.
 //  * Both wave groups run their epilogues side by side: waves 0-3 take one extra barrier at the epilogue's start (waves 4-7 finish
 //    their last MFMA cluster meanwhile), waves 4-7 one in front of the next tile, which staggers the groups again.  Staggered
-//    through the epilogue, each group sat at a barrier through the other's epilogue (tools/gemm_e_ktiles.py).
+//    through the epilogue, each group sat at a barrier through the other's epilogue.
 #include "gemm_common.hpp"
 #include <type_traits>
 #include <vector>
@@ -44,12 +45,10 @@
 #define E_KTILE (4 * E_HALF)       // A0 A1 B0 B1
 #define E_RING (2 * E_KTILE)       // 128 KiB: two K-tiles
 #define E_BIAS E_RING              // 8 x 1 KiB: each wave's copy of the tile's 256 bias floats
-#define E_LUT (E_RING + 8192 + 512)           // EP_GATE_BITS: 256 x 16 B, mask byte -> the four AND masks of its 8 bf16 columns
-#define E_XSTG (E_RING + 8192 + 512 + 4096)    // 8 x 2 KiB: each wave's staging image of the epilogue's lane transpose
-#define E_LDS_BYTES (E_XSTG + 8 * 2048)        // + 512 B of phase stamps (diagnostic build VAR 64) + the LUT + the staging
-#ifndef E_XCHG_LDS
-#define E_XCHG_LDS 1                           // 0: the lane transpose as 4 x ds_bpermute_b32 per unit (round 2)
-#endif
+#define E_PAD (E_BIAS + 8192)      // 512 B unused: the layout below is the one every measurement was taken with
+#define E_LUT (E_PAD + 512)        // EP_GATE_BITS: 256 x 16 B, mask byte -> the four AND masks of its 8 bf16 columns
+#define E_XSTG (E_LUT + 4096)      // 8 x 2 KiB: each wave's staging image of the epilogue's lane transpose
+#define E_LDS_BYTES (E_XSTG + 8 * 2048)
 
 // epilogue modes
 #define EP_PLAIN 0       // bias
@@ -141,8 +140,6 @@ __device__ __forceinline__ ei4v ersrc(const void* base, unsigned bytes) {
 // other row groups, run-to-run different (E_BLOAD16 has had its s_nop 4 for the same reason)
 #define E_BSTORE16(src_, voff_, rs_, soff_, imm_) \
   asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen offset:%4\n\ts_nop 2" :: "v"(src_), "v"(voff_), "s"(rs_), "s"(soff_), "i"(imm_) : "memory")
-#define E_BSTORE16_NT(src_, voff_, rs_, soff_, imm_) \
-  asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen offset:%4 nt\n\ts_nop 2" :: "v"(src_), "v"(voff_), "s"(rs_), "s"(soff_), "i"(imm_) : "memory")
 #define E_WAIT8(n_, r_) \
   asm volatile("s_waitcnt vmcnt(%8)" : "+v"(r_[0]), "+v"(r_[1]), "+v"(r_[2]), "+v"(r_[3]), "+v"(r_[4]), "+v"(r_[5]), "+v"(r_[6]), "+v"(r_[7]) : "i"(n_) : "memory")
 #define E_WAIT4(n_, r_) \
@@ -153,14 +150,7 @@ template <int EPI> struct ECnt {
   // next tile's K-tile 1], side loads of rows 64-127, then the stores / atomics of the two halves
   static constexpr int L0 = (EPI == EP_RESID || EPI == EP_ROWDOT) ? 8 : 0;  // (EP_GATE_BITS: its 8 mask loads go out in phase 1 of the last K-tile, ahead of A1(t+1): every later wait retires them)
   static constexpr int L1 = L0;
-#ifndef E_DUP
-#define E_DUP 0    // timing probe (-DE_DUP=1): every B0 half tile is requested twice - ten LDS-DMA instructions per wave and K-tile instead of eight, the
-#endif             // load of the row-complete 128 x 512 tile of DESIGN.md "what comes next"; every counted wait leaves two more operations in flight
-#define E_DX (2 * E_DUP)
-#ifndef E_ABL
-#define E_ABL 0    // timing-only ablation builds (results wrong by design): 1 no bit-mask stores (ReLU + bits), 2 no bit-mask loads (gate)
-#endif
-  static constexpr int S_HALF = 8 + ((EPI == EP_RELU_BITS && !(E_ABL & 1)) ? 4 : 0) + (EPI == EP_ROWDOT ? 4 : 0);
+  static constexpr int S_HALF = 8 + (EPI == EP_RELU_BITS ? 4 : 0) + (EPI == EP_ROWDOT ? 4 : 0);
 };
 
 // Work-item order for split-K slice counts that are no multiple of 8 (e.g. 12 tiles x 21 slices).  Workgroup T runs on XCD T & 7;
@@ -189,7 +179,7 @@ __device__ __forceinline__ void esplitk_xcd_item(int T, int tiles, int nsl, int&
   id = kk % tiles;
 }
 
-template <bool TA, bool TB, int EPI, int VAR>
+template <bool TA, bool TB, int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef ECnt<EPI> CN;
@@ -316,11 +306,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
   // one; a workgroup's last tile "prefetches" its own first K-tiles again: the stream keeps its shape, no branches)
   const EStep<TA, 64> sa(p.lda);
   const EStep<TB, 32> sb(p.ldb);
-  // (ks & 32, timing probe for stored products: every tile reads its A rows from the first 4096 rows - always in L2 -, results wrong by design)
-  const long long amask = (EPI != EP_SPLITK && (ks & 32)) ? 4095 : -1LL;
-  const unsigned char* cA = (const unsigned char*)A + (tm0 & amask) * sa.tile + (kbeg / E_BK) * sa.ktile;
+  const unsigned char* cA = (const unsigned char*)A + tm0 * sa.tile + (kbeg / E_BK) * sa.ktile;
   const unsigned char* cB = (const unsigned char*)B + tn0 * sb.tile + (kbeg / E_BK) * sb.ktile;
-  const unsigned char* nA = (const unsigned char*)A + (nm0 & amask) * sa.tile;
+  const unsigned char* nA = (const unsigned char*)A + nm0 * sa.tile;
   const unsigned char* nB = (const unsigned char*)B + nn0 * sb.tile;
   auto issue = [&](int u, int which, unsigned char* ktbase) {
     if (EPI == EP_SPLITK && u >= nk) return;  // one work item: nothing follows (the ring is the epilogue's staging area)
@@ -329,7 +317,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
     unsigned char* dst = ktbase + which * E_HALF + wave * 1024;
     if (which < 2) eglds2((nx ? nA : cA) + uu * sa.ktile + which * sa.half, sa.piece, offA, dst);
     else eglds2((nx ? nB : cB) + uu * sb.ktile + (which - 2) * sb.half, sb.piece, offB, dst);
-    if (E_DUP && which == 2) eglds2((nx ? nB : cB) + uu * sb.ktile + (which - 2) * sb.half, sb.piece, offB, dst);   // timing probe: the same half tile again
   };
   const bool use_bias = (EPI <= EP_RELU_BITS) && p.bias;
   unsigned char* const biasl = smem + E_BIAS + wave * 1024;
@@ -339,15 +326,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
                                      (__attribute__((address_space(3))) void*)(biasl), 16, 0, 0);
   };
 
-  if (VAR & 2) {
-    // de-phase the workgroups: all tiles take the same time, so without this every CU reaches its epilogue (128 KiB of
-    // stores) at the same moment.  Workgroups that stream the same A panel (ntn consecutive ones of an XCD) stay together.
-    const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3, per = (G >> 3);
-    const int ngr = (per + ntn - 1) / ntn, gr = loc / ntn;
-    const int period = nk * 2900 + 6000;                       // cycles per tile, roughly
-    const int delay = (int)((long long)period * (gr * 8 + xcd) / (ngr * 8));
-    for (int i = 0; i < delay; i += 1024) __builtin_amdgcn_s_sleep(16);
-  }
   if (EPI == EP_GATE_BITS) {
     // bit e of a mask byte keeps column e of the lane's 8: dword k holds columns 2k (low half) and 2k + 1
     if (tid < 256) {
@@ -361,37 +339,22 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
   // ---- prologue: K-tile 0 and all of K-tile 1 (a tile's A1(1) is always issued ahead of its first K-tile)
   issue(0, 2, smem); issue(0, 0, smem); issue(0, 3, smem); issue(0, 1, smem);
   issue(1, 2, smem + E_KTILE); issue(1, 0, smem + E_KTILE); issue(1, 3, smem + E_KTILE); issue(1, 1, smem + E_KTILE);
-  if (E_DUP) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
   E_BAR();
   if (wr == 1) { E_BAR(); }  // the stagger: waves 4-7 run one barrier behind
 
   int d = 0;  // ring slot of the current K-tile
   bool first = true;
-  // VAR 8 (diagnostic build): s_memtime stamps of waves 0 and 4 per tile -> p.gate as u64 [G][2][64 tiles][4]
-  unsigned long long* stamp = nullptr;
-  int tix = 0;
-  if (VAR & 8) stamp = (unsigned long long*)p.gate + ((size_t)blockIdx.x * 2 + wr) * 64 * 4;
-#define E_STAMP(k_) if ((VAR & 8) && wc == 0 && lane == 0 && tix < 64) stamp[tix * 4 + (k_)] = (k_) == 3 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();
-
-  // VAR 64 (diagnostic build): s_memtime at 17 points of ONE K-tile (tile PT_TILE, K-tile PT_K) of waves 0 and 4, through LDS
-  // (a global store would enter the counted vmcnt stream) -> p.gate as u64 [G][2][32] at the end of the kernel
-  bool pst_on = false;
-#define E_PST(n_) if ((VAR & 64) && pst_on && wc == 0 && lane == 0) ((volatile unsigned long long*)(smem + E_RING + 8192))[wr * 32 + (n_)] = __builtin_amdgcn_s_memtime();
-  // VAR 128 (diagnostic build): s_memtime at the start of every K-tile of the workgroup's THIRD tile, at its epilogue's start and end
-  // and at the next tile's first two K-tiles (waves 0 and 4) -> p.gate as u64 [G][2][32]
-#define E_KST(n_) if ((VAR & 128) && wc == 0 && lane == 0 && (n_) < 32) ((volatile unsigned long long*)(smem + E_RING + 8192))[wr * 32 + (n_)] = __builtin_amdgcn_s_memtime();
 
   // Epilogue addressing.  After the column swap lane (li, lq) holds the 8 columns 8 cq .. 8 cq + 7 of a 32-column block of row li:
   // the four 16-byte pieces of a row sit in lanes 16 apart and ADJACENT lanes belong to different rows.  The memory pipeline merges
   // the addresses of adjacent lanes only: stored (or loaded) like that, a 1 KiB wave-instruction is 64 separate 16-byte requests and
   // takes 64 cycles of the CU's store path instead of 16 (tools/probe_store3.hip: 128 KiB tile 7.5 k cycles against 2.1 k, at any
-  // row pitch, with nothing else running).  So the packed values go through ONE lane transpose first (4 x ds_bpermute_b32 per unit):
-  // lane L then holds piece L & 3 of row L >> 2 and four adjacent lanes cover 64 contiguous bytes; side inputs and the bit mask are
-  // addressed in that layout as well.
+  // row pitch, with nothing else running).  So the packed values go through ONE lane transpose first (see below): lane L then holds
+  // piece L & 3 of row L >> 2 and four adjacent lanes cover 64 contiguous bytes; side inputs and the bit mask are addressed in that
+  // layout as well.
   const int cq = ((lq & 1) << 1) | (lq >> 1);
   const int er = lane >> 2, ep = lane & 3;                                          // row and 16-byte piece of the transposed layout
-  const int tsrc = 4 * (er + 16 * (((ep & 1) << 1) | (ep >> 1)));                  // ds_bpermute address: the lane that holds (row er, piece ep)
   const unsigned cvo = (unsigned)(((128 * wr + er) * p.ldc + 64 * wc + 8 * ep) * 2);   // C
   const unsigned gvo = (unsigned)(((128 * wr + er) * (EPI == EP_RESID ? p.ldr : p.ldg) + 64 * wc + 8 * ep) * 2);  // residual / row-dot matrix
   // bit mask (EP_RELU_BITS out, EP_GATE_BITS in): 8 bytes per row and wave; row pitch ldg, or - PERO_GEMM_MASK_TILED - 32 bytes inside the N-tile's own M x 32 plane
@@ -401,11 +364,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
     return (const unsigned char*)p.gate + (mtiled ? (tn >> 8) * p.M * 32 + tm * 32 : tm * p.ldg + (tn >> 3));
   };
   const unsigned mvo = (unsigned)((128 * wr + er) * mld + 8 * wc);
-  auto lane_t = [&](const unsigned x) -> unsigned { return (unsigned)__builtin_amdgcn_ds_bpermute(tsrc, (int)x); };
-  (void)cq; (void)tsrc;
-  // The same transpose through LDS memory (E_XCHG_LDS): a unit is written as the lanes hold it (one ds_write_b128: row li, piece cq)
-  // and read back in the transposed layout (one ds_read_b128: row er, piece ep) - 13 + 4 cycles of the LDS pipeline per unit against
-  // 4 x 6 for the bpermutes (tools/probe_bperm.hip); the f32 sums of EP_RESID 2 x (13 + 4) against 8 x 6, and without their lane
+  // The transpose goes through LDS memory: a unit is written as the lanes hold it (one ds_write_b128: row li, piece cq) and read back
+  // in the transposed layout (one ds_read_b128: row er, piece ep) - 13 + 4 cycles of the LDS pipeline per unit against 4 x 6 for
+  // four ds_bpermute_b32 (tools/probe_bperm.hip); the f32 sums of EP_RESID 2 x (13 + 4) against 8 x 6, and without their lane
   // swaps.  A wave's LDS instructions execute in order, so the read needs no wait of its own and a slot is reused without one.
   // Pieces are XOR-swizzled so that both directions are conflict-free (bf16: [16 rows][64 B], 2 slots; f32: [16][128 B]).
   unsigned char* const xstg = smem + E_XSTG + wave * 2048;
@@ -425,8 +386,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
   eu2v sm0[4], sm1[4];       // EP_GATE_BITS: the 8 mask bytes of a row (this wave's 64 columns), per row group
 
   for (;;) {
-    E_STAMP(0);
-    E_STAMP(3);
 #pragma unroll
     for (int ha = 0; ha < 2; ha++)
 #pragma unroll
@@ -450,11 +409,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
       constexpr bool last = decltype(last_c)::value;
       unsigned char* const kt = smem + d * E_KTILE;         // K-tile t
       unsigned char* const kn = smem + (d ^ 1) * E_KTILE;   // K-tiles t + 1 (being completed) and, slot by slot, t + 2
-      if (VAR & 64) pst_on = (tix == ((VAR & 8) ? 2 : 0)) && t == (nk > 4 ? 4 : 1);
-      if ((VAR & 128) && (tix == 2 || EPI == EP_SPLITK)) { E_KST(t); }
-      if ((VAR & 128) && tix == 3 && t < 3) { E_KST(nk + 2 + t); }
       // P1
-      E_PST(0);
       E_RD_B(fb0, 0);
       __builtin_amdgcn_sched_barrier(0);
       E_RD_A(0);
@@ -462,47 +417,32 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
           const int so0 = 16 * i * spitch, so1 = (64 + 16 * i) * spitch;
-          if (E_ABL & 2) { sm0[i] = (eu2v){0xffffffffu, 0xffffffffu}; sm1[i] = sm0[i]; asm volatile("" : "+v"(sm0[i]), "+v"(sm1[i])); }
-          else {
           E_BLOAD8(sm0[i], mvo, srs, so0, 0);
           E_BLOAD8(sm1[i], mvo, srs, so1, 0);
-          }
         }
       }
       if (last || t > 0) issue(t + 1, 1, kn);                       // A1(t+1)  (a tile's A1(1) went out ahead of the previous epilogue)
       if (TA) asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");  // the B0 reads (issued first) are done: B0 may be restaged in P2
       else asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-      E_PST(1);
       E_BAR();
       E_LGKM0_B(fb0);
       E_LGKM0_A();
-      E_PST(2);
       E_MFMA(0, 0, fb0);
-      E_PST(3);
       E_BAR();
-      E_PST(4);
       // P2
       E_RD_B(fb1, 1);
       issue(t + 2, 2, kt);                                  // B0(t+2)
-      E_PST(5);
       E_BAR();
       E_LGKM0_B(fb1);
-      E_PST(6);
       E_MFMA(0, 1, fb1);
-      E_PST(7);
       E_BAR();
-      E_PST(8);
       // P3
       E_RD_A(1);
       issue(t + 2, 0, kt);                                  // A0(t+2)
-      E_PST(9);
       E_BAR();
       E_LGKM0_A();
-      E_PST(10);
       E_MFMA(1, 1, fb1);
-      E_PST(11);
       E_BAR();
-      E_PST(12);
       // P4
       if (CN::L0 && last) {  // side inputs of the wave's rows 0-63
 #pragma unroll
@@ -516,23 +456,16 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
       // K-tile t+1 has landed (this wave's pieces).  What was issued after its last half tile A1(t+1) stays in flight:
       // normally the three half tiles of t+2; in a tile's first K-tile also the previous epilogue (side loads of rows 64-127,
       // stores) and the bias row; in its last K-tile the side loads issued just above.
-      if (!last && t == 0 && first) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(7 + E_DX) : "memory");  // + the bias row
+      if (!last && t == 0 && first) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(7) : "memory");  // + the bias row
       // (the column-sum atomic of EP_GATE_BITS leaves only when the workgroup's N-tile changes: on that one tile the count below asks for
       //  one operation more than needed to have retired - never for one less)
-      else if (!last && t == 0 && !first) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(6 + E_DX + 1 + CN::L1 + 2 * CN::S_HALF) : "memory");
-      else if (CN::L0 && last) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(6 + E_DX + CN::L0) : "memory");
+      else if (!last && t == 0 && !first) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(6 + 1 + CN::L1 + 2 * CN::S_HALF) : "memory");
+      else if (CN::L0 && last) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(6 + CN::L0) : "memory");
       else if (EPI == EP_SPLITK && t + 2 >= nk) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stream has ended
-      else asm volatile("s_waitcnt vmcnt(%0)" :: "i"(6 + E_DX) : "memory");
-      E_PST(13);
-      if ((VAR & 128) && last && tix == 2) { E_KST(nk + 5); }
+      else asm volatile("s_waitcnt vmcnt(%0)" :: "i"(6) : "memory");
       E_BAR();
-      if ((VAR & 128) && last && tix == 2) { E_KST(nk + 6); }
-      E_PST(14);
       E_MFMA(1, 0, fb0);
-      E_PST(15);
-      if ((VAR & 128) && last && tix == 2) { E_KST(nk + 7); }
       E_BAR();
-      E_PST(16);
       d ^= 1;
     };
     // (the first K-tile is its own copy of the code: its MFMAs take the zero accumulators as an inline constant, so the 128 registers
@@ -542,25 +475,18 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
     ktile(std::true_type{}, nk - 1);
 
     // ---- epilogue, straight from the accumulators
-    E_STAMP(1);
-    if ((VAR & 128) && tix == 2) { E_KST(nk); }
     first = false;
     issue(nk + 1, 1, smem + (d ^ 1) * E_KTILE);  // A1 of the next tile's K-tile 1: ahead of the stores in the in-order counter
-    // Undo the stagger for the epilogue (VAR 16: keep it).  Staggered, waves 4-7 sit at the barrier behind their last MFMA
+    // Undo the stagger for the epilogue.  Staggered, waves 4-7 sit at the barrier behind their last MFMA
     // cluster until waves 0-3 reach the next tile's first barrier, i.e. through the whole epilogue of waves 0-3, and waves 0-3 then
     // sit through the epilogue of waves 4-7: the two epilogues ran one after the other (stamps at K = 512: 4.5 k + 5.3 k cycles of a
     // 40 k-cycle tile).  With one extra barrier here waves 0-3 wait the 256 cycles of that last cluster and both epilogues run
     // side by side; waves 4-7 take the extra barrier in front of the next tile, which staggers the groups again.
-    if (EPI != EP_SPLITK && !(VAR & 16) && wr == 0) { E_BAR(); }
-    if ((VAR & 128) && tix == 2) { E_KST(nk + 8); }
+    if (EPI != EP_SPLITK && wr == 0) { E_BAR(); }
     if (EPI == EP_SPLITK) {
       // f32 tile added into C with atomics whose wave-instructions cover 256 contiguous bytes (full atomic rate): two rounds
       // through the (now free) 128 KiB ring, [128 rows][256 f32], 16-byte chunk index XORed with (row & 15)
       if (wr == 0) { E_BAR(); }  // undo the stagger: every wave has finished its last reads and MFMAs
-      if ((VAR & 64) && wc == 0 && lane < 17)
-        ((unsigned long long*)p.gate)[((size_t)blockIdx.x * 2 + wr) * 32 + lane] = ((unsigned long long*)(smem + E_RING + 8192))[wr * 32 + lane];
-      if ((VAR & 128) && wc == 0 && lane < 32)
-        ((unsigned long long*)p.gate)[((size_t)blockIdx.x * 2 + wr) * 32 + lane] = ((unsigned long long*)(smem + E_RING + 8192))[wr * 32 + lane];
       if (p.resid) {
         // partial tile -> workspace with plain 16-byte stores, accumulator by accumulator: every wave-instruction writes 1 KiB of
         // contiguous bytes ([accumulator][wave][lane] float4; pero_splitk_reduce_k knows the layout).  The slices of a tile are summed
@@ -605,9 +531,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
       return;
     }
     {
-      // (VAR 1, timing probe: every tile of a workgroup lands on the workgroup's FIRST tile - the stores are issued and acknowledged, the lines stay in L2)
-      const ei4v crs = (VAR & 1) ? ersrc((bf16raw*)p.C + (long long)((blockIdx.x >> 3) * 256) * p.ldc + (blockIdx.x & 7) * 256, (unsigned)(256 * p.ldc * 2))
-                                 : ersrc((bf16raw*)p.C + tm0 * p.ldc + tn0, (unsigned)(256 * p.ldc * 2));
+      const ei4v crs = ersrc((bf16raw*)p.C + tm0 * p.ldc + tn0, (unsigned)(256 * p.ldc * 2));
       const int cpitch = (int)(p.ldc * 2);
       // bias of the lane's columns as the accumulators hold them: 64 wc + 32 hb + 16 j + 4 (lane >> 4) .. + 3
       f4v bx[2][2];
@@ -618,7 +542,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
           bx[hb][j] = (f4v){0.f, 0.f, 0.f, 0.f};
           if (use_bias) bx[hb][j] = *(const f4v*)(biasl + (64 * wc + 32 * hb + 16 * j + 4 * lq) * 4);
         }
-      if ((VAR & 128) && tix == 2) { E_KST(nk + 9); }
       float cs[2][8];  // EP_GATE_BITS + column sums
       float rd[4];     // EP_ROWDOT: row dots of one row group
 #pragma unroll
@@ -636,7 +559,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
           }
           E_WAIT8(2 + 2 + CN::L1, side0);
         }
-        if ((VAR & 128) && tix == 2 && ha == 1) { E_KST(nk + 10); }
         if (CN::L1 && ha == 1) E_WAIT8(CN::S_HALF, side1);
         if (EPI == EP_GATE_BITS && ha == 0) {
           // retired by phase 4's wait of the last K-tile long ago (the statements tie the registers to a wait)
@@ -666,25 +588,15 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
               const f4v x = EPI <= EP_RELU_BITS ? acc[ha][hb][i][0] + bx[hb][0] : acc[ha][hb][i][0];
               const f4v y = EPI <= EP_RELU_BITS ? acc[ha][hb][i][1] + bx[hb][1] : acc[ha][hb][i][1];
               if (EPI == EP_RESID) {
-                // f32 columns first (one rounding): even lane groups keep x and take the odd neighbour's x, odd ones y
+                // f32 columns first (one rounding), through the staging image: x = columns 4 lq .. + 3 (piece lq), y = columns 16 + 4 lq ..
+                // (piece 4 + lq) of the row's 32 f32; read: columns 8 ep .. + 7
                 float v[8];
-                if (E_XCHG_LDS) {
-                  // x = columns 4 lq .. + 3 (piece lq), y = columns 16 + 4 lq .. (piece 4 + lq) of the row's 32 f32; read: columns 8 ep .. + 7
-                  *(f4v*)(xstg + xw32 + ((lq ^ xsw) << 4)) = x;
-                  *(f4v*)(xstg + xw32 + (((4 + lq) ^ xsw) << 4)) = y;
-                  const f4v r0 = *(const f4v*)(xstg + xr32 + (((2 * ep) ^ xsr) << 4));
-                  const f4v r1 = *(const f4v*)(xstg + xr32 + (((2 * ep + 1) ^ xsr) << 4));
+                *(f4v*)(xstg + xw32 + ((lq ^ xsw) << 4)) = x;
+                *(f4v*)(xstg + xw32 + (((4 + lq) ^ xsw) << 4)) = y;
+                const f4v r0 = *(const f4v*)(xstg + xr32 + (((2 * ep) ^ xsr) << 4));
+                const f4v r1 = *(const f4v*)(xstg + xr32 + (((2 * ep + 1) ^ xsr) << 4));
 #pragma unroll
-                  for (int e = 0; e < 4; e++) { v[e] = r0[e]; v[4 + e] = r1[e]; }
-                } else {
-#pragma unroll
-                  for (int e = 0; e < 4; e++) {
-                    auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(x[e]), __float_as_uint(y[e]), false, false);
-                    v[e] = __uint_as_float(sw[0]); v[4 + e] = __uint_as_float(sw[1]);
-                  }
-#pragma unroll
-                  for (int e = 0; e < 8; e++) v[e] = __uint_as_float(lane_t(__float_as_uint(v[e])));   // the f32 sums move, rounded once below
-                }
+                for (int e = 0; e < 4; e++) { v[e] = r0[e]; v[4 + e] = r1[e]; }
                 const eu4v r4 = ha ? side1[2 * i + hb] : side0[2 * i + hb];
 #pragma unroll
                 for (int e = 0; e < 4; e++) { v[2 * e] += __uint_as_float(r4[e] << 16); v[2 * e + 1] += __uint_as_float(r4[e] & 0xffff0000u); }
@@ -699,12 +611,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
                 }
                 auto s0 = __builtin_amdgcn_permlane16_swap(px0, py0, false, false);
                 auto s1 = __builtin_amdgcn_permlane16_swap(px1, py1, false, false);
-                if (E_XCHG_LDS) {
-                  *(eu4v*)(xstg + hb * 1024 + xw16) = (eu4v){s0[0], s1[0], s0[1], s1[1]};
-                  o[ii][hb] = *(const eu4v*)(xstg + hb * 1024 + xr16);
-                } else {
-                  o[ii][hb][0] = lane_t(s0[0]); o[ii][hb][1] = lane_t(s1[0]); o[ii][hb][2] = lane_t(s0[1]); o[ii][hb][3] = lane_t(s1[1]);
-                }
+                *(eu4v*)(xstg + hb * 1024 + xw16) = (eu4v){s0[0], s1[0], s0[1], s1[1]};
+                o[ii][hb] = *(const eu4v*)(xstg + hb * 1024 + xr16);
               }
             }
 #pragma unroll
@@ -742,14 +650,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
 #pragma unroll
                 for (int k = 0; k < 4; k++) rd[i] = edot2(ou[k], g4[k], rd[i]);   // one v_dot2c_f32_bf16 instead of 4 unpacks, 2 multiplies, 2 adds
               }
-              if (VAR & 4) {  // ablation: no stores (the values stay live)
-                asm volatile("" :: "v"(ou[0]), "v"(ou[1]), "v"(ou[2]), "v"(ou[3]));
-                if (i + hb == 0) { if (hb) E_BSTORE16(ou, cvo, crs, so, 64); else E_BSTORE16(ou, cvo, crs, so, 0); }
-              } else if (VAR & 32) {
-                if (hb) E_BSTORE16_NT(ou, cvo, crs, so, 64); else E_BSTORE16_NT(ou, cvo, crs, so, 0);
-              } else {
-                if (hb) E_BSTORE16(ou, cvo, crs, so, 64); else E_BSTORE16(ou, cvo, crs, so, 0);
-              }
+              if (hb) E_BSTORE16(ou, cvo, crs, so, 64); else E_BSTORE16(ou, cvo, crs, so, 0);
             }
             if (EPI == EP_RELU_BITS) {
               // OR over the four lanes of a row (one quad): every one of them then holds the row's 8 bytes
@@ -761,8 +662,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
               const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc((unsigned char*)mask_base(tm0, tn0), 0, (int)(256 * mld), 0x00020000);
               // all four store them (same address, same data): one instruction, no branch (storing from the quad's first lane only
               // measured no faster)
-              if (E_ABL & 1) asm volatile("" :: "v"(mo[0]), "v"(mo[1]));
-              else __builtin_amdgcn_raw_buffer_store_b64(mo, mrs, mvo, (64 * ha + 16 * i) * (int)mld, 0);
+              __builtin_amdgcn_raw_buffer_store_b64(mo, mrs, mvo, (64 * ha + 16 * i) * (int)mld, 0);
             }
             if (EPI == EP_ROWDOT) {
               // sum over the four lanes of a row (one quad), then its first lane adds into [m][n / 128] (two waves per 128-column block)
@@ -819,31 +719,22 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_e256(GemmP p, int ks) {
         cs_run += tot;
       }
     }
-    E_STAMP(2);
-    if ((VAR & 128) && tix == 2) { E_KST(nk + 1); }
-    tix++;
     if (!has_next) break;
     T += G;
     tm0 = nm0; tn0 = nn0; cA = nA; cB = nB;
     has_next = T + G < nt;
     tile_of(has_next ? T + G : T, nm0, nn0);
-    nA = (const unsigned char*)A + (nm0 & amask) * sa.tile;
+    nA = (const unsigned char*)A + nm0 * sa.tile;
     nB = (const unsigned char*)B + nn0 * sb.tile;
-    if (!(VAR & 16) && wr == 1) { E_BAR(); }  // the stagger again
+    if (wr == 1) { E_BAR(); }  // the stagger again
   }
-  if ((VAR & 64) && wc == 0 && lane < 17)
-    ((unsigned long long*)p.gate)[(VAR & 8 ? (size_t)gridDim.x * 2 * 64 * 4 : 0) + ((size_t)blockIdx.x * 2 + wr) * 32 + lane] = ((unsigned long long*)(smem + E_RING + 8192))[wr * 32 + lane];
-  if ((VAR & 128) && wc == 0 && lane < 32)
-    ((unsigned long long*)p.gate)[((size_t)blockIdx.x * 2 + wr) * 32 + lane] = ((unsigned long long*)(smem + E_RING + 8192))[wr * 32 + lane];
   if (EPI == EP_GATE_BITS && colsum && cs_tn0 >= 0) atomicAdd((float*)p.bias + cs_tn0 + 64 * wc + 32 * (lane >> 5) + 8 * (lane & 3) + ((lane >> 2) & 7), cs_run);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last tile's surplus prefetches land before the LDS is released
-  if ((VAR & 16) && wr == 0) { E_BAR(); }  // balance the stagger barrier (otherwise the last epilogue's extra barrier has done it)
 #undef E_RD_A
 #undef E_RD_B
 #undef E_MFMA
 #undef E_BAR
 #undef E_LGKM0
-#undef E_STAMP
 }
 
 // =====================================================================================================================================
@@ -878,7 +769,7 @@ template <int EPI> struct DCnt {
   static constexpr int ST = 16 + (EPI == EP_RELU_BITS ? 8 : 0) + (EPI == EP_ROWDOT ? 8 : 0);   // stores / atomics of a tile
 };
 
-template <int EPI, int VAR>
+template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_d128(GemmP p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef DCnt<EPI> CN;
@@ -1151,12 +1042,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_d128(GemmP p) {
                   cs[hb][2 * k + 1] = edot2(ou[k], sel_hi, cs[hb][2 * k + 1]);
                 }
               }
-              if (VAR & 4) {  // ablation: no stores (the values stay live)
-                asm volatile("" :: "v"(ou[0]), "v"(ou[1]), "v"(ou[2]), "v"(ou[3]));
-                if (i + hb == 0) { if (hb) E_BSTORE16(ou, cvo, crs, so, 64); else E_BSTORE16(ou, cvo, crs, so, 0); }
-              } else {
-                if (hb) E_BSTORE16(ou, cvo, crs, so, 64); else E_BSTORE16(ou, cvo, crs, so, 0);
-              }
+              if (hb) E_BSTORE16(ou, cvo, crs, so, 64); else E_BSTORE16(ou, cvo, crs, so, 0);
             }
             if (EPI == EP_RELU_BITS) {
               mL |= (unsigned)__builtin_amdgcn_mov_dpp((int)mL, 0xB1, 0xf, 0xf, false);  // quad_perm [1,0,3,2]
@@ -1244,8 +1130,8 @@ bool pero_launch_gemm_d128(const GemmP& p0, long long batch, bool ta, bool tb, b
   dim3 grid(G), block(256);
 #define LAUNCH_D(EP_)                                                                              \
   do {                                                                                             \
-    PERO_LDS_ATTR((gemm_bf16_d128<EP_, 0>), D_LDS_BYTES);                                          \
-    hipLaunchKernelGGL((gemm_bf16_d128<EP_, 0>), grid, block, D_LDS_BYTES, st, p);                 \
+    PERO_LDS_ATTR((gemm_bf16_d128<EP_>), D_LDS_BYTES);                                             \
+    hipLaunchKernelGGL((gemm_bf16_d128<EP_>), grid, block, D_LDS_BYTES, st, p);                    \
   } while (0)
   switch (epi) {
     case EP_RELU: LAUNCH_D(EP_RELU); break;
@@ -1275,12 +1161,6 @@ bool pero_launch_gemm_d128(const GemmP& p0, long long batch, bool ta, bool tb, b
 //    instructions) and W1 in phase 4 (A, B00, B10 of t + 1: newer are A(t+2), B01 / B11(t+1), B00 / B10(t+2) = 10); in a tile's first K-tile the
 //    previous epilogue's side loads and stores, in its last the side loads of its own epilogue are counted out (constants at the waits).
 // Epilogue: gemm_bf16_e256's plain / residual epilogue with `128 wr` gone from the row offsets and `256 wr` added to the columns.
-#ifndef N_DBG
-#define N_DBG 0   // bring-up switches of the LayerNorm epilogue: 1 no gamma / beta loads (gamma = 1, beta = 0), 2 no mean / rstd stores, 4 pass 2 recomputes nothing (stores y again)
-#endif
-#ifndef LNB_ABL
-#define LNB_ABL 0   // timing-only ablation builds of the LayerNorm-backward epilogue (results wrong by design; tools/lnb_ab.py): 1 no column-sum
-#endif             // butterflies, 2 no pass 1b arithmetic, 4 no pass 2 arithmetic (the packed dt rows are stored), 8 pass 2 without its second load of the t rows
 #define N_BM 128
 #define N_ASLOTS 3
 #define N_BSLOTS 6
@@ -1578,7 +1458,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_n512(GemmP p, LnP q) {
       };
       // t rows 0-63 first (they are needed after BOTH halves of pass 1a: issued behind rows 0-63 they had one half to arrive and the wave waited
       // for HBM; with every arithmetic instruction of this epilogue compiled out it still cost 128 us per launch over the plain residual
-      // epilogue - tools/lnb_ab.py, LNB_ABL = 7: its loads' latency, not its 1 900 vector-ALU instructions, is what the epilogue costs)
+      // epilogue (an ablation build): its loads' latency, not its 1 900 vector-ALU instructions, is what the epilogue costs)
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         const int so = 16 * i * tpitch_l;
@@ -1614,7 +1494,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_n512(GemmP p, LnP q) {
             const eu4v tw = ha ? tside1[2 * i + hb] : tside0[2 * i + hb];
 #pragma unroll
             for (int e = 0; e < 4; e++) {
-              if (LNB_ABL & 2) { if (e == 0) { a1[0] += __uint_as_float(dtp[ha][i][hb][0]); a2[0] += __uint_as_float(tw[0]); } continue; }
               const ef2v d = lo2(dtp[ha][i][hb][e]);
               const ef2v u = lo2(tw[e]) - Bp(hb, e);
               a1 = __builtin_elementwise_fma(d, Gp(hb, e), a1);
@@ -1699,7 +1578,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_n512(GemmP p, LnP q) {
           eu4v od;
 #pragma unroll
           for (int e = 0; e < 4; e++) {
-            if (LNB_ABL & 4) { od[e] = dtp[ha][i][hb][e] ^ tw[e]; AX[e][0] += rs + c1 + c2; continue; }
             const ef2v d = lo2(dtp[ha][i][hb][e]);
             const ef2v xh = (lo2(tw[e]) - Bt[e]) * IG[e];
             ef2v o = __builtin_elementwise_fma(d, G[e], c1v);
@@ -1712,12 +1590,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_n512(GemmP p, LnP q) {
           if (hb) E_BSTORE16(od, cvo_, crs_, so, 64); else E_BSTORE16(od, cvo_, crs_, so, 0);
         }
         if constexpr (ha == 1) {
-          if (LNB_ABL & 1) { tot_g[hb] = AG[0][0] + AG[3][1]; tot_b[hb] = AB[0][0] + AB[3][1]; tot_x[hb] = AX[0][0] + AX[3][1]; }
-          else {
           tot_g[hb] = colred8(AG);
           tot_b[hb] = colred8(AB);
           tot_x[hb] = colred8(AX);
-          }
         }
       };
       E_WAIT4(8, rsc[0]);                                  // chunk 0's rstd: newer are chunks 1 and 2 (4 + 4)
@@ -1792,7 +1667,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_n512(GemmP p, LnP q) {
               E_BLOAD16(side1[2 * i + 1], gvo, srs, so, 64);
             }
           }
-          if (LN && !(N_DBG & 1) && ha == 1 && ib == 2) {   // (three quarters of the accumulators and side registers are free by now; only the four stores of rows 96-127 follow)
+          if (LN && ha == 1 && ib == 2) {   // (three quarters of the accumulators and side registers are free by now; only the four stores of rows 96-127 follow)
             // gamma / beta of the lane's columns 256 wr + 64 wc + 32 hb + 8 ep .. + 7 (two 16-byte halves each): needed in pass 2
             const ei4v grs = ersrc(q.gamma + 256 * wr + 64 * wc, 64 * 4), ers = ersrc(q.beta + 256 * wr + 64 * wc, 64 * 4);
             const unsigned gvoff = (unsigned)(8 * ep * 4);
@@ -1879,7 +1754,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_n512(GemmP p, LnP q) {
               part[ha][i] = quad(all[(2 * ep) * 512 + r + 8 * ep] + all[(2 * ep + 1) * 512 + r + 8 * ep + 4]);
             }
         };
-        if (!(N_DBG & 8)) exchange(rsum, 0);
+        exchange(rsum, 0);
         float mu[2][4], qs[2][4];
         float xc[2][4][2][8];   // the centred values: unpacked and centred ONCE, used by the variance and by the normalisation (the accumulators are dead: 128 registers)
 #pragma unroll
@@ -1898,9 +1773,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_n512(GemmP p, LnP q) {
               }
             qs[ha][i] = a;
           }
-        if (!(N_DBG & 8)) exchange(qs, 1);
+        exchange(qs, 1);
         // mean / rstd of the tile's rows: wave w writes the 16 rows of its (ha, i) = (w >> 2, w & 3)
-        if (!(N_DBG & 1)) E_WAIT8(SH / 2, gb);   // gamma / beta: newer are the four stores of rows 96-127
+        E_WAIT8(SH / 2, gb);   // gamma / beta: newer are the four stores of rows 96-127
         const ei4v trs = ersrc((bf16raw*)q.t + tm0 * q.ldt, (unsigned)(128 * q.ldt * 2));
         const int tpitch = (int)(q.ldt * 2);
         const unsigned tvo = (unsigned)((er * q.ldt + 256 * wr + 64 * wc + 8 * ep) * 2);
@@ -1909,7 +1784,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_n512(GemmP p, LnP q) {
 #pragma unroll
           for (int i = 0; i < 4; i++) {
             const float rs = 1.0f / sqrtf(qs[ha][i] / 512.f + q.eps);
-            if (!(N_DBG & 2) && wave == ha * 4 + i && ep == 0) {
+            if (wave == ha * 4 + i && ep == 0) {
               q.mean[tm0 + 64 * ha + 16 * i + er] = mu[ha][i];
               q.rstd[tm0 + 64 * ha + 16 * i + er] = rs;
             }
@@ -1918,9 +1793,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_n512(GemmP p, LnP q) {
               eu4v ot;
 #pragma unroll
               for (int e = 0; e < 4; e++) {
-                const float g0 = (N_DBG & 1) ? 1.f : __uint_as_float(gb[2 * hb + (e >> 1)][2 * (e & 1)]), g1 = (N_DBG & 1) ? 1.f : __uint_as_float(gb[2 * hb + (e >> 1)][2 * (e & 1) + 1]);
-                const float b0 = (N_DBG & 1) ? 0.f : __uint_as_float(gb[4 + 2 * hb + (e >> 1)][2 * (e & 1)]), b1 = (N_DBG & 1) ? 0.f : __uint_as_float(gb[4 + 2 * hb + (e >> 1)][2 * (e & 1) + 1]);
-                ot[e] = (N_DBG & 4) ? yk[ha][i][hb][e] : pack2bf(xc[ha][i][hb][2 * e] * rs * g0 + b0, xc[ha][i][hb][2 * e + 1] * rs * g1 + b1);
+                const float g0 = __uint_as_float(gb[2 * hb + (e >> 1)][2 * (e & 1)]), g1 = __uint_as_float(gb[2 * hb + (e >> 1)][2 * (e & 1) + 1]);
+                const float b0 = __uint_as_float(gb[4 + 2 * hb + (e >> 1)][2 * (e & 1)]), b1 = __uint_as_float(gb[4 + 2 * hb + (e >> 1)][2 * (e & 1) + 1]);
+                ot[e] = pack2bf(xc[ha][i][hb][2 * e] * rs * g0 + b0, xc[ha][i][hb][2 * e + 1] * rs * g1 + b1);
               }
               const int so = (64 * ha + 16 * i) * tpitch;
               if (hb) E_BSTORE16(ot, tvo, trs, so, 64); else E_BSTORE16(ot, tvo, trs, so, 0);
@@ -2076,19 +1951,14 @@ long long pero_gemm_e256_splitk_ws_bytes(long long M, long long N, long long K, 
 
 // Qualifies: one problem (batch 1), bf16 operands; stored bf16 output (alpha == 1) or a split-K f32 product; M % 256 == N % 256 == K % 64 == 0, K >= 128.
 // ws / ws_bytes: the caller's workspace for the split-K partial tiles (pero_gemm's `workspace`); never allocated here.
-int g_gemm_e_var = 0;
 int g_gemm_e_walk = 1;   // pero_set_option("gemm_e_walk", 0): every stored product in the side-by-side order
-bool pero_launch_gemm_e256(const GemmP& p0, long long batch, int k_split, bool ta, bool tb, bool out_f32, hipStream_t st, int var, void* ws,
+bool pero_launch_gemm_e256(const GemmP& p0, long long batch, int k_split, bool ta, bool tb, bool out_f32, hipStream_t st, void* ws,
                            long long ws_bytes) {
   if (p0.M % E_BM || p0.N % E_BN || p0.K % E_BK || p0.K < 2 * E_BK || batch != 1) return false;
-  if (var < 0) var = g_gemm_e_var;
-  const int wg_cap = ((var >> 8) & 0xff) * 8;  // diagnostic: at most this many workgroups (bits 8-15 of the variant, in units of 8)
-  const int walk = (var >> 16) & 0x3f;         // stored products (bit 5: the A-rows-from-L2 timing probe): N-tiles of a row panel per workgroup, one after the other (bits 16-19; see the kernel's tile_of)
-  var &= 0xff;
   int ks = 0;
   if (p0.flags & PERO_GEMM_ATOMIC) {
     // split-K: f32 C, plain product, equal slices of whole K-tiles, one slice set per XCD
-    if (!out_f32 || p0.bias || p0.resid || (p0.gate && !(var & (64 | 128))) || (p0.flags & ~(PERO_GEMM_ATOMIC | PERO_GEMM_TRANS_A | PERO_GEMM_TRANS_B | PERO_GEMM_TILE_V | PERO_GEMM_TILE256))) return false;
+    if (!out_f32 || p0.bias || p0.resid || p0.gate || (p0.flags & ~(PERO_GEMM_ATOMIC | PERO_GEMM_TRANS_A | PERO_GEMM_TRANS_B | PERO_GEMM_TILE_V | PERO_GEMM_TILE256))) return false;
     const long long tiles = (p0.M / E_BM) * (p0.N / E_BN), steps = p0.K / E_BK;
     bool xcd_ok = false;
     ks = e256_splitk_slices(tiles, steps, k_split, &xcd_ok);
@@ -2098,7 +1968,7 @@ bool pero_launch_gemm_e256(const GemmP& p0, long long batch, int k_split, bool t
     dim3 grid((unsigned)(tiles * ks)), block(512);
     const int nsl = ks;
     const bool ws_ok = ws && (((size_t)ws) & 15) == 0 && ws_bytes >= tiles * ks * (long long)(E_BM * E_BN * sizeof(float));
-    p.resid = (g_gemm_splitk_ws && ws_ok && !(var & (64 | 128)) && nsl > 1) ? ws : nullptr;
+    p.resid = (g_gemm_splitk_ws && ws_ok && nsl > 1) ? ws : nullptr;
     auto reduce = [&]() {
       if (p.resid)
         hipLaunchKernelGGL(pero_splitk_reduce_k, dim3((unsigned)(tiles * 64)), dim3(256), 0, st, (const f4v*)p.resid, (float*)p.C, (long long)p.ldc,
@@ -2106,23 +1976,13 @@ bool pero_launch_gemm_e256(const GemmP& p0, long long batch, int k_split, bool t
     };
     if (!xcd_ok) {
       ks = -ks;
-      p.kchunk = (g_gemm_splitk_table && !(var & (64 | 128))) ? 1 : 0;   // work items handed out XCD by XCD (esplitk_xcd_item)
+      p.kchunk = g_gemm_splitk_table ? 1 : 0;   // work items handed out XCD by XCD (esplitk_xcd_item)
     }
 #define LAUNCH_ES(TA_, TB_)                                                                                                \
   do {                                                                                                                     \
-    PERO_LDS_ATTR((gemm_bf16_e256<TA_, TB_, EP_SPLITK, 0>), E_LDS_BYTES);                                                  \
-    hipLaunchKernelGGL((gemm_bf16_e256<TA_, TB_, EP_SPLITK, 0>), grid, block, E_LDS_BYTES, st, p, ks);                    \
+    PERO_LDS_ATTR((gemm_bf16_e256<TA_, TB_, EP_SPLITK>), E_LDS_BYTES);                                                     \
+    hipLaunchKernelGGL((gemm_bf16_e256<TA_, TB_, EP_SPLITK>), grid, block, E_LDS_BYTES, st, p, ks);                       \
   } while (0)
-    if ((var & 128) && ta && tb) {
-      PERO_LDS_ATTR((gemm_bf16_e256<true, true, EP_SPLITK, 128>), E_LDS_BYTES);
-      hipLaunchKernelGGL((gemm_bf16_e256<true, true, EP_SPLITK, 128>), grid, block, E_LDS_BYTES, st, p, ks);
-      return true;
-    }
-    if ((var & 64) && ta && tb) {
-      PERO_LDS_ATTR((gemm_bf16_e256<true, true, EP_SPLITK, 64>), E_LDS_BYTES);
-      hipLaunchKernelGGL((gemm_bf16_e256<true, true, EP_SPLITK, 64>), grid, block, E_LDS_BYTES, st, p, ks);
-      return true;
-    }
     if (!ta && !tb) LAUNCH_ES(false, false); else if (!ta && tb) LAUNCH_ES(false, true); else if (ta && tb) LAUNCH_ES(true, true); else LAUNCH_ES(true, false);
 #undef LAUNCH_ES
     reduce();
@@ -2134,9 +1994,7 @@ bool pero_launch_gemm_e256(const GemmP& p0, long long batch, int k_split, bool t
   const bool relu = p0.flags & PERO_GEMM_RELU, bits = p0.flags & PERO_GEMM_RELU_BITS, rowdot = p0.flags & PERO_GEMM_ROWDOT,
              cs = p0.flags & PERO_GEMM_COLSUM;
   int epi;
-  if ((var & 128) && p0.resid && !relu && !bits && !rowdot && !cs) epi = EP_RESID;   // stamp build of the residual epilogue
-  else if (var & (8 | 128)) epi = EP_PLAIN;          // stamp builds: `gate` is the stamp buffer
-  else if (rowdot) { if (relu || bits || cs || p0.resid || !p0.gate || !p0.bias) return false; epi = EP_ROWDOT; }
+  if (rowdot) { if (relu || bits || cs || p0.resid || !p0.gate || !p0.bias) return false; epi = EP_ROWDOT; }
   else if (bits) {
     if (!p0.gate || p0.resid || (relu && cs)) return false;
     // the gate epilogue has no input-bias path (its `bias` is the column-sum OUTPUT under PERO_GEMM_COLSUM): a gated product WITH an
@@ -2154,18 +2012,16 @@ bool pero_launch_gemm_e256(const GemmP& p0, long long batch, int k_split, bool t
   GemmP p = p0;
   p.kchunk = p.K;
   const long long nt = (p.M / E_BM) * (p.N / E_BN);
-  unsigned G = (unsigned)(nt < num_cus ? ((nt + 7) / 8) * 8 : num_cus);
-  if (wg_cap && (unsigned)wg_cap < G) G = (unsigned)wg_cap;
+  const unsigned G = (unsigned)(nt < num_cus ? ((nt + 7) / 8) * 8 : num_cus);
   dim3 grid(G), block(512);
   // Walk of the stored K <= 512 products (the kernel's tile_of): by default the ntn workgroups of an XCD that share a 256-row panel of A run its ntn N-tiles side
   // by side and wait for the same bytes from HBM together.  With each workgroup taking `seq` N-tiles of its panel one after the other, seq x as many panels are in
   // flight per XCD and the panel's later passes come from the caches: 524 288 x 2048 x 512 plain / ReLU 1 056 -> 1 010 us, bit-mask gate 1 086 -> 1 054, N = 1536
-  // 784 -> 772, N = 4096 2 117 -> 1 926 (seq 4 / 3; tools/e256_walk2.py).  NOT for the epilogue that writes the ReLU bit mask in ROWS (its 32 bytes per row and tile are a
+  // 784 -> 772, N = 4096 2 117 -> 1 926 (seq 4 / 3; profiles/r04_e256_store_probes.txt).  NOT for the epilogue that writes the ReLU bit mask in ROWS (its 32 bytes per row and tile are a
   // quarter of a line: written rounds apart they cost more than the walk gains, 1 095 -> 1 147; with PERO_GEMM_MASK_TILED a tile's mask is whole lines), not at K = 2048 (+- 1 %).  Same tiles, same bits.
-  ks = walk;
-  if (!(walk & 31) && g_gemm_e_walk && p.K <= 512 && (epi == EP_PLAIN || epi == EP_RELU || epi == EP_GATE_BITS || (epi == EP_RELU_BITS && (p.flags & PERO_GEMM_MASK_TILED))) && nt >= 2LL * G) {
+  if (g_gemm_e_walk && p.K <= 512 && (epi == EP_PLAIN || epi == EP_RELU || epi == EP_GATE_BITS || (epi == EP_RELU_BITS && (p.flags & PERO_GEMM_MASK_TILED))) && nt >= 2LL * G) {
     const long long ntn = p.N / E_BN;
-    ks = (walk & 32) | ((ntn >= 8 && ntn % 4 == 0) ? 4 : (ntn >= 6 && ntn % 3 == 0) ? 3 : 0);
+    ks = (ntn >= 8 && ntn % 4 == 0) ? 4 : (ntn >= 6 && ntn % 3 == 0) ? 3 : 0;
   }
   if (epi == EP_ROWDOT) {  // the two waves of a 128-column block add into it: cleared first (hipMemsetAsync's fill kernel took 27 us for these 4 MB)
     const long long n = p.M * (p.N >> 7);
@@ -2174,38 +2030,24 @@ bool pero_launch_gemm_e256(const GemmP& p0, long long batch, int k_split, bool t
     else
       hipMemsetAsync((void*)p.bias, 0, (size_t)n * sizeof(float), st);
   }
-#define LAUNCH_E(TA_, TB_, EP_, VAR_)                                                                                            \
-  do {                                                                                                                     \
-    PERO_LDS_ATTR((gemm_bf16_e256<TA_, TB_, EP_, VAR_>), E_LDS_BYTES);                                                     \
-    hipLaunchKernelGGL((gemm_bf16_e256<TA_, TB_, EP_, VAR_>), grid, block, E_LDS_BYTES, st, p, ks);                                  \
+#define LAUNCH_E(TA_, TB_, EP_)                                                               \
+  do {                                                                                        \
+    PERO_LDS_ATTR((gemm_bf16_e256<TA_, TB_, EP_>), E_LDS_BYTES);                              \
+    hipLaunchKernelGGL((gemm_bf16_e256<TA_, TB_, EP_>), grid, block, E_LDS_BYTES, st, p, ks); \
   } while (0)
   if (!ta && !tb) {
     switch (epi) {
-      case EP_RELU: LAUNCH_E(false, false, EP_RELU, 0); break;
-      case EP_RESID: if (var == 128) LAUNCH_E(false, false, EP_RESID, 128); else if (var == 2) LAUNCH_E(false, false, EP_RESID, 2); else if (var == 16) LAUNCH_E(false, false, EP_RESID, 16); else LAUNCH_E(false, false, EP_RESID, 0); break;
-      case EP_RELU_BITS: LAUNCH_E(false, false, EP_RELU_BITS, 0); break;
-      case EP_GATE_BITS: LAUNCH_E(false, false, EP_GATE_BITS, 0); break;
-      case EP_ROWDOT: LAUNCH_E(false, false, EP_ROWDOT, 0); break;
-      default:
-        switch (var) {
-          case 1: LAUNCH_E(false, false, EP_PLAIN, 1); break;
-          case 2: LAUNCH_E(false, false, EP_PLAIN, 2); break;
-          case 4: LAUNCH_E(false, false, EP_PLAIN, 4); break;
-          case 8: LAUNCH_E(false, false, EP_PLAIN, 8); break;
-          case 10: LAUNCH_E(false, false, EP_PLAIN, 10); break;
-          case 12: LAUNCH_E(false, false, EP_PLAIN, 12); break;
-          case 16: LAUNCH_E(false, false, EP_PLAIN, 16); break;
-          case 32: LAUNCH_E(false, false, EP_PLAIN, 32); break;
-          case 72: LAUNCH_E(false, false, EP_PLAIN, 72); break;
-          case 128: LAUNCH_E(false, false, EP_PLAIN, 128); break;
-          case 132: LAUNCH_E(false, false, EP_PLAIN, 132); break;
-          default: LAUNCH_E(false, false, EP_PLAIN, 0); break;
-        }
+      case EP_RELU: LAUNCH_E(false, false, EP_RELU); break;
+      case EP_RESID: LAUNCH_E(false, false, EP_RESID); break;
+      case EP_RELU_BITS: LAUNCH_E(false, false, EP_RELU_BITS); break;
+      case EP_GATE_BITS: LAUNCH_E(false, false, EP_GATE_BITS); break;
+      case EP_ROWDOT: LAUNCH_E(false, false, EP_ROWDOT); break;
+      default: LAUNCH_E(false, false, EP_PLAIN); break;
     }
   }
-  else if (!ta && tb) LAUNCH_E(false, true, EP_PLAIN, 0);
-  else if (ta && tb) LAUNCH_E(true, true, EP_PLAIN, 0);
-  else LAUNCH_E(true, false, EP_PLAIN, 0);
+  else if (!ta && tb) LAUNCH_E(false, true, EP_PLAIN);
+  else if (ta && tb) LAUNCH_E(true, true, EP_PLAIN);
+  else LAUNCH_E(true, false, EP_PLAIN);
 #undef LAUNCH_E
   return true;
 }

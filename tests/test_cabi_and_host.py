@@ -124,6 +124,20 @@ def test_argument_validation_without_gpu():
         _lib.call("pero_colsum", None, None, 0, 0, 0, 0, None)
 
 
+def test_set_option_takes_the_tested_knobs_and_no_diagnostic_variant():
+    """Every option name the GPU tests set is accepted (each set to its default here, so the process state does not change); the option
+    that selected the eight-phase kernel's diagnostic builds, some of which gave wrong results by design, is gone and is rejected like any
+    unknown name."""
+    from pero_pretraining_amd import _lib
+    h = _lib.lib()
+    defaults = {"gemm_policy": 0, "splitk_workspace": 1, "gemm_e_walk": 1, "gemm_d128": 0, "gemm_nw": 0, "attn_bwd_pair": 1, "attn_pipe": 1,
+                "attn_lh": 0}
+    for name, value in defaults.items():
+        assert h.pero_set_option(name.encode(), value) == 0, name
+    assert h.pero_set_option(b"gemm_e_var", 1) == -1
+    assert b"unknown option gemm_e_var" in h.pero_last_error()
+
+
 def test_no_cpu_fallback():
     from pero_pretraining_amd._lib import PeroHipError
     from pero_pretraining_amd.masked_pretraining import model as M

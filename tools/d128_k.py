@@ -23,10 +23,8 @@ for N, K in ((2048, 192), (2048, 512), (2048, 1024), (2048, 2048), (2048, 4096),
     out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
     fl = 2.0 * M * N * K
     r = []
-    for opt, var in ((0, 0), (64, 0)):
+    for opt in (0, 64):
         _lib.call("pero_set_option", b"gemm_d128", opt)
-        _lib.call("pero_set_option", b"gemm_e_var", var)
         r.append(bench(lambda: ops.gemm(x, w, out)))
     _lib.call("pero_set_option", b"gemm_d128", 0)
-    _lib.call("pero_set_option", b"gemm_e_var", 0)
     print(f"N={N} K={K}: e256 {r[0]:.0f} us ({fl / r[0] / 1e6:.0f} TF/s) | d128 {r[1]:.0f} us ({fl / r[1] / 1e6:.0f} TF/s)", flush=True)
