@@ -265,6 +265,34 @@ int pero_vq_gather(const float* x, const float* codebook, const int64_t* indices
 int pero_vq_ema_update(const float* x, const int64_t* indices, float* ema_cluster_size, float* ema_w, float* codebook,
                        float* work, int64_t M, int64_t K, int64_t D, double decay, double epsilon, void* stream);
 
+/* ---- mini-batch k-means fit (scripts/fit_kmeans.py: sklearn MiniBatchKMeans) -----------------------------
+ * Every sum has a fixed order (no float atomics): the same inputs give the same bits from run to run.
+ *
+ * One centre update with the semantics of sklearn's _minibatch_update_dense, in place: for every centre k with
+ * n_k > 0 rows in the batch  centers[k] = (centers[k]*weight_sums[k] + sum of its rows) / (weight_sums[k] + n_k),
+ * weight_sums[k] += n_k; centres without rows keep their bits.  shift_out[0] = sum_k |c_new - c_old|^2.
+ * x (B,D) f32; sorted_labels / order (B) int64: the batch labels sorted ascending (stable) and the permutation that
+ * sorts them (order[j] = batch row at sorted position j); centers (K,D) f32; weight_sums (K) f64.
+ * work: at least (2K + 1) * 4 bytes. */
+int pero_kmeans_update(const float* x, const int64_t* order, const int64_t* sorted_labels, float* centers,
+                       double* weight_sums, float* shift_out, void* work, int64_t B, int64_t K, int64_t D, void* stream);
+/* out[r] = |x_r|^2, x (rows,D) f32 */
+int pero_kmeans_sqnorm(const float* x, float* out, int64_t rows, int64_t D, void* stream);
+/* The work for one new centre of greedy k-means++ (sklearn _kmeans_plusplus): for each of the t candidate rows
+ * (1 <= t <= 32) the distances of all n rows, their minimum with closest_dist_sq and the potential (the sum of
+ * those minima); the candidate with the lowest potential (the first on a tie) is committed: chosen[0] = its row
+ * index, potential[0] = its potential (f64), closest_dist_sq (n, in/out) <- its minima.  sqnorm (n) = |x_i|^2.
+ * work: f32 workspace of at least 4 + t*n + t*ceil(n/64) elements. */
+int pero_kmeans_pp_step(const float* x, const float* sqnorm, float* closest_dist_sq, const int64_t* candidates,
+                        int64_t* chosen, double* potential, float* work, int64_t n, int64_t D, int64_t t, void* stream);
+/* Early stopping of the fit loop on the device (sklearn _mini_batch_convergence), one call per step.
+ * batch_inertia[0]: sum of the batch's squared distances to the centres before the update; shift[0]: shift_out of
+ * the update.  state (f64[6], zeroed by the caller before the first step): EWA inertia, its minimum, steps without
+ * improvement, stop flag, steps seen, step at which the flag was raised.  tol <= 0 and max_no_improvement < 0
+ * switch the respective rule off. */
+int pero_kmeans_converge(const float* batch_inertia, const float* shift, double* state, int64_t n_samples,
+                         int64_t batch_size, double tol, int64_t max_no_improvement, void* stream);
+
 /* ---- row gather / scatter by index (boolean-mask selections of the losses) ----------------------------- */
 /* dst[i] = src[index[i]] for i < n_idx, zero rows for n_idx <= i < n_rows_out (padding) */
 int pero_gather_rows(const void* src, const int64_t* index, void* dst, int64_t n_idx, int64_t n_rows_out,

@@ -434,6 +434,64 @@ def vq_ema_update(x, idx, ema_cluster_size, ema_w, codebook, decay, epsilon):
          float(decay), float(epsilon), stream())
 
 
+def sum_scale(partial, scale=1.0, out=None):
+    """out[0] = scale * sum(partial) in a fixed order (f32)."""
+    out = torch.empty(1, device=partial.device, dtype=torch.float32) if out is None else out
+    call("pero_sum_scale", ptr(partial), ptr(out), partial.numel(), float(scale), stream())
+    return out
+
+
+# ---- mini-batch k-means fit (scripts/kmeans.py) -------------------------------------------------------------------
+def kmeans_update(x, labels, centers, weight_sums, shift=None):
+    """In-place mini-batch centre update (sklearn _minibatch_update_dense): x (B, D) f32, labels (B) int64 from
+    `vq_argmin` on the centres as they are now, centers (K, D) f32, weight_sums (K) f64.  Returns the f32 scalar
+    tensor sum |c_new - c_old|^2.  Bit-identical from run to run: the stable sort fixes the order of every sum."""
+    _req_cuda(x, labels, centers, weight_sums)
+    B, D = x.shape
+    K = centers.shape[0]
+    assert labels.shape == (B,) and labels.dtype == torch.int64 and centers.shape == (K, D) and weight_sums.shape == (K,)
+    assert x.dtype == centers.dtype == torch.float32 and weight_sums.dtype == torch.float64
+    assert x.is_contiguous() and centers.is_contiguous() and weight_sums.is_contiguous()
+    sorted_labels, order = torch.sort(labels, stable=True)
+    shift = torch.empty(1, device=x.device, dtype=torch.float32) if shift is None else shift
+    work = torch.empty(2 * K + 2, device=x.device, dtype=torch.int32)
+    call("pero_kmeans_update", ptr(x), ptr(order), ptr(sorted_labels), ptr(centers), ptr(weight_sums), ptr(shift), ptr(work), B, K, D,
+         stream())
+    return shift
+
+
+def kmeans_sqnorm(x):
+    _req_cuda(x)
+    rows, d = x.shape
+    out = torch.empty(rows, device=x.device, dtype=torch.float32)
+    call("pero_kmeans_sqnorm", ptr(x), ptr(out), rows, d, stream())
+    return out
+
+
+def kmeans_pp_workspace(n, t, device):
+    return torch.empty(4 + t * n + t * ((n + 63) // 64), device=device, dtype=torch.float32)
+
+
+def kmeans_pp_step(x, sqnorm, closest_dist_sq, candidates, chosen, potential, work=None):
+    """One centre of greedy k-means++: of the candidate rows `candidates` (t int64) the one with the lowest potential
+    is committed - its index to chosen[0] (int64), its potential to potential[0] (f64), closest_dist_sq updated in
+    place.  No host synchronisation."""
+    _req_cuda(x, sqnorm, closest_dist_sq, candidates, chosen, potential)
+    n, d = x.shape
+    t = candidates.numel()
+    assert candidates.dtype == chosen.dtype == torch.int64 and potential.dtype == torch.float64 and x.is_contiguous()
+    work = kmeans_pp_workspace(n, t, x.device) if work is None else work
+    assert work.numel() >= 4 + t * n + t * ((n + 63) // 64)
+    call("pero_kmeans_pp_step", ptr(x), ptr(sqnorm), ptr(closest_dist_sq), ptr(candidates), ptr(chosen), ptr(potential), ptr(work), n, d, t,
+         stream())
+
+
+def kmeans_converge(batch_inertia, shift, state, n_samples, batch_size, tol, max_no_improvement):
+    """Advance the on-device early-stopping state (f64[6], see include/pero_hip.h) by one step."""
+    call("pero_kmeans_converge", ptr(batch_inertia), ptr(shift), ptr(state), int(n_samples), int(batch_size), float(tol),
+         -1 if max_no_improvement is None else int(max_no_improvement), stream())
+
+
 def gather_rows(src, index, n_rows_out=None, out=None):
     n_idx = index.numel()
     n_out = n_idx if n_rows_out is None else n_rows_out

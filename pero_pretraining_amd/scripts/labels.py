@@ -11,6 +11,7 @@ import json
 import numpy as np
 import torch
 
+from .. import ops
 from ..models.autoencoders import kmeans_labels
 
 
@@ -82,6 +83,31 @@ def compute_labels(encode, quantizer, dataset, batch_operator=None):
             for line_id, line_mask, line_labels in zip(batch["ids"], masks, labels):
                 data[line_id] = line_labels[line_mask == 1].tolist()
     return data
+
+
+def compute_features(encode, dataset, batch_operator=None):
+    """scripts/produce_features.py:25-49: the feature vectors of the positions inside the lines (`image_masks == 1`),
+    in dataset order, as ONE (M, D) f32 device tensor - the input of `scripts.kmeans.MiniBatchKMeans.fit`.  The rows
+    are compacted on the device (`ops.gather_rows` over the valid positions); no feature travels to the host.
+    `encode` -> (N, D, T) or (N, D, 1, T)."""
+    chunks = []
+    with torch.no_grad():
+        for batch in dataset:
+            images = batch_operator.prepare_batch(batch) if batch_operator is not None else batch["images"]
+            features = encode(images)
+            if features.dim() == 4:
+                features = features.squeeze(2)
+            n, d, t = features.shape
+            flat = features.permute(0, 2, 1).reshape(n * t, d).float().contiguous()
+            masks = batch["image_masks"]
+            masks = masks if isinstance(masks, torch.Tensor) else torch.from_numpy(np.asarray(masks))
+            assert tuple(masks.shape) == (n, t), (tuple(masks.shape), n, t)
+            index = torch.nonzero(masks.reshape(-1).to(flat.device) == 1).reshape(-1)
+            if index.numel():
+                chunks.append(ops.gather_rows(flat, index))
+    if not chunks:
+        raise ValueError("compute_features: the dataset has no valid position")
+    return torch.cat(chunks, 0)
 
 
 def compute_kmeans_labels(encode, centroids, dataset, output_path, batch_operator=None):
