@@ -14,6 +14,7 @@
 // K and V tiles arrive by LDS-DMA; K image XOR-swizzled for conflict-free ds_read_b128 (256-byte rows), V image
 // swizzled in 64-byte blocks for conflict-free transposed reads.  2 workgroups per CU (64 KiB LDS each).
 #include "common.hpp"
+#include "options.hpp"
 
 #define AT_HALF_BYTES 16384   // 64 rows x 256 B
 #define AT_PRIO(n_) __builtin_amdgcn_s_setprio(n_)
@@ -229,7 +230,6 @@ static int attn_heads_per_block(long long N, long long S, long long nh) {
   return hpb;
 }
 
-extern int g_attn_pipe;
 __global__ void attn_fwd_p_k(const bf16raw* qkv, bf16raw* out, float* lse2, int S, int nh, int hpb, float c);   // (defined behind the asm helpers)
 extern "C" int pero_attention_fwd(const void* qkv, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads,
                                   int64_t head_dim, int dtype, void* stream) {
@@ -241,7 +241,7 @@ extern "C" int pero_attention_fwd(const void* qkv, void* out, float* lse, int64_
   PERO_LDS_ATTR(attn_fwd_p_k, 2 * AT_TILE_BYTES);
   const float c = (float)(1.4426950408889634 / sqrt((double)head_dim));
   const int hpb = attn_heads_per_block(N, S, num_heads);
-  if (g_attn_pipe)
+  if (g_opt.attn_pipe)
     hipLaunchKernelGGL(attn_fwd_p_k, dim3((unsigned)(N * (num_heads / hpb) * (S / 128))), dim3(256), 2 * AT_TILE_BYTES, (hipStream_t)stream,
                        (const bf16raw*)qkv, (bf16raw*)out, lse, (int)S, (int)num_heads, hpb, c);
   else
@@ -1046,7 +1046,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pair_k(const bf16raw* qkv, co
 // LDS-DMA, 16 (4) bytes per lane: global address = sbase + voff, LDS address = dst + 16 (4) * lane
 // Every asm vector-memory instruction below that takes an SGPR base opens with wait states: a v_readlane_b32 / v_readfirstlane_b32 that has
 // just (re)written the SGPR - a restored spill - needs five of them before a vector-memory instruction reads it, and the compiler pads that
-// hazard for its own instructions only (gemm_e.hip's E_BSTORE16 took stale row offsets that way in round 3; tools/check_async_loads.py
+// hazard for its own instructions only (gemm_e_common.hpp's E_BSTORE16 took stale row offsets that way in round 3; tools/check_async_loads.py
 // checks the ISA of these kernels too: tests/test_cabi_and_host.py).  With the s_mov the LDS-DMA forms have s_nop 3 + 1.
 __device__ __forceinline__ void lh_dma16(const void* sbase, unsigned voff, unsigned dst) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %1, %0" :: "s"(sbase), "v"(voff), "s"(dst) : "memory", "m0");
@@ -1062,7 +1062,7 @@ __device__ __forceinline__ void lh_gload16(T& d, const void* sbase, unsigned vof
 __device__ __forceinline__ void lh_gload4(float& d, const void* sbase, unsigned voff) {
   asm volatile("s_nop 4\n\tglobal_load_dword %0, %1, %2" : "=v"(d) : "v"(voff), "s"(sbase) : "memory");
 }
-// (the trailing wait states: the data registers are rewritten right behind the store - see E_BSTORE16 in gemm_e.hip)
+// (the trailing wait states: the data registers are rewritten right behind the store - see E_BSTORE16 in gemm_e_common.hpp)
 template <int IMM, typename T>
 __device__ __forceinline__ void lh_gstore16(const T& v, void* sbase, unsigned voff) {
   static_assert(sizeof(T) == 16 && IMM >= 0 && IMM < 4096, "global_store_dwordx4");
@@ -1715,12 +1715,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
   }
 }
 
-
-int g_attn_bwd_pair = 1;  // pero_set_option("attn_bwd_pair", 0 / 1)
-int g_attn_order = 32;    // pero_set_option("attn_order", n): dispatch order of the paired backward's blocks (see attn_bwd_pair_k; 0 = a unit's four blocks side by side)
-int g_attn_lh = 0;        // pero_set_option("attn_lh", 0 / 1): S = 256 with D handed in and a bias gradient wanted -> the persistent (line, head) kernel
-                          // attn_bwd_lh_k.  Same bits; measured 735-745 us against 725-735 us of the paired kernels at 1024 lines: off
-int g_attn_pipe = 1;      // pero_set_option("attn_pipe", 0 / 1): the bodies with software-pipelined operand reads (default) / the compiler-scheduled ones
 extern "C" int pero_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
                                   float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim, int dtype,
                                   void* stream) {
@@ -1739,8 +1733,9 @@ extern "C" int pero_attention_bwd(const void* qkv, const void* out, const void* 
   const float c = (float)(1.4426950408889634 / sqrt((double)head_dim));
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((unsigned)(N * num_heads * (S / 128))), block(256);
-  if (!out && g_attn_bwd_pair && g_attn_lh && S == 256 && dbias && N * num_heads < (1LL << 20) && num_heads <= 1024) {   // (32-bit byte offsets inside a unit and inside the partial-sum workspace)
+  if (!out && g_opt.attn_bwd_pair && g_opt.attn_lh && S == 256 && dbias && N * num_heads < (1LL << 20) && num_heads <= 1024) {   // (32-bit byte offsets inside a unit and inside the partial-sum workspace)
     // one persistent workgroup per CU, a (line, head) per pass (attn_bwd_lh_k); its bias partials: one row per unit
+    // ("attn_lh", off: same bits; measured 735-745 us against 725-735 us of the paired kernels at 1024 lines)
     PERO_LDS_ATTR(attn_bwd_lh_k, LH_LDS_BYTES);
     const long long units = N * num_heads;
     const int cus = pero_num_cus();
@@ -1750,22 +1745,22 @@ extern "C" int pero_attention_bwd(const void* qkv, const void* out, const void* 
     PERO_CHECK_LAUNCH("pero_attention_bwd");
     return PERO_OK;
   }
-  if (!out && g_attn_bwd_pair) {
+  if (!out && g_opt.attn_bwd_pair) {
     const size_t lds = AT_DKV2_LDS > 2 * AT_TILE_BYTES ? AT_DKV2_LDS : 2 * AT_TILE_BYTES;
-    if (g_attn_pipe)
+    if (g_opt.attn_pipe)
       hipLaunchKernelGGL(attn_bwd_pair_k<true>, dim3(2 * grid.x), block, lds, st, (const bf16raw*)qkv, (const bf16raw*)dout, lse, dvec, (bf16raw*)dqkv,
-                         dbias ? work : nullptr, (int)S, (int)num_heads, c, scale, g_attn_order);
+                         dbias ? work : nullptr, (int)S, (int)num_heads, c, scale, g_opt.attn_order);
     else
       hipLaunchKernelGGL(attn_bwd_pair_k<false>, dim3(2 * grid.x), block, lds, st, (const bf16raw*)qkv, (const bf16raw*)dout, lse, dvec, (bf16raw*)dqkv,
-                         dbias ? work : nullptr, (int)S, (int)num_heads, c, scale, g_attn_order);
+                         dbias ? work : nullptr, (int)S, (int)num_heads, c, scale, g_opt.attn_order);
   } else {
-  if (g_attn_pipe)
+  if (g_opt.attn_pipe)
     hipLaunchKernelGGL(attn_bwd_dq_k<true>, grid, block, 2 * AT_TILE_BYTES, st, (const bf16raw*)qkv, (const bf16raw*)out, (const bf16raw*)dout, lse,
                        dvec, (bf16raw*)dqkv, dbias ? work : nullptr, (int)S, (int)num_heads, c, scale);
   else
     hipLaunchKernelGGL(attn_bwd_dq_k<false>, grid, block, 2 * AT_TILE_BYTES, st, (const bf16raw*)qkv, (const bf16raw*)out, (const bf16raw*)dout, lse,
                        dvec, (bf16raw*)dqkv, dbias ? work : nullptr, (int)S, (int)num_heads, c, scale);
-  if (g_attn_pipe)
+  if (g_opt.attn_pipe)
     hipLaunchKernelGGL(attn_bwd_dkv2_k<true>, grid, block, AT_DKV2_LDS, st, (const bf16raw*)qkv, (const bf16raw*)dout, lse, dvec,
                        (bf16raw*)dqkv, dbias ? work : nullptr, (int)S, (int)num_heads, c, scale);
   else

@@ -15,7 +15,7 @@
 #include "common.hpp"
 
 #include "gemm_common.hpp"
-#include <string.h>
+#include "options.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // fast bf16 kernel
@@ -365,41 +365,7 @@ __global__ __launch_bounds__(256) void gemm_generic(GemmP p) {
 //         * other stored products -> gemm_bf16_r256 (256x128x32, two workgroups per CU: small batches) when M is a multiple
 //           of 256, else the persistent 128x128x64 kernel of this file (also: batched products, PERO_GEMM_TILE128);
 //   forcing one family for A/B runs and tests: 1 = 128x128x64 persistent, 4 = o128, 7 = r256, 20 = e256 (any tile count).
-extern int g_attn_bwd_pair;           // attention.hip
-extern int g_attn_pipe;
-extern int g_attn_order;
-extern int g_attn_lh;
-extern int g_gemm_splitk_ws;          // gemm_e.hip
-extern int g_gemm_splitk_table;
-extern int g_gemm_nw;
-extern int g_gemm_d128;
-extern int g_gemm_e_walk;
-static int g_gemm_policy = 0;         // 0 = auto, 1 = 128x128x64 persistent kernel (this file), 4 = gemm_bf16_o128, 7 = gemm_bf16_r256, 20 = gemm_bf16_e256
-static int g_gemm_e256_min = 192;     // auto: stored products with at least this many 256x256 tiles take the eight-phase kernel (0 = never)
-static int g_gemm_e_splitk_min = 4;   // ... and split-K products (reduction >= 32768 rows) with at least this many output tiles
-static int g_splitk_items = 512;      // split-K of the 128x128 kernel aims at this many work items
-static int g_splitk_nearest = 0;
-int g_pero_splitk_xcd = 1;            // one k-slice per XCD where the slice count allows it (gemm_o.hip)
-extern "C" int pero_set_option(const char* name, int value) {
-  if (name && !strcmp(name, "gemm_policy")) { g_gemm_policy = value; return PERO_OK; }
-  if (name && !strcmp(name, "attn_bwd_pair")) { g_attn_bwd_pair = value; return PERO_OK; }
-  if (name && !strcmp(name, "attn_pipe")) { g_attn_pipe = value; return PERO_OK; }
-  if (name && !strcmp(name, "attn_order")) { g_attn_order = value; return PERO_OK; }
-  if (name && !strcmp(name, "attn_lh")) { g_attn_lh = value; return PERO_OK; }
-  if (name && !strcmp(name, "splitk_workspace")) { g_gemm_splitk_ws = value; return PERO_OK; }
-  if (name && !strcmp(name, "splitk_table")) { g_gemm_splitk_table = value; return PERO_OK; }
-  if (name && !strcmp(name, "gemm_nw")) { g_gemm_nw = value; return PERO_OK; }
-  if (name && !strcmp(name, "gemm_d128")) { g_gemm_d128 = value; return PERO_OK; }
-  if (name && !strcmp(name, "gemm_e_walk")) { g_gemm_e_walk = value; return PERO_OK; }
-  if (name && !strcmp(name, "gemm_e256_min")) { g_gemm_e256_min = value; return PERO_OK; }
-  if (name && !strcmp(name, "gemm_e_splitk_min")) { g_gemm_e_splitk_min = value; return PERO_OK; }
-  if (name && !strcmp(name, "splitk_xcd")) { g_pero_splitk_xcd = value; return PERO_OK; }
-  if (name && !strcmp(name, "splitk_nearest")) { g_splitk_nearest = value; return PERO_OK; }
-  if (name && !strcmp(name, "splitk_items")) { g_splitk_items = value > 0 ? value : 512; return PERO_OK; }
-  pero_set_error("pero_set_option: unknown option %s", name ? name : "(null)");
-  return PERO_E_INVALID;
-}
-
+// (the options and their defaults: options.hpp)
 static int gemm_dispatch(const void* A, const void* B, void* C, const float* bias, const void* residual, const void* gate,
                          int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int64_t ldg,
                          int64_t batch, int64_t batch_inner,
@@ -409,12 +375,12 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const float* bia
 
 // does a split-K product of this shape take the eight-phase kernel (whose partial tiles can go to a caller-owned workspace)?
 static bool splitk_takes_e256(int64_t M, int64_t N, int64_t K, int flags) {
-  const bool can256 = M % 256 == 0 && N % 256 == 0 && !(flags & PERO_GEMM_TILE128) && g_gemm_policy != 1;
+  const bool can256 = M % 256 == 0 && N % 256 == 0 && !(flags & PERO_GEMM_TILE128) && g_opt.gemm_policy != 1;
   const long long t256 = can256 ? (M / 256) * (N / 256) : 0;
   return can256 && K % 64 == 0 && K >= 128 &&
-         (g_gemm_policy == 20 || (g_gemm_policy == 0 && ((flags & PERO_GEMM_TILE256) || (g_gemm_e256_min > 0 && K >= 32768 && t256 >= g_gemm_e_splitk_min))));
+         (g_opt.gemm_policy == 20 || (g_opt.gemm_policy == 0 && ((flags & PERO_GEMM_TILE256) || (g_opt.gemm_e256_min > 0 && K >= 32768 && t256 >= g_opt.gemm_e_splitk_min))));
 }
-// Linear + residual + LayerNorm in one launch (the row-complete 128 x 512 tile of gemm_e.hip): Y = A W^T + bias + R (bf16, stored: the backward
+// Linear + residual + LayerNorm in one launch (the row-complete 128 x 512 tile of gemm_n.hip): Y = A W^T + bias + R (bf16, stored: the backward
 // needs it), T = (Y - mean) * rstd * gamma + beta over the ROUNDED rows of Y (layernorm_fwd4_k's arithmetic), mean / rstd (f32 per row).
 extern "C" int pero_gemm_resid_layernorm(const void* A, const void* W, const float* bias, const void* R, const float* gamma, const float* beta,
                                          void* Y, void* T, float* mean, float* rstd, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
@@ -516,13 +482,13 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const float* bia
               (sAo % 8 == 0) && (sAi % 8 == 0) && (sBo % 8 == 0) && (sBi % 8 == 0) && ((sCo * esz_o) % 16 == 0) &&
               ((sCi * esz_o) % 16 == 0) && (!residual || (ldr % 8 == 0 && aligned16(residual))) &&
               (!gate || (flags & PERO_GEMM_RELU_BITS) || (ldg % 8 == 0 && aligned16(gate))) && (!(residual || gate) || out_dtype == PERO_BF16 || true);
-  if (fast && g_gemm_policy == 1) { flags |= PERO_GEMM_TILE128; p.flags = flags; pc.flags = flags | cs_bits; }
+  if (fast && g_opt.gemm_policy == 1) { flags |= PERO_GEMM_TILE128; p.flags = flags; pc.flags = flags | cs_bits; }
   const bool force128 = flags & PERO_GEMM_TILE128, force256 = flags & PERO_GEMM_TILE256;
   PERO_REQUIRE(!(flags & PERO_GEMM_MASK_TILED) || ((flags & PERO_GEMM_RELU_BITS) && N % 256 == 0), "pero_gemm: PERO_GEMM_MASK_TILED needs PERO_GEMM_RELU_BITS and N %% 256 == 0");
   if (flags & PERO_GEMM_RELU_BITS) {
     // bit-mask ReLU gate: only the e256 / r256 epilogues read or write it
     PERO_REQUIRE(fast && gate && batch == 1 && out_dtype == PERO_BF16 && !ta && !(flags & PERO_GEMM_ATOMIC) && !force128 && M % 256 == 0 &&
-                 N % 128 == 0 && K % 32 == 0 && !(flags & PERO_GEMM_ROWDOT) && (g_gemm_policy == 0 || g_gemm_policy == 7 || g_gemm_policy == 20),
+                 N % 128 == 0 && K % 32 == 0 && !(flags & PERO_GEMM_ROWDOT) && (g_opt.gemm_policy == 0 || g_opt.gemm_policy == 7 || g_opt.gemm_policy == 20),
                  "pero_gemm: PERO_GEMM_RELU_BITS needs a bf16 product for the 256-row tile kernels (M %% 256, N %% 128, K %% 32, batch 1)");
   }
   if (fast) {
@@ -531,7 +497,7 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const float* bia
     const long long t256 = can256 ? (M / 256) * (N / 256) * batch : 0;
     const long long t128 = (M / T_BM) * (N / T_BN) * batch;
     const int k_split_req = k_split;
-    const bool auto_or = g_gemm_policy == 0;
+    const bool auto_or = g_opt.gemm_policy == 0;
     // the eight-phase persistent 256x256x64 kernel (gemm_e.hip): split-K weight gradients on long reductions ...
     if (atomic && out_dtype == PERO_F32 && batch == 1 && splitk_takes_e256(M, N, K, flags) &&
         pero_launch_gemm_e256(p, batch, k_split_req, ta, tb, true, st, workspace, workspace_bytes)) {
@@ -539,30 +505,30 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const float* bia
       return PERO_OK;
     }
     // the row-complete 128 x 512 tile (opt-in): N = 512 stored products with the plain / residual epilogue
-    if (!atomic && g_gemm_nw && !want_cs && out_dtype == PERO_BF16 && pero_launch_gemm_n512(p, batch, ta, tb, false, st)) {
+    if (!atomic && g_opt.gemm_nw && !want_cs && out_dtype == PERO_BF16 && pero_launch_gemm_n512(p, batch, ta, tb, false, st)) {
       PERO_CHECK_LAUNCH("pero_gemm(n512)");
       return PERO_OK;
     }
     // two workgroups per CU on 256 x 128 tiles (opt-in): stored products with few K-tiles per tile, plain / ReLU / bit-mask epilogues
-    if (!atomic && g_gemm_d128 && out_dtype == PERO_BF16 && !want_rd && K <= g_gemm_d128 * 64LL && (auto_or || g_gemm_policy == 20) &&
+    if (!atomic && g_opt.gemm_d128 && out_dtype == PERO_BF16 && !want_rd && K <= g_opt.gemm_d128 * 64LL && (auto_or || g_opt.gemm_policy == 20) &&
         pero_launch_gemm_d128(pc, batch, ta, tb, false, st)) {
       *colsum_fused = want_cs;
       PERO_CHECK_LAUNCH("pero_gemm(d128)");
       return PERO_OK;
     }
     // ... and stored bf16 products with every fused epilogue
-    if (!atomic && can256 && (g_gemm_policy == 20 || (auto_or && (force256 || (g_gemm_e256_min > 0 && t256 >= g_gemm_e256_min)))) &&
+    if (!atomic && can256 && (g_opt.gemm_policy == 20 || (auto_or && (force256 || (g_opt.gemm_e256_min > 0 && t256 >= g_opt.gemm_e256_min)))) &&
         pero_launch_gemm_e256(pc, batch, k_split, ta, tb, out_dtype == PERO_F32, st)) {
       *colsum_fused = want_cs;
       PERO_CHECK_LAUNCH("pero_gemm(e256)");
       return PERO_OK;
     }
     if (atomic && k_split == 0) {
-      long long ks = (g_splitk_items + t128 - 1) / t128;
+      long long ks = (g_opt.splitk_items + t128 - 1) / t128;
       if (ks > K / 512) ks = K / 512;
       if (ks < 1) ks = 1;
       // powers of two (<= 8) or multiples of 8: lets the kernel place one k-slice per XCD
-      if (ks >= 8) ks = ((ks + (g_splitk_nearest ? 4 : 7)) / 8) * 8;
+      if (ks >= 8) ks = ((ks + (g_opt.splitk_nearest ? 4 : 7)) / 8) * 8;
       else if (ks > 4) ks = 8;
       else if (ks == 3) ks = 4;
       if (ks > K / 64) ks = 1;
@@ -571,17 +537,17 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const float* bia
       k_split = 1;
     }
     // split-K atomics: one 128x128x64 tile per workgroup
-    if (!force128 && atomic && g_gemm_policy != 7 && pero_launch_gemm_o128(p, batch, k_split, ta, tb, out_dtype == PERO_F32, st)) {
+    if (!force128 && atomic && g_opt.gemm_policy != 7 && pero_launch_gemm_o128(p, batch, k_split, ta, tb, out_dtype == PERO_F32, st)) {
       PERO_CHECK_LAUNCH("pero_gemm(bf16 o128)");
       return PERO_OK;
     }
-    if (!force128 && !atomic && g_gemm_policy == 4 && !want_cs && !(flags & PERO_GEMM_RELU_BITS) &&
+    if (!force128 && !atomic && g_opt.gemm_policy == 4 && !want_cs && !(flags & PERO_GEMM_RELU_BITS) &&
         pero_launch_gemm_o128(p, batch, k_split, ta, tb, out_dtype == PERO_F32, st)) {
       PERO_CHECK_LAUNCH("pero_gemm(bf16 o128)");
       return PERO_OK;
     }
     // 256x128x32 tiles, two workgroups per CU: stored products of small batches; carries the column-sum / row-dot / bit-mask epilogues
-    if (!force128 && !atomic && g_gemm_policy != 4 && pero_launch_gemm_r256(want_cs ? pc : p, batch, k_split, ta, tb, out_dtype == PERO_F32, st)) {
+    if (!force128 && !atomic && g_opt.gemm_policy != 4 && pero_launch_gemm_r256(want_cs ? pc : p, batch, k_split, ta, tb, out_dtype == PERO_F32, st)) {
       *colsum_fused = want_cs;
       PERO_CHECK_LAUNCH("pero_gemm(bf16 r256)");
       return PERO_OK;

@@ -2,6 +2,7 @@
 // f32 epilogue staged through LDS (coalesced 16-byte stores).  Kept as the A/B baseline of the tile-kernel policy
 // (tools/step_ab.py) and used for split-K atomic products when selected.
 #include "gemm_common.hpp"
+#include "options.hpp"
 
 #define O_BM 128
 #define O_BN 128
@@ -251,9 +252,8 @@ bool pero_launch_gemm_o128(const GemmP& p0, long long batch, int k_split, bool t
   }
   dim3 grid((unsigned)((p.M / O_BM) * (p.N / O_BN)), (unsigned)batch, (unsigned)k_split), block(256);
   int ks_xcd = 0;
-  extern int g_pero_splitk_xcd;
   const long long tiles = (p.M / O_BM) * (p.N / O_BN);
-  if (g_pero_splitk_xcd && batch == 1 && k_split > 1 && (k_split == 2 || k_split == 4 || k_split % 8 == 0) && (tiles * k_split) % 8 == 0 &&
+  if (g_opt.splitk_xcd && batch == 1 && k_split > 1 && (k_split == 2 || k_split == 4 || k_split % 8 == 0) && (tiles * k_split) % 8 == 0 &&
       (k_split >= 8 || tiles % (8 / k_split) == 0)) {
     ks_xcd = k_split;
     grid = dim3((unsigned)(tiles * k_split), 1, 1);

@@ -202,7 +202,7 @@ def attention_bwd(qkv, p, dout, n, s, h):
 FUSED_ATTENTION = True  # bf16, head_dim 128, S % 128 == 0: flash-style HIP kernels; else batched GEMM + softmax
 
 
-FUSE_LN_FWD_MAX_K = 4096  # Linear + residual + LayerNorm as ONE launch (csrc/gemm_e.hip gemm_bf16_n512, pero_gemm_resid_layernorm) for reductions up to this
+FUSE_LN_FWD_MAX_K = 4096  # Linear + residual + LayerNorm as ONE launch (csrc/gemm_n.hip gemm_bf16_n512, pero_gemm_resid_layernorm) for reductions up to this
                           # length: at K = 512 (out-projection) the fused launch takes 509 us against 352 + 195 for the pair (524 288 rows), at
                           # K = 2048 (linear2) 1 133 against 931 + 190 - the row-complete tile runs 5 % behind the 256 x 256 one there; in the
                           # 2048-line step: never 147.7 ms, out-projection only 147.0, both 146.8.  0: never

@@ -137,7 +137,7 @@ def layernorm_fwd(x, gamma, beta, eps, pe=None, offsets=None, S=1):
 
 
 def gemm_resid_layernorm_ok(a, w, residual):
-    """Shapes the fused Linear + residual + LayerNorm launch takes (csrc/gemm_e.hip gemm_bf16_n512: bf16, 512 output columns)."""
+    """Shapes the fused Linear + residual + LayerNorm launch takes (csrc/gemm_n.hip gemm_bf16_n512: bf16, 512 output columns)."""
     return (a.dtype == torch.bfloat16 and a.dim() == 2 and w.dim() == 2 and w.shape[0] == 512 and a.shape[0] % 128 == 0 and a.shape[1] % 64 == 0 and
             a.shape[1] >= 192 and a.shape[1] == w.shape[1] and residual is not None and residual.shape == (a.shape[0], 512) and
             a.stride(1) == 1 and w.stride(1) == 1 and residual.stride(1) == 1 and a.stride(0) % 8 == 0 and w.stride(0) % 8 == 0 and residual.stride(0) % 8 == 0)
@@ -164,7 +164,7 @@ def gemm_resid_layernorm(a, w, bias, residual, gamma, beta, eps, store_y=True):
 
 
 def gemm_resid_layernorm_bwd_ok(a, w_t, residual, t):
-    """Shapes the fused input-gradient + LayerNorm-backward launch takes (csrc/gemm_e.hip gemm_bf16_n512, EP_RESID_LNB)."""
+    """Shapes the fused input-gradient + LayerNorm-backward launch takes (csrc/gemm_n.hip gemm_bf16_n512, EP_RESID_LNB)."""
     return (a.dtype == torch.bfloat16 and a.dim() == 2 and w_t.dim() == 2 and w_t.shape[0] == 512 and a.shape[0] % 128 == 0 and a.shape[1] % 64 == 0 and
             a.shape[1] >= 192 and a.shape[1] == w_t.shape[1] and residual is not None and residual.shape == (a.shape[0], 512) and
             t is not None and t.shape == (a.shape[0], 512) and a.stride(1) == 1 and w_t.stride(1) == 1 and residual.stride(1) == 1 and t.stride(1) == 1 and

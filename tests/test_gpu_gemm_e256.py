@@ -1,4 +1,5 @@
-"""The eight-phase persistent 256x256x64 bf16 GEMM (csrc/gemm_e.hip) against exact / f32 references and against the other
+"""The eight-phase persistent 256x256x64 bf16 GEMM (csrc/gemm_e.hip) and its siblings on the same schedule (gemm_bf16_d128 in csrc/gemm_d.hip,
+gemm_bf16_n512 in csrc/gemm_n.hip) against exact / f32 references and against the other
 tile kernels (bit for bit): every operand layout, every fused epilogue, the split-K mode, many tiles per workgroup."""
 import numpy as np
 import pytest
