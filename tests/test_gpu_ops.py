@@ -1,7 +1,11 @@
-"""GPU parity of every C-ABI kernel against the CPU oracle (oracle/pero_oracle.py) on seeded inputs.
-Integer / index outputs are compared bit-exact; f32-mode kernels to 1e-5 relative (different f32
-summation order than the CPU), bf16-mode kernels against an f32 evaluation of the same bf16-rounded
-inputs with a tolerance set by the bf16 output rounding (2^-8 relative)."""
+"""GPU parity of the C-ABI kernels of the masked step against the CPU oracle (oracle/pero_oracle.py) on seeded inputs: GEMM and its
+epilogues, fused attention, LayerNorm, softmax, masked cross entropy, Adam, the front end, the quantizer, gather / scatter, transposes.
+Integer / index outputs are compared bit-exact; f32-mode kernels to 1e-5 relative (different f32 summation order than the CPU), bf16-mode
+kernels against an f32 evaluation of the same bf16-rounded inputs with a tolerance set by the bf16 output rounding (2^-8 relative).  The
+softmax and masked-CE gradients at the shapes of the step's fast paths are held to the f64 restatements of tests/parity_ref.py through its
+`assert_within` bound.  The joint-embedding reductions (csrc/losses.hip), BatchNorm (csrc/bnorm.hip) and the small utilities are pinned in
+tests/test_gpu_kernel_parity.py, k-means in tests/test_gpu_kmeans.py, evaluation and collation in tests/test_gpu_next_rows.py; DESIGN.md
+section 5 lists, per entry point, the test that pins it."""
 import math
 
 import numpy as np
@@ -10,13 +14,15 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import parity_ref as R  # noqa: E402
 from oracle import pero_oracle as O  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def ops():
     from pero_pretraining_amd import ops as _ops
-    return _ops
+    yield _ops
+    print("\nPARITY_RATIOS " + repr({k: round(v, 4) for k, v in sorted(R.RATIOS.items())}))
 
 
 def dev(x, dtype=None):
@@ -221,10 +227,10 @@ def test_gemm_batched_strided_attention_shapes(ops):
     assert rel_err(out, ref_o) < 2 ** -8
 
 
-@pytest.mark.parametrize("n,s,h", [(2, 256, 2), (1, 128, 4), (2, 384, 1)])
+@pytest.mark.parametrize("n,s,h", [(2, 256, 2), (1, 128, 4), (2, 384, 1), (1, 512, 1)])
 def test_fused_attention_fwd_bwd(ops, n, s, h):
     """Flash-style kernels (scores never stored) vs the oracle's attention on the same bf16 inputs (f64), and
-    the gradients through it; exercises 1, 2 and 3 key tiles (online softmax rescale)."""
+    the gradients through it; exercises 1, 2, 3 and 4 key tiles (online softmax rescale)."""
     hd = 128
     d = h * hd
     g = torch.Generator().manual_seed(n * 1000 + s + h)
@@ -306,6 +312,75 @@ def test_attention_backward_variants_give_the_same_bits(ops, n):
         assert float((db - dbr).abs().max()) <= 1e-5 * max(1.0, float(dbr.abs().max())), name
     want = ref.float().sum(0)
     assert float((dbr - want).abs().max()) <= 1e-3 * max(1.0, float(want.abs().max()))
+
+
+def _attn_inputs(n, s, h, seed, spiked_lines):
+    """The recipe of test_fused_attention_fwd_bwd, drawn on the device (these cases hold up to 2048 lines): the spiked query / key rows in
+    every line of `spiked_lines`."""
+    d = h * 128
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    qkv = (torch.randn(n * s, 3 * d, device="cuda", generator=g) * 0.7).bfloat16()
+    for line in spiked_lines:
+        qkv[line * s + 5, :d] *= 6.0
+        qkv[line * s + s // 2 + 3, d:2 * d] *= 6.0
+    dout = torch.randn(n * s, d, device="cuda", generator=g).bfloat16()
+    return qkv, dout
+
+
+def _heads_per_block(n, s, h):
+    """csrc/attention.hip attn_heads_per_block: the largest divisor of the head count that keeps two workgroups per CU."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    return next((c for c in range(h, 0, -1) if h % c == 0 and n * (s // 128) * (h // c) >= 2 * cus), 1)
+
+
+@pytest.mark.parametrize("n,hpb", [(256, 4), (128, 2)])
+def test_fused_attention_fwd_several_heads_per_workgroup(ops, n, hpb):
+    """S = 256, four heads: from 128 lines on a workgroup walks two heads, from 256 lines all four (the forward the benchmark runs).  The
+    arithmetic of a (line, head) in attn_fwd_p_k does not depend on how many heads share the workgroup - running maximum, sum and output
+    accumulators start afresh at a head's first key tile, the MFMAs of a tile are issued in one order - so out and lse are, bit for bit, those
+    of the same call on 16-line chunks (one head per workgroup); three lines are also held to the oracle at the forward tolerances of
+    test_fused_attention_fwd_bwd (2^-7, 2e-3)."""
+    s, h, hd = 256, 4, 128
+    d = h * hd
+    assert _heads_per_block(n, s, h) == hpb and _heads_per_block(16, s, h) == 1
+    lines = (0, n // 2 - 1, n - 1)
+    qkv, _ = _attn_inputs(n, s, h, 5000 + n, lines)
+    out, lse = ops.attention_fwd_fused(qkv, n, s, h)
+    for lo in range(0, n, 16):
+        o1, l1 = ops.attention_fwd_fused(qkv[lo * s:(lo + 16) * s], 16, s, h)
+        assert torch.equal(out[lo * s:(lo + 16) * s], o1) and torch.equal(lse[lo * h:(lo + 16) * h], l1), lo
+    for line in lines:
+        rows = qkv[line * s:(line + 1) * s].double().cpu()
+        assert rel_err(out[line * s:(line + 1) * s], O.attention(rows, 1, s, h)) < 2 ** -7, line
+        q, k, _ = rows.reshape(1, s, 3, h, hd).permute(2, 0, 3, 1, 4)
+        lse_ref = torch.logsumexp((q @ k.transpose(-1, -2)) / math.sqrt(hd), -1) / math.log(2.0)
+        assert float((lse[line * h:(line + 1) * h].cpu().double().reshape(1, h, s) - lse_ref).abs().max()) < 2e-3, line
+
+
+@pytest.mark.parametrize("n", [512, 2048])
+def test_fused_attention_bias_gradient_wide_reductions(ops, n):
+    """One head, S = 256: 1024 workgroup rows per head take the 64-slice reduction of the in_proj bias gradient, 4096 the 128-slice one
+    (every other attention test stays below 1024: 16 slices).  dbias against the column sums of the stored dqkv as in
+    test_fused_attention_fwd_bwd (1e-3 of the largest sum), accumulated into a pre-filled vector; dqkv of the first and the last line against
+    the oracle at that test's tolerances (3e-2, cosine 0.9995)."""
+    s, h, hd = 256, 1, 128
+    d = h * hd
+    qkv, dout = _attn_inputs(n, s, h, 6000 + n, (0, n - 1))
+    out, lse = ops.attention_fwd_fused(qkv, n, s, h)
+    dvec = torch.stack([(out[lo:lo + 65536].float() * dout[lo:lo + 65536].float()).sum(-1) for lo in range(0, n * s, 65536)]).reshape(n * s, h)
+    dbias = torch.full((3 * d,), 2.0, device="cuda")
+    dqkv = ops.attention_bwd_fused(qkv, None, dout, lse, n, s, h, dbias=dbias, dvec=dvec)
+    want = 2.0 + dqkv.sum(0, dtype=torch.float64)
+    assert float((dbias.double() - want).abs().max()) <= 1e-3 * max(1.0, float(want.abs().max()))
+    assert float((dbias - 2.0).abs().max()) > 1.0
+    for line in (0, n - 1):
+        ref_in = qkv[line * s:(line + 1) * s].double().cpu().requires_grad_(True)
+        O.attention(ref_in, 1, s, h).backward(dout[line * s:(line + 1) * s].double().cpu())
+        got = dqkv[line * s:(line + 1) * s]
+        for name, sl in (("dq", slice(0, d)), ("dk", slice(d, 2 * d)), ("dv", slice(2 * d, 3 * d))):
+            assert rel_err(got[:, sl], ref_in.grad[:, sl]) < 3e-2, (line, name)
+            a, b = got[:, sl].double().cpu().flatten(), ref_in.grad[:, sl].flatten()
+            assert float(a @ b / (a.norm() * b.norm())) > 0.9995, (line, name)
 
 
 # ------------------------------------------------------------------------------------------ row kernels
@@ -492,6 +567,87 @@ def test_masked_ce(ops, dtype, uw):
     assert rows_c.shape == (n_out, V)
     assert torch.equal(rows_c[:sel.numel()], dl[dev(sel)])
     assert float(rows_c[sel.numel():].float().abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("rows,cols", [(1, 1), (5, 63), (6, 64), (7, 257), (130, 1000)])   # below / at / above one wave's 64 lanes, odd sizes, 33 blocks
+def test_softmax_fwd_bwd_against_f64(ops, dtype, rows, cols):
+    """Scores up to 300 at scale 0.3 (the exponent's argument spans 180) and a row of identical values; forward and backward inside the
+    derived bound of parity_ref.assert_within: `cols` terms in the row sum, the argument errors of expf (parity_ref.softmax), a reciprocal and
+    a product; backward: `cols` products in the dot, then three products."""
+    g = torch.Generator().manual_seed(rows * 1000 + cols)
+    s = (torch.rand(rows, cols, generator=g) * 2 - 1) * 300
+    s[rows // 2] = 123.0
+    dp = torch.randn(rows, cols, generator=g)
+    scale = float(np.float32(0.3))
+    p = ops.softmax_fwd(dev(s), scale, dtype)
+    ref, mag = R.softmax(s, scale)
+    R.assert_within(p, ref, mag["p"], cols, dtype, extra_ulps=mag["ulps"] + 1, what="pero_softmax_fwd")
+    ds = ops.softmax_bwd(p, dev(dp), scale)
+    rds, mds = R.softmax_bwd(p, dp, scale)      # from the probabilities the kernel stored (checked above)
+    R.assert_within(ds, rds, mds, cols + 3, dtype, what="pero_softmax_bwd")
+
+
+def _ce_inputs(rows, V, dtype, seed):
+    g = torch.Generator().manual_seed(seed)
+    logits = torch.randn(rows, V, generator=g) * 3
+    hot = torch.arange(0, rows, 5)                                       # a fifth of the rows: one +80 and one -80
+    logits[hot, torch.randint(0, V, (hot.numel(),), generator=g)] = 80.0
+    logits[hot, torch.randint(0, V, (hot.numel(),), generator=g)] = -80.0
+    labels = torch.randint(0, V, (rows,), generator=g)
+    labels[rows - rows // 6:] = -1
+    mask = (torch.rand(rows, generator=g) < 0.3).long() * (labels >= 0)
+    return logits.to(dtype), labels, mask
+
+
+def _check_masked_ce(ops, logits, logits_dev, labels, mask, uw):
+    """loss at test_masked_ce's 2e-6; gradients (dloss null and 0.5) inside assert_within: V terms in the row's sum of exponentials, the
+    argument errors of the two expf and the logf (parity_ref.masked_ce), the division by the row count and two products."""
+    rows, V = logits.shape
+    (loss_ref, grad_ref), mag = R.masked_ce(logits, labels, mask, uw)
+    loss, work = ops.masked_ce_fwd(logits_dev, dev(labels), dev(mask), uw)
+    print(f"masked_ce {tuple(logits.shape)} {logits.dtype} uw={uw}: loss {float(loss)!r} ref {float(loss_ref)!r}")
+    assert abs(float(loss) - float(loss_ref)) < 2e-6 * abs(float(loss_ref))
+    dl = ops.masked_ce_bwd(logits_dev, dev(labels), dev(mask), work, uw)
+    R.assert_within(dl, grad_ref, mag["grad"], V, logits.dtype, extra_ulps=mag["ulps"] + 3, what="pero_masked_ce_bwd")
+    dl2 = ops.masked_ce_bwd(logits_dev, dev(labels), dev(mask), work, uw, dloss=torch.full((1,), 0.5, device="cuda"))
+    R.assert_within(dl2, 0.5 * grad_ref, 0.5 * mag["grad"], V, logits.dtype, extra_ulps=mag["ulps"] + 4, what="pero_masked_ce_bwd")
+    return loss, work, dl
+
+
+@pytest.mark.parametrize("uw", [None, 0.25])
+@pytest.mark.parametrize("rows,V,dtype", [(1000, 4096, torch.float32), (1000, 4096, torch.bfloat16),   # whole row in registers; each part of ce_final_k sums 16 rows
+                                          (70, 8192, torch.float32), (70, 8192, torch.bfloat16)])       # looped forward, 16-byte backward
+def test_masked_ce_vector_paths(ops, rows, V, dtype, uw):
+    logits, labels, mask = _ce_inputs(rows, V, dtype, rows + V)
+    loss, work, dl = _check_masked_ce(ops, logits, dev(logits), labels, mask, uw)
+    if V != 4096:
+        return
+    # the compact forms at the head's width: what test_masked_ce asserts at V = 333
+    sel = torch.nonzero(mask == 1).reshape(-1)
+    if uw is None:
+        loss_c, work_c = ops.masked_ce_fwd_rows(dev(logits), dev(labels), dev(mask), dev(sel))
+        assert torch.equal(loss_c, loss)
+        assert torch.equal(ops.masked_ce_bwd(dev(logits), dev(labels), dev(mask), work_c, uw), dl)
+    extra = torch.nonzero((mask == 0) & (labels < 0)).reshape(-1)[:2]
+    index = torch.cat([sel, extra])
+    n_out = ((index.numel() + 15) // 16) * 16 + 16
+    rows_c = ops.masked_ce_bwd_rows(dev(logits), dev(labels), dev(mask), work, dev(index), n_out, uw)
+    assert rows_c.shape == (n_out, V)
+    assert torch.equal(rows_c[:sel.numel()], dl[dev(sel)])
+    assert float(rows_c[sel.numel():].float().abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("uw", [None, 0.25])
+def test_masked_ce_rows_not_16_byte_aligned(ops, uw):
+    """bf16, V = 4096, logits a view that starts 8 bytes into its buffer: the whole-row-in-registers forward and the 16-byte backward must
+    step aside; the values stay inside the same bound."""
+    logits, labels, mask = _ce_inputs(70, 4096, torch.bfloat16, 70 + 4096 + 1)
+    base = torch.empty(logits.numel() + 8, device="cuda", dtype=torch.bfloat16)
+    view = base[4:4 + logits.numel()].view(logits.shape)
+    view.copy_(logits)
+    assert view.data_ptr() % 16 == 8
+    _check_masked_ce(ops, logits, view, labels, mask, uw)
 
 
 def test_masked_ce_empty_mask_is_nan(ops):
