@@ -66,7 +66,7 @@ extern "C" {
 const char* pero_last_error(void);
 int pero_abi_version(void);
 /* tuning knobs for benchmarking and tests (defaults are the measured best; the one table: csrc/options.hpp): "gemm_policy" (0 = auto, 1 / 4 / 7 / 20 = force
- * one tile-kernel family, table in csrc/gemm.hip), "attn_bwd_pair" (1: the attention backward with D handed in runs as one launch, csrc/attention.hip),
+ * one tile-kernel family, table in csrc/gemm.hip), "attn_bwd_pair" (1: the attention backward with D handed in runs as one launch, csrc/attention_bwd.hip),
  * "attn_pipe" (1: attention loops with software-pipelined inline-asm operand reads; 0: the compiler-scheduled loops - same bits), "attn_lh" (0; 1: S = 256
  * backward as one persistent workgroup per CU and (line, head) - same bits, not faster), "splitk_workspace" (1: the split-K
  * products of the eight-phase kernel leave partial tiles in the caller's `workspace`, summed in slice order by a second kernel - deterministic;

@@ -4,7 +4,7 @@ Token layout: every activation is a row-major (N*S, d) matrix of token rows (lin
 what the reference reaches after its `n d s -> s n d` / `s n d -> n d s` transposes
 (models/transformers.py:82-89) - those are pure layout and vanish here.
 
-Attention: bf16 with head_dim 128 and S % 128 == 0 runs the fused flash-style kernels of csrc/attention.hip on the
+Attention: bf16 with head_dim 128 and S % 128 == 0 runs the fused flash-style kernels of csrc/attention_fwd.hip / attention_bwd.hip / attention_lh.hip on the
 packed qkv tensor (scores never stored; one f32 log-sum-exp per query saved for the backward); f32 parity mode and other
 shapes take the unfused form of torch SDPA - per (line, head) batched GEMMs + a row softmax kernel, scores in f32.
 Every product of the backward pass is pero_gemm with a different operand-layout flag: input gradients as K-contiguous

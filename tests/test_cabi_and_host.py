@@ -290,10 +290,12 @@ def test_inline_asm_vector_memory_of_the_tile_gemm_passes_the_isa_lint(tmp_path)
 
 
 def test_inline_asm_vector_memory_of_the_attention_kernels_passes_the_sgpr_lint(tmp_path):
-    """The same SGPR hazard check on csrc/attention.hip (round-3 advice): its asm global_load_dword* / global_store_dword* / global_load_lds
+    """The same SGPR hazard check on the three attention files csrc/attention_fwd.hip, attention_bwd.hip, attention_lh.hip and their header
+    attention_common.hpp: their asm global_load_dword* / global_store_dword* / global_load_lds
     statements take an SGPR base, the kernels hold 20-38 v_readlane / v_readfirstlane each, and nothing but the `s_nop`s inside the asm strings
     keeps a restored SGPR five wait states away from the vector-memory instruction that reads it.  (Only the SGPR check: the in-flight-register
     check models straight-line code and the attention loops are compiler-scheduled.)"""
+    import re
     import shutil
     import subprocess
     import sys
@@ -301,14 +303,21 @@ def test_inline_asm_vector_memory_of_the_attention_kernels_passes_the_sgpr_lint(
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = str(tmp_path / "attention.s")
-    subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-ffp-contract=off", "-Wno-unused-value",
-                    "-S", "--cuda-device-only", os.path.join(root, "pero_pretraining_amd", "csrc", "attention.hip"), "-o", out],
-                   check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "check_async_loads.py"), out, "attn", "--sgpr-only"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:]
-    assert "attn_fwd_p_k" in r.stdout and "attn_bwd_pair_k" in r.stdout and "attn_bwd_lh_k" in r.stdout
-    src = open(os.path.join(root, "pero_pretraining_amd", "csrc", "attention.hip")).read()
-    import re
-    for m in re.finditer(r'asm volatile\("([^"]*(?:global_load_dword|global_store_dword)[^"]*)"', src):
-        assert m.group(1).startswith("s_nop 4"), "asm vector-memory statement without leading wait states: " + m.group(1)[:60]
+    csrc = os.path.join(root, "pero_pretraining_amd", "csrc")
+    files = ("attention_fwd", "attention_bwd", "attention_lh")
+    compiles = {name: subprocess.Popen([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-ffp-contract=off",
+                                        "-Wno-unused-value", "-S", "--cuda-device-only", os.path.join(csrc, name + ".hip"), "-o", str(tmp_path / (name + ".s"))],
+                                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL) for name in files}   # side by side
+    linted = ""
+    for name in files:
+        assert compiles[name].wait() == 0, name
+        r = subprocess.run([sys.executable, os.path.join(root, "tools", "check_async_loads.py"), str(tmp_path / (name + ".s")), "attn", "--sgpr-only"],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, (name, r.stdout[-2000:])
+        linted += r.stdout
+    assert "attn_fwd_p_k" in linted and "attn_bwd_pair_k" in linted and "attn_bwd_lh_k" in linted
+    src = "".join(open(os.path.join(csrc, name)).read() for name in [f + ".hip" for f in files] + ["attention_common.hpp"])
+    statements = re.findall(r'asm volatile\("([^"]*(?:global_load_dword|global_store_dword)[^"]*)"', src)
+    assert len(statements) >= 4, statements          # lh_gload16, lh_gload4, lh_gstore16, lh_gstore4: as many as the one-file source had
+    for text in statements:
+        assert text.startswith("s_nop 4"), "asm vector-memory statement without leading wait states: " + text[:60]

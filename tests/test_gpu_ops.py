@@ -328,7 +328,7 @@ def _attn_inputs(n, s, h, seed, spiked_lines):
 
 
 def _heads_per_block(n, s, h):
-    """csrc/attention.hip attn_heads_per_block: the largest divisor of the head count that keeps two workgroups per CU."""
+    """csrc/attention_fwd.hip attn_heads_per_block: the largest divisor of the head count that keeps two workgroups per CU."""
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     return next((c for c in range(h, 0, -1) if h % c == 0 and n * (s // 128) * (h // c) >= 2 * cus), 1)
 
