@@ -180,17 +180,18 @@ int pero_softmax_fwd(const float* s, void* p, int64_t rows, int64_t cols, float 
 int pero_softmax_bwd(const void* p, const float* dp, void* ds, int64_t rows, int64_t cols, float scale, int dtype,
                      void* stream);
 
-/* ---- fused attention (bf16, head_dim 128, S % 128 == 0) on the packed qkv (N*S, 3*nh*128) tensor -----------------
+/* ---- fused attention (bf16, head_dim 128, any S >= 1) on the packed qkv (N*S, 3*nh*128) tensor -------------------
  * out (N*S, nh*128) = softmax(q k^T / sqrt(hd)) v per (line, head); lse (N*nh, S) f32 = base-2 log-sum-exp of the
- * scaled scores (kept for the backward kernels).  Scores never touch memory.  Other shapes / f32: use the
- * batched pero_gemm + pero_softmax_* path. */
+ * scaled scores (kept for the backward kernels).  Scores never touch memory.  A line is cut into ceil(S/128) blocks of 128
+ * rows; when S % 128 != 0 the last block is ragged: no address outside the line's S rows is read or written, and out,
+ * lse, dvec and dqkv keep their unpadded shapes.  Other head dims / f32: use the batched pero_gemm + pero_softmax_* path. */
 int pero_attention_fwd(const void* qkv, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads,
                        int64_t head_dim, int dtype, void* stream);
 /* dqkv (N*S, 3d) from dout (N*S, d).  dvec (N*S, nh) f32: D[row][head] = sum over the head's 128 columns of dout*out -
  * computed and stored by the call when `out` is given, or supplied by the caller (out == null; e.g. written by the
  * PERO_GEMM_ROWDOT epilogue of the product that produced dout).  dbias (f32 [3d], may be null):
  * the column sums of dqkv - in_proj's bias gradient - are ACCUMULATED into it: per-workgroup partial rows from the kernels'
- * staged output tiles into work (f32, 3 * N * nh * (S/128) * 128 elements; required with dbias), then one small reduction. */
+ * staged output tiles into work (f32, 3 * N * nh * ceil(S/128) * 128 elements; required with dbias), then one small reduction. */
 int pero_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
                        float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim, int dtype,
                        void* stream);

@@ -7,7 +7,8 @@
 //   attn_bwd_dkv2_body : 128 keys, key on the lane, sweeps the queries in 32-query sub-tiles: S = Q K^T, P, dP = dO V^T, dS;
 //                        dV^T += dO^T P, dK^T += Q^T dS.
 // each compiler-scheduled and as `_p` with software-pipelined operand reads (attention_common.hpp; pero_set_option("attn_pipe"), same MFMAs
-// in the same order, same bits).  Kernels: attn_bwd_dq_k<PIPE> then attn_bwd_dkv2_k<PIPE> (two launches: dq writes D), attn_bwd_pair_k<PIPE>
+// in the same order, same bits).  The `_p` bodies also have a RAGGED form for S % 128 != 0 (the three rules: attention_common.hpp), which the
+// launcher selects for every such S; the compiler-scheduled bodies and attn_bwd_lh_k take full tiles only.  Kernels: attn_bwd_dq_k<PIPE> then attn_bwd_dkv2_k<PIPE> (two launches: dq writes D), attn_bwd_pair_k<PIPE>
 // (both bodies in one launch when D is handed in), attn_bias_reduce_k.  No atomics in dqkv, deterministic; costs 7 MFMA products instead of
 // the minimal 5 (attention is ~8 % of the step's FLOPs).  All LDS tiles use the ONE dual-use image of attention_common.hpp.
 // Who waits for whom: every stage loop opens with vmcnt(0) + barrier (the stage has landed, every wave is done with the other buffer) and
@@ -20,8 +21,11 @@
 // segments (the direct form was 16 scattered 8-byte stores per lane); the staged rows also give the tile's column sums -
 // this (line, head) block's share of in_proj's bias gradient - for 128 (x2) atomics instead of a pass over dqkv.
 // Image: 128 rows x 256 B, 8-byte granule index XORed with (row & 31): conflict-free ds_write_b64 and ds_read_b128.
+// RAGGED: only the tile's first `nrows` rows exist in the line and are stored; the staged rows behind them are exact zeros (the bodies see to
+// that), so the column sums need no change.
+template <bool RAGGED = false>
 __device__ __forceinline__ void attn_store_tile(const f16v (&acc)[4], unsigned char* stg, bf16raw* out_base, long long ld,
-                                                float* colsum, int tid, int wave, int r, int h5) {
+                                                float* colsum, int tid, int wave, int r, int h5, int nrows = 128) {
   __syncthreads();  // the staging region is free (every wave is past its last tile read)
   const int row_w = wave * 32 + r;
 #pragma unroll
@@ -42,7 +46,7 @@ __device__ __forceinline__ void attn_store_tile(const f16v (&acc)[4], unsigned c
     const int x = row & 31;
     uint4 v = *(const uint4*)(stg + row * 256 + ((ch ^ (x >> 1)) << 4));
     if (x & 1) { const unsigned t0 = v.x, t1 = v.y; v.x = v.z; v.y = v.w; v.z = t0; v.w = t1; }
-    *(uint4*)(out_base + (long long)row * ld + ch * 8) = v;
+    if (!RAGGED || row < nrows) *(uint4*)(out_base + (long long)row * ld + ch * 8) = v;
   }
   if (colsum) {
     // Column sums of the staged tile (this (line, head) block's share of in_proj's bias gradient) on the MATRIX pipe, which idles through
@@ -193,34 +197,36 @@ __device__ __forceinline__ constexpr int dq_after(int j) {   // LDS instructions
   for (int k = j + 1; k <= j + DQ_DEPTH && k < 48; k++) n += dq_ninstr(k);
   return n;
 }
+template <bool RAGGED>
 __device__ __forceinline__ void attn_bwd_dq_body_p(unsigned char* smem, int lh, int qb, const bf16raw* qkv, const bf16raw* out,
                                                    const bf16raw* dout, const float* lse2, float* dvec, bf16raw* dqkv, float* dbias, int S,
                                                    int nh, float c, float scale) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h5 = lane >> 5, r = lane & 31;
-  const int nqb = S >> 7;
+  const int nqb = RAGGED ? (S + 127) >> 7 : S >> 7;
   const int line = lh / nh, head = lh % nh;
   const long long d = (long long)nh * 128, ld = 3 * d;
   const bf16raw* base = qkv + (long long)line * S * ld + head * 128;
   const bf16raw* Kg = base + d;
   const bf16raw* Vg = base + 2 * d;
   const int q = qb * 128 + wave * 32 + r;
+  const int qc = RAGGED ? (q < S - 1 ? q : S - 1) : q;   // ragged: a query >= S reads the line's last row; its dS is forced to 0 below
 
-  attn_glds_img<4>(Kg, ld, smem, wave, lane);
-  attn_glds_img<4>(Vg, ld, smem + AT_HALF_BYTES, wave, lane);
+  attn_glds_img<4, RAGGED>(Kg, ld, smem, wave, lane, S - 1);
+  attn_glds_img<4, RAGGED>(Vg, ld, smem + AT_HALF_BYTES, wave, lane, S - 1);
 
   bf8v qf[8], gf[8];
   float dsum = 0.f;
-  const long long dix = ((long long)line * S + q) * nh + head;
+  const long long dix = ((long long)line * S + qc) * nh + head;
   {
-    const bf16raw* qrow = base + (long long)q * ld + 8 * h5;
-    const bf16raw* grow = dout + ((long long)line * S + q) * d + head * 128 + 8 * h5;
+    const bf16raw* qrow = base + (long long)qc * ld + 8 * h5;
+    const bf16raw* grow = dout + ((long long)line * S + qc) * d + head * 128 + 8 * h5;
 #pragma unroll
     for (int ks = 0; ks < 8; ks++) {
       qf[ks] = *(const bf8v*)(qrow + 16 * ks);
       gf[ks] = *(const bf8v*)(grow + 16 * ks);
     }
     if (out) {
-      const bf16raw* orow = out + ((long long)line * S + q) * d + head * 128 + 8 * h5;
+      const bf16raw* orow = out + ((long long)line * S + qc) * d + head * 128 + 8 * h5;
 #pragma unroll
       for (int ks = 0; ks < 8; ks++) {
         const bf8v of = *(const bf8v*)(orow + 16 * ks);
@@ -228,12 +234,12 @@ __device__ __forceinline__ void attn_bwd_dq_body_p(unsigned char* smem, int lh, 
         for (int e = 0; e < 8; e++) dsum += (float)gf[ks][e] * (float)of[e];
       }
       dsum += __shfl_xor(dsum, 32, 64);
-      if (h5 == 0) dvec[dix] = dsum;
+      if (h5 == 0 && (!RAGGED || q < S)) dvec[dix] = dsum;
     } else {
       dsum = dvec[dix];
     }
   }
-  const float lq = lse2[(long long)lh * S + q];
+  const float lq = lse2[(long long)lh * S + qc];
 
   // fragment addresses inside a stage (byte offsets from the stage's K image): row fragments per ks, transposed fragments per dt
   const unsigned s0 = at_lds_addr(smem);
@@ -255,15 +261,15 @@ __device__ __forceinline__ void attn_bwd_dq_body_p(unsigned char* smem, int lh, 
   f16v dq[4];
 #pragma unroll
   for (int t = 0; t < 4; t++) dq[t] = (f16v){0};
-  const int nhalf = S >> 6;
+  const int nhalf = RAGGED ? (S + 63) >> 6 : S >> 6;   // ragged: a last half without a key is not swept
   for (int hk = 0; hk < nhalf; hk++) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // half hk landed; every wave is done with the other buffer
     const unsigned stage = s0 + (hk & 1) * 2 * AT_HALF_BYTES;
     if (hk + 1 < nhalf) {
       unsigned char* nb = smem + ((hk + 1) & 1) * 2 * AT_HALF_BYTES;
-      attn_glds_img<4>(Kg + (long long)(hk + 1) * 64 * ld, ld, nb, wave, lane);
-      attn_glds_img<4>(Vg + (long long)(hk + 1) * 64 * ld, ld, nb + AT_HALF_BYTES, wave, lane);
+      attn_glds_img<4, RAGGED>(Kg + (long long)(hk + 1) * 64 * ld, ld, nb, wave, lane, S - 1 - (hk + 1) * 64);
+      attn_glds_img<4, RAGGED>(Vg + (long long)(hk + 1) * 64 * ld, ld, nb + AT_HALF_BYTES, wave, lane, S - 1 - (hk + 1) * 64);
     }
     bf8v fr[8];
     f16v s, dp;
@@ -293,6 +299,14 @@ __device__ __forceinline__ void attn_bwd_dq_body_p(unsigned char* smem, int lh, 
           const float p = __builtin_amdgcn_exp2f(fmaf(s[e], c, -lq));
           s[e] = p * (dp[e] - dsum) * scale;
         }
+        if (RAGGED && (hk == nhalf - 1 || qb == nqb - 1)) {
+          // dS^T selected to 0 for keys >= S (the line's last half) and queries >= S (its last query block): the staged dQ rows of such
+          // queries are exact zeros.  Key of s[e] inside the sub-tile = 8 (e >> 2) + 4 h5 + (e & 3)
+          constexpr int t = j / 24;
+          const int lim = q < S ? S - hk * 64 - t * 32 - 4 * h5 : 0;
+#pragma unroll
+          for (int e = 0; e < 16; e++) s[e] = (8 * (e >> 2) + (e & 3) < lim) ? s[e] : 0.f;
+        }
         dsf[0] = pack8(s, 0);
         dsf[1] = pack8(s, 1);
         AT_PRIO(1);
@@ -311,17 +325,18 @@ __device__ __forceinline__ void attn_bwd_dq_body_p(unsigned char* smem, int lh, 
     });
     AT_PRIO(0);
   }
-  attn_store_tile(dq, smem, dqkv + ((long long)line * S + qb * 128) * ld + head * 128, ld,
-                  dbias ? dbias + ((long long)lh * nqb + qb) * 128 : nullptr, tid, wave, r, h5);
+  attn_store_tile<RAGGED>(dq, smem, dqkv + ((long long)line * S + qb * 128) * ld + head * 128, ld,
+                          dbias ? dbias + ((long long)lh * nqb + qb) * 128 : nullptr, tid, wave, r, h5, S - qb * 128);
 }
-template <bool PIPE>
+// (RAGGED implies PIPE in all three kernels: the launcher sees to it)
+template <bool PIPE, bool RAGGED = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_k(const bf16raw* qkv, const bf16raw* out, const bf16raw* dout, const float* lse2,
                                                         float* dvec, bf16raw* dqkv, float* dbias, int S, int nh, float c, float scale) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int nqb = S >> 7;
+  const int nqb = RAGGED ? (S + 127) >> 7 : S >> 7;
   int lh, qb;
   attn_block_map(blockIdx.x, nqb, gridDim.x / nqb, lh, qb);
-  if (PIPE) attn_bwd_dq_body_p(smem, lh, qb, qkv, out, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
+  if (PIPE) attn_bwd_dq_body_p<RAGGED>(smem, lh, qb, qkv, out, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
   else attn_bwd_dq_body(smem, lh, qb, qkv, out, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
 }
 
@@ -424,29 +439,39 @@ __device__ __forceinline__ void attn_bwd_dkv2_body(unsigned char* smem, int lh, 
 #define DKV_TD (DKV_POOL - 1)        // transposed fragments in flight: 5 .. 7
 #define DKV_RDEPTH (DKV_POOL - 2)   // row fragments in flight (a dP product holds two pool entries: dO and V); transposed fragments: 7
                                     // in flight (two LDS instructions each: 14 of the 15 the counter can hold)
+template <bool RAGGED>
 __device__ __forceinline__ void attn_bwd_dkv2_body_p(unsigned char* smem, int lh, int kb, long long nwg, const bf16raw* qkv, const bf16raw* dout,
                                                      const float* lse2, const float* dvec, bf16raw* dqkv, float* dbias, int S, int nh, float c,
                                                      float scale) {
   unsigned char* vimg = smem + 4 * AT_SUB_BYTES;
   float* lds_ld = (float*)(smem + 4 * AT_SUB_BYTES + AT_TILE_BYTES);  // [2 buffers][32 lse2 | 32 D]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h5 = lane >> 5, r = lane & 31;
-  const int nkb = S >> 7;
+  const int nkb = RAGGED ? (S + 127) >> 7 : S >> 7;
   const int line = lh / nh, head = lh % nh;
   const long long d = (long long)nh * 128, ld = 3 * d;
   const bf16raw* base = qkv + (long long)line * S * ld + head * 128;
   const bf16raw* Gg = dout + (long long)line * S * d + head * 128;
   const int key = kb * 128 + wave * 32 + r;
+  const int kc = RAGGED ? (key < S - 1 ? key : S - 1) : key;   // ragged: a key >= S computes on the line's last row; its dK / dV rows are zeroed below
+  // row statistics of a 32-query stage: threads 0-31 load lse2[lh][q], threads 32-63 load D[(line*S + q)*nh + head]   (ragged: q clamped to S - 1)
   const float* stat = tid < 32 ? lse2 + (long long)lh * S + tid : dvec + ((long long)line * S + (tid & 31)) * nh + head;
   const long long stat_step = tid < 32 ? 32 : 32LL * nh;
+  // ragged: the queries >= S of the line's LAST stage take the statistics of the line's last row - one per-lane element offset, used in that stage only
+  int stat_tail = 0;
+  if constexpr (RAGGED) {
+    const int qs = (((S + 31) >> 5) - 1) * 32 + (tid & 31);
+    stat_tail = qs < S ? 0 : (S - 1 - qs) * (tid < 32 ? 1 : nh);
+  }
 
-  if (tid < 64) lds_ld[tid] = stat[0];
-  attn_glds_img<8>(base + 2 * d + (long long)kb * 128 * ld, ld, vimg, wave, lane);  // this workgroup's V tile, resident
-  attn_glds_img<2>(base, ld, smem, wave, lane);
-  attn_glds_img<2>(Gg, d, smem + AT_SUB_BYTES, wave, lane);
+  if constexpr (RAGGED) { if (tid < 64) lds_ld[tid] = stat[S <= 32 ? stat_tail : 0]; }
+  else if (tid < 64) lds_ld[tid] = stat[0];
+  attn_glds_img<8, RAGGED>(base + 2 * d + (long long)kb * 128 * ld, ld, vimg, wave, lane, S - 1 - kb * 128);  // this workgroup's V tile, resident
+  attn_glds_img<2, RAGGED>(base, ld, smem, wave, lane, S - 1);
+  attn_glds_img<2, RAGGED>(Gg, d, smem + AT_SUB_BYTES, wave, lane, S - 1);
 
   bf8v kf[8];
   {
-    const bf16raw* krow = base + d + (long long)key * ld + 8 * h5;
+    const bf16raw* krow = base + d + (long long)kc * ld + 8 * h5;
 #pragma unroll
     for (int ks = 0; ks < 8; ks++) kf[ks] = *(const bf8v*)(krow + 16 * ks);
   }
@@ -470,7 +495,7 @@ __device__ __forceinline__ void attn_bwd_dkv2_body_p(unsigned char* smem, int lh
   f16v dv[4], dk[4];
 #pragma unroll
   for (int t = 0; t < 4; t++) { dv[t] = (f16v){0}; dk[t] = (f16v){0}; }
-  const int nsub = S >> 5;
+  const int nsub = RAGGED ? (S + 31) >> 5 : S >> 5;   // ragged: stages without a query are not swept
   for (int sq = 0; sq < nsub; sq++) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // stage sq (Q / dO rows + statistics) landed; every wave is done with the other buffers
@@ -479,10 +504,11 @@ __device__ __forceinline__ void attn_bwd_dkv2_body_p(unsigned char* smem, int lh
     const float* lds_d = lds_l + 32;
     float nstat = 0.f;
     if (sq + 1 < nsub) {
-      if (tid < 64) nstat = stat[(sq + 1) * stat_step];  // before the DMA: vmcnt is in-order
+      if constexpr (RAGGED) { if (tid < 64) nstat = stat[(sq + 1) * stat_step + (sq + 2 == nsub ? stat_tail : 0)]; }
+      else if (tid < 64) nstat = stat[(sq + 1) * stat_step];  // before the DMA: vmcnt is in-order
       unsigned char* nb = smem + ((sq + 1) & 1) * 2 * AT_SUB_BYTES;
-      attn_glds_img<2>(base + (long long)(sq + 1) * 32 * ld, ld, nb, wave, lane);
-      attn_glds_img<2>(Gg + (long long)(sq + 1) * 32 * d, d, nb + AT_SUB_BYTES, wave, lane);
+      attn_glds_img<2, RAGGED>(base + (long long)(sq + 1) * 32 * ld, ld, nb, wave, lane, S - 1 - (sq + 1) * 32);
+      attn_glds_img<2, RAGGED>(Gg + (long long)(sq + 1) * 32 * d, d, nb + AT_SUB_BYTES, wave, lane, S - 1 - (sq + 1) * 32);
     }
     bf8v fr[DKV_POOL];
     f16v s, dp;
@@ -540,7 +566,8 @@ __device__ __forceinline__ void attn_bwd_dkv2_body_p(unsigned char* smem, int lh
       at_wait_lgkm2<after>(l4[g4], d4[g4]);
 #pragma unroll
       for (int e = 0; e < 4; e++) {
-        const float p = __builtin_amdgcn_exp2f(fmaf(s[4 * g4 + e], c, -l4[g4][e]));
+        float p = __builtin_amdgcn_exp2f(fmaf(s[4 * g4 + e], c, -l4[g4][e]));
+        if constexpr (RAGGED) p = (sq * 32 + 8 * g4 + 4 * h5 + e < S) ? p : 0.f;   // queries >= S (the last stage): P = 0, so dS = 0 (its other factor is finite)
         s[4 * g4 + e] = p;                                              // P
         dp[4 * g4 + e] = p * (dp[4 * g4 + e] - d4[g4][e]) * scale;     // dS
       }
@@ -563,29 +590,36 @@ __device__ __forceinline__ void attn_bwd_dkv2_body_p(unsigned char* smem, int lh
     AT_PRIO(0);
     if (sq + 1 < nsub && tid < 64) lds_ld[((sq + 1) & 1) * 64 + tid] = nstat;  // visible after the next barrier
   }
+  if constexpr (RAGGED) {   // keys >= S computed on a copy of the last key: their staged dK / dV rows are exact zeros
+    const bool live = key < S;
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) { dk[t][e] = live ? dk[t][e] : 0.f; dv[t][e] = live ? dv[t][e] : 0.f; }
+  }
   bf16raw* tile_o = dqkv + ((long long)line * S + kb * 128) * ld + d + head * 128;  // dK tile; dV tile = + d columns
-  attn_store_tile(dk, smem, tile_o, ld, dbias ? dbias + (nwg + (long long)lh * nkb + kb) * 128 : nullptr, tid, wave, r, h5);
-  attn_store_tile(dv, smem, tile_o + d, ld, dbias ? dbias + (2 * nwg + (long long)lh * nkb + kb) * 128 : nullptr, tid, wave, r, h5);
+  attn_store_tile<RAGGED>(dk, smem, tile_o, ld, dbias ? dbias + (nwg + (long long)lh * nkb + kb) * 128 : nullptr, tid, wave, r, h5, S - kb * 128);
+  attn_store_tile<RAGGED>(dv, smem, tile_o + d, ld, dbias ? dbias + (2 * nwg + (long long)lh * nkb + kb) * 128 : nullptr, tid, wave, r, h5, S - kb * 128);
 }
-template <bool PIPE>
+template <bool PIPE, bool RAGGED = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv2_k(const bf16raw* qkv, const bf16raw* dout, const float* lse2, const float* dvec,
                                                           bf16raw* dqkv, float* dbias, int S, int nh, float c, float scale) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int nkb = S >> 7;
+  const int nkb = RAGGED ? (S + 127) >> 7 : S >> 7;
   int lh, kb;
   attn_block_map(blockIdx.x, nkb, gridDim.x / nkb, lh, kb);
-  if (PIPE) attn_bwd_dkv2_body_p(smem, lh, kb, gridDim.x, qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
+  if (PIPE) attn_bwd_dkv2_body_p<RAGGED>(smem, lh, kb, gridDim.x, qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
   else attn_bwd_dkv2_body(smem, lh, kb, gridDim.x, qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
 }
 // Both backward kernels as ONE launch (D already computed: `out` is not read, so no workgroup depends on another): the 2 x (S / 128)
 // workgroups of a (line, head) - its dQ blocks and its dK / dV blocks, which all read the same Q, K, V and dO rows - sit next to
 // each other in one XCD's dispatch order, so the rows come from HBM once and the other readers find them in that XCD's L2
 // (FETCH_SIZE of the backward at 256 lines: 534 MB as two launches, 308 MB paired, 267 MB = each row once; 789 -> 740 us at 1024 lines).
-template <bool PIPE>
+template <bool PIPE, bool RAGGED = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_pair_k(const bf16raw* qkv, const bf16raw* dout, const float* lse2, float* dvec,
                                                           bf16raw* dqkv, float* dbias, int S, int nh, float c, float scale, int order) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int nb = S >> 7;
+  const int nb = RAGGED ? (S + 127) >> 7 : S >> 7;
   int lh, blk;
   attn_block_map(blockIdx.x, 2 * nb, gridDim.x / (2 * nb), lh, blk);
   {   // Dispatch order inside an XCD (pero_set_option("attn_order", n); default 32): chunks of 32 units whose 64 dK / dV blocks - one round of the XCD's 64 workgroup
@@ -610,10 +644,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pair_k(const bf16raw* qkv, co
     }
   }
   if (blk < nb) {
-    if (PIPE) attn_bwd_dq_body_p(smem, lh, blk, qkv, nullptr, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
+    if (PIPE) attn_bwd_dq_body_p<RAGGED>(smem, lh, blk, qkv, nullptr, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
     else attn_bwd_dq_body(smem, lh, blk, qkv, nullptr, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
   } else {
-    if (PIPE) attn_bwd_dkv2_body_p(smem, lh, blk - nb, (long long)(gridDim.x >> 1), qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
+    if (PIPE) attn_bwd_dkv2_body_p<RAGGED>(smem, lh, blk - nb, (long long)(gridDim.x >> 1), qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
     else attn_bwd_dkv2_body(smem, lh, blk - nb, (long long)(gridDim.x >> 1), qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
   }
 }
@@ -623,15 +657,16 @@ extern "C" int pero_attention_bwd(const void* qkv, const void* out, const void* 
                                   float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim, int dtype,
                                   void* stream) {
   PERO_REQUIRE(qkv && dout && lse && dvec && dqkv, "pero_attention_bwd: null pointer");
-  PERO_REQUIRE(dtype == PERO_BF16 && head_dim == 128 && S % 128 == 0 && S > 0 && N > 0 && num_heads > 0,
-               "pero_attention_bwd: fused kernel needs bf16, head_dim 128, S %% 128 == 0");
+  PERO_REQUIRE(dtype == PERO_BF16 && head_dim == 128 && S > 0 && N > 0 && num_heads > 0, "pero_attention_bwd: fused kernel needs bf16, head_dim 128, S > 0");
   PERO_REQUIRE(aligned16(qkv) && (!out || aligned16(out)) && aligned16(dout) && aligned16(dqkv), "pero_attention_bwd: 16-byte alignment");
   PERO_REQUIRE(!dbias || work, "pero_attention_bwd: dbias needs the partial-sum workspace");
   static const bool lds_attrs_once = [] {
     const struct { const void* kernel; int bytes; } attrs[] = {
         {(const void*)attn_bwd_dq_k<false>, 2 * AT_TILE_BYTES}, {(const void*)attn_bwd_dq_k<true>, 2 * AT_TILE_BYTES},
         {(const void*)attn_bwd_dkv2_k<false>, AT_DKV2_LDS},     {(const void*)attn_bwd_dkv2_k<true>, AT_DKV2_LDS},
-        {(const void*)attn_bwd_pair_k<false>, AT_PAIR_LDS},     {(const void*)attn_bwd_pair_k<true>, AT_PAIR_LDS}};
+        {(const void*)attn_bwd_pair_k<false>, AT_PAIR_LDS},     {(const void*)attn_bwd_pair_k<true>, AT_PAIR_LDS},
+        {(const void*)attn_bwd_dq_k<true, true>, 2 * AT_TILE_BYTES}, {(const void*)attn_bwd_dkv2_k<true, true>, AT_DKV2_LDS},
+        {(const void*)attn_bwd_pair_k<true, true>, AT_PAIR_LDS}};
     for (const auto& a : attrs) hipFuncSetAttribute(a.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, a.bytes);
     return true;
   }();
@@ -639,7 +674,9 @@ extern "C" int pero_attention_bwd(const void* qkv, const void* out, const void* 
   const float scale = (float)(1.0 / sqrt((double)head_dim));
   const float c = (float)(1.4426950408889634 / sqrt((double)head_dim));
   hipStream_t st = (hipStream_t)stream;
-  dim3 grid((unsigned)(N * num_heads * (S / 128))), block(256);
+  const int64_t nb = (S + 127) / 128;   // query blocks = key blocks of a line; the last one is ragged when S % 128 != 0
+  const bool ragged = S % 128 != 0;     // then the RAGGED instantiations of the pipelined bodies run, whatever "attn_pipe" says
+  dim3 grid((unsigned)(N * num_heads * nb)), block(256);
   if (!out && g_opt.attn_bwd_pair && g_opt.attn_lh && S == 256 && dbias && N * num_heads < (1LL << 20) && num_heads <= 1024) {   // (32-bit byte offsets inside a unit and inside the partial-sum workspace)
     // one persistent workgroup per CU, a (line, head) per pass (attn_bwd_lh_k); its bias partials: one row per unit
     // ("attn_lh", off: same bits; measured 735-745 us against 725-735 us of the paired kernels at 1024 lines)
@@ -653,16 +690,16 @@ extern "C" int pero_attention_bwd(const void* qkv, const void* out, const void* 
   bf16raw* dq_ = (bf16raw*)dqkv;
   float* const part = dbias ? work : nullptr;   // the partial-sum workspace of the bias gradient
   if (!out && g_opt.attn_bwd_pair) {
-    hipLaunchKernelGGL(pipe ? attn_bwd_pair_k<true> : attn_bwd_pair_k<false>, dim3(2 * grid.x), block, AT_PAIR_LDS, st, q_, g_, lse, dvec, dq_, part,
+    hipLaunchKernelGGL((ragged ? attn_bwd_pair_k<true, true> : pipe ? attn_bwd_pair_k<true> : attn_bwd_pair_k<false>), dim3(2 * grid.x), block, AT_PAIR_LDS, st, q_, g_, lse, dvec, dq_, part,
                        (int)S, (int)num_heads, c, scale, g_opt.attn_order);
   } else {
-    hipLaunchKernelGGL(pipe ? attn_bwd_dq_k<true> : attn_bwd_dq_k<false>, grid, block, 2 * AT_TILE_BYTES, st, q_, o_, g_, lse, dvec, dq_, part,
+    hipLaunchKernelGGL((ragged ? attn_bwd_dq_k<true, true> : pipe ? attn_bwd_dq_k<true> : attn_bwd_dq_k<false>), grid, block, 2 * AT_TILE_BYTES, st, q_, o_, g_, lse, dvec, dq_, part,
                        (int)S, (int)num_heads, c, scale);
-    hipLaunchKernelGGL(pipe ? attn_bwd_dkv2_k<true> : attn_bwd_dkv2_k<false>, grid, block, AT_DKV2_LDS, st, q_, g_, lse, dvec, dq_, part,
+    hipLaunchKernelGGL((ragged ? attn_bwd_dkv2_k<true, true> : pipe ? attn_bwd_dkv2_k<true> : attn_bwd_dkv2_k<false>), grid, block, AT_DKV2_LDS, st, q_, g_, lse, dvec, dq_, part,
                        (int)S, (int)num_heads, c, scale);
   }
   if (dbias)
-    hipLaunchKernelGGL(attn_bias_reduce_k, dim3((unsigned)num_heads, 3, (N * (S / 128) >= 4096) ? 128 : (N * (S / 128) >= 1024) ? 64 : 16), dim3(128), 0, st, work, dbias, (int)N, (int)num_heads, (int)(S / 128));
+    hipLaunchKernelGGL(attn_bias_reduce_k, dim3((unsigned)num_heads, 3, (N * nb >= 4096) ? 128 : (N * nb >= 1024) ? 64 : 16), dim3(128), 0, st, work, dbias, (int)N, (int)num_heads, (int)nb);
   PERO_CHECK_LAUNCH("pero_attention_bwd");
   return PERO_OK;
 }

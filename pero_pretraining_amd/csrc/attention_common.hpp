@@ -1,7 +1,13 @@
 // What the three attention kernel families share: the forward (attention_fwd.hip), the tiled backward (attention_bwd.hip) and the persistent
 // (line, head) backward (attention_lh.hip).  Fused multi-head attention for the encoder layers (torch SDPA inside
 // TransformerEncoderLayer._sa_block, reference models/transformers.py:36-43,86): softmax(q k^T / sqrt(hd)) v over all S keys of a line, no
-// masks; bf16, head_dim 128, S a multiple of 128, operating directly on the packed qkv (N*S, 3d) tensor.
+// masks; bf16, head_dim 128, any S >= 1, operating directly on the packed qkv (N*S, 3d) tensor.
+// Ragged S (S % 128 != 0): a line has nb = ceil(S / 128) query blocks and key tiles, the last one with S - 128 (nb - 1) rows.  The launchers then
+// start the RAGGED = true instantiations of the PIPELINED bodies (attn_fwd_p_k, attn_bwd_dq_body_p, attn_bwd_dkv2_body_p) whatever "attn_pipe"
+// says - the compiler-scheduled bodies have no ragged form - under three rules: (1) every row index that feeds a global address is clamped to
+// the line's last row (the LDS-DMA source rows here, the Q / dO / O / lse / D reads in the bodies), so a tail row holds a copy of a real row and
+// every MFMA operand is finite; (2) P is SELECTED to 0 wherever the key >= S or the query >= S; (3) every row store is guarded by row < S.
+// S % 128 == 0 starts RAGGED = false: the code of before, bit for bit.
 // In this header: the AT_* sizes; the LDS-DMA tile loaders and the fragment reads of the forward's K and V images and of the backward's
 // dual-use image (img_f); the workgroup -> ((line, head), block) map; the software-pipelining helpers (at_*: operand reads by inline asm, each
 // MFMA tied to a counted lgkmcnt); those asm wrappers of the persistent backward (lh_*) that the pipelined forward uses too; the declaration of
@@ -25,28 +31,38 @@ typedef short s8v __attribute__((ext_vector_type(8)));
 //   V image (forward):         64-byte block index ^ (row & 3)                conflict-free transposed reads (ds_read_b64_tr_b16)
 //   dual-use image (backward): slot ^ img_f(row), img_f = ((row&3)<<2)|((row>>2)&3)   conflict-free for both kinds of read, so K (dQ bodies)
 //                              and Q, dO (dK / dV bodies) are staged once
+// RAGGED: LDS row `row` receives source row min(row, lim.last), lim.last = the last row of the line counted from g (>= 0): the source address is per
+// lane, the swizzle stays that of the LDS row.
 // a whole 128 x 128 tile (pieces 0..31) of the forward's K (VIMG = false) or V (true) image
-template <bool VIMG>
-__device__ __forceinline__ void attn_glds_tile(const bf16raw* g, long long ld, unsigned char* lds, int wave, int lane) {
+// The limit's type has a default only in the full-tile form, which ignores it: a ragged call without a limit does not compile.
+struct at_no_limit { __device__ constexpr at_no_limit(int = 0) {} };
+struct at_row_limit { int last; __device__ constexpr at_row_limit(int l) : last(l) {} };
+template <bool RAGGED> using at_limit = std::conditional_t<RAGGED, at_row_limit, at_no_limit>;
+template <bool VIMG, bool RAGGED = false>
+__device__ __forceinline__ void attn_glds_tile(const bf16raw* g, long long ld, unsigned char* lds, int wave, int lane, at_limit<RAGGED> lim = {}) {
 #pragma unroll
   for (int i = 0; i < 8; i++) {
     const int p = wave + 4 * i;
     const int row = 4 * p + (lane >> 4), slot = lane & 15;
     const int chunk = VIMG ? ((((slot >> 2) ^ (row & 3)) << 2) | (slot & 3)) : (slot ^ (row & 15));
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + (long long)row * ld + chunk * 8),
+    int srow = row;
+    if constexpr (RAGGED) srow = row < lim.last ? row : lim.last;
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + (long long)srow * ld + chunk * 8),
                                      (__attribute__((address_space(3))) void*)(lds + p * 1024), 16, 0, 0);
   }
 }
 __device__ __forceinline__ int img_f(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 // NP pieces per wave of the dual-use image: 8 = a 128-row tile (32 KiB), 4 = a 64-row half (16 KiB), 2 = a 32-row stage (8 KiB)
-template <int NP>
-__device__ __forceinline__ void attn_glds_img(const bf16raw* g, long long ld, unsigned char* lds, int wave, int lane) {
+template <int NP, bool RAGGED = false>
+__device__ __forceinline__ void attn_glds_img(const bf16raw* g, long long ld, unsigned char* lds, int wave, int lane, at_limit<RAGGED> lim = {}) {
 #pragma unroll
   for (int i = 0; i < NP; i++) {
     const int p = wave + 4 * i;
     const int row = 4 * p + (lane >> 4), slot = lane & 15;
     const int chunk = slot ^ img_f(row);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + (long long)row * ld + chunk * 8),
+    int srow = row;
+    if constexpr (RAGGED) srow = row < lim.last ? row : lim.last;
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + (long long)srow * ld + chunk * 8),
                                      (__attribute__((address_space(3))) void*)(lds + p * 1024), 16, 0, 0);
   }
 }

@@ -1,6 +1,7 @@
 // Forward of the fused attention: attn_fwd_k (compiler-scheduled loop), attn_fwd_p_k (the same loop with software-pipelined operand reads,
 // the default: pero_set_option("attn_pipe")) and their launcher pero_attention_fwd.  One workgroup = 128 queries of one (line, head); 4 waves x
-// 32 queries.  Keys are processed in tiles of 128 (online softmax across tiles).  Everything is computed TRANSPOSED so that a query lives
+// 32 queries.  Keys are processed in tiles of 128 (online softmax across tiles).  S % 128 != 0 always runs attn_fwd_p_k<RAGGED = true> (the
+// ragged last tile: attention_common.hpp); attn_fwd_k takes S % 128 == 0 only.  Everything is computed TRANSPOSED so that a query lives
 // on a LANE and keys / head-dim live on registers (guide section 3 "an accumulator tile as the next MFMA's operand"):
 //   S^T tile (32 keys x 32 q)  = mfma_32x32x16(A = K rows from LDS, B = Q^T from registers)
 //   row max / sum of a query    = in-lane reduction over its 64 score registers + ONE lane^32 exchange
@@ -172,27 +173,29 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(const bf16raw* qkv, bf16raw
 // (six in flight), the first seven transposed V fragments in flight while the exponentials run, then rolling.  Same MFMAs in the
 // same order: out and lse are bit-identical to attn_fwd_k.
 #define FW_POOL 8
+template <bool RAGGED>
 __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16raw* out, float* lse2, int S, int nh, int hpb, float c) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* kimg = smem;
   unsigned char* vimg = smem + AT_TILE_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h5 = lane >> 5, r = lane & 31;
-  const int nqb = S >> 7, ngrp = nh / hpb;
+  const int nqb = RAGGED ? (S + 127) >> 7 : S >> 7, ngrp = nh / hpb;
   int lg, qb;
   attn_block_map(blockIdx.x, nqb, gridDim.x / nqb, lg, qb);
   const int line = lg / ngrp, head0 = (lg % ngrp) * hpb;
   const long long d = (long long)nh * 128, ld = 3 * d;
   const bf16raw* lbase = qkv + (long long)line * S * ld;  // + head * 128 : q ; + d : k ; + 2d : v
   const int q = qb * 128 + wave * 32 + r;  // this lane's query (both lane halves hold the same query)
-  const int nkt = S >> 7, units = hpb * nkt;
+  const int nkt = nqb, units = hpb * nkt;
 
-  attn_glds_tile<false>(lbase + head0 * 128 + d, ld, kimg, wave, lane);
-  attn_glds_tile<true>(lbase + head0 * 128 + 2 * d, ld, vimg, wave, lane);
+  attn_glds_tile<false, RAGGED>(lbase + head0 * 128 + d, ld, kimg, wave, lane, S - 1);
+  attn_glds_tile<true, RAGGED>(lbase + head0 * 128 + 2 * d, ld, vimg, wave, lane, S - 1);
 
   // this lane's Q row fragments by loads the compiler does not see (it waits vmcnt(0) for its own loads once LDS-DMA is in flight, which
   // would also wait for the V tile the loop top lets fly): uniform base + 32-bit lane offset
   bf8v qf[8];
-  const unsigned qoff = (unsigned)((long long)q * ld * 2 + 16 * h5);
+  const int qc = RAGGED ? (q < S - 1 ? q : S - 1) : q;   // ragged: a query >= S computes on a copy of the line's last row and stores nothing
+  const unsigned qoff = (unsigned)((long long)qc * ld * 2 + 16 * h5);
   auto load_q = [&](int head) {
     const bf16raw* qb_ = lbase + head * 128;
     at_static_for<0, 8>([&](auto kc) __attribute__((always_inline)) { constexpr int ks = decltype(kc)::value; lh_gload16<32 * ks>(qf[ks], qb_, qoff); });
@@ -243,7 +246,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
     lh_barrier();  // every wave is done with the K image; V(u) landed
     if (u + 1 < units) {
       const int nhd = head0 + (u + 1) / nkt, nkt_i = (u + 1) % nkt;
-      attn_glds_tile<false>(lbase + nhd * 128 + d + (long long)nkt_i * 128 * ld, ld, kimg, wave, lane);
+      attn_glds_tile<false, RAGGED>(lbase + nhd * 128 + d + (long long)nkt_i * 128 * ld, ld, kimg, wave, lane, S - 1 - nkt_i * 128);
     }
     // ---- transposed V fragments: m = (t, sub, dt), seven in flight; the first seven go out in front of the softmax arithmetic
     auto issue_v = [&](auto mc) __attribute__((always_inline)) {
@@ -253,6 +256,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
     };
     at_static_for<0, 7>(issue_v);
 
+    if (RAGGED && kt == nkt - 1) {
+      // the line's last key tile: scores of keys >= S (copies of the last key's) become -inf in front of the running maximum, so their P is exactly
+      // 0; the tile holds at least one real key, so the maximum stays finite.  Key of s[t][e] = 32 t + 8 (e >> 2) + 4 h5 + (e & 3)
+      const int lim = S - kt * 128 - 4 * h5;
+#pragma unroll
+      for (int t = 0; t < 4; t++)
+#pragma unroll
+        for (int e = 0; e < 16; e++) s[t][e] = (32 * t + 8 * (e >> 2) + (e & 3) < lim) ? s[t][e] : -INFINITY;
+    }
     // ---- online softmax, all lane-local except one lane^32 exchange per reduction
     float mx = s[0][0];
 #pragma unroll
@@ -316,7 +328,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
           lh_ds_write8(vbase + qrow_l * 256 + ((g ^ (qrow_l & 31)) << 3), w);
         }
       // base-2 LSE of c*scores (both lane halves hold it and store it: same value, same address)
-      lh_gstore4(m * c + __builtin_amdgcn_logf(l), lse2 + ((long long)line * nh + head) * S, (unsigned)q * 4u);
+      if (!RAGGED || q < S) lh_gstore4(m * c + __builtin_amdgcn_logf(l), lse2 + ((long long)line * nh + head) * S, (unsigned)q * 4u);
       lh_wait_lgkm_plain<0>();
       lh_barrier();
       {
@@ -333,7 +345,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
           const int row = (tid_l >> 4) + 16 * i;
           at_u4v x = v[i];
           if (row & 1) x = (at_u4v){v[i][2], v[i][3], v[i][0], v[i][1]};
-          lh_gstore16<0>(x, out + ((long long)line * S + qb * 128) * d + head * 128, (unsigned)(row * (int)d * 2 + ch * 16));
+          if (!RAGGED || qb * 128 + row < S) lh_gstore16<0>(x, out + ((long long)line * S + qb * 128) * d + head * 128, (unsigned)(row * (int)d * 2 + ch * 16));
         }
       }
       if (u + 1 < units) {  // next head: fresh statistics, its Q rows (the loads complete under the loop-top wait)
@@ -347,7 +359,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
     if (u + 1 < units) {
       lh_barrier();  // every wave is done with the V image (and with the O staging reads)
       const int nhd = head0 + (u + 1) / nkt, nkt_i = (u + 1) % nkt;
-      attn_glds_tile<true>(lbase + nhd * 128 + 2 * d + (long long)nkt_i * 128 * ld, ld, vimg, wave, lane);
+      attn_glds_tile<true, RAGGED>(lbase + nhd * 128 + 2 * d + (long long)nkt_i * 128 * ld, ld, vimg, wave, lane, S - 1 - nkt_i * 128);
     }
   }
 }
@@ -357,21 +369,24 @@ static int attn_heads_per_block(long long N, long long S, long long nh) {
   const int num_cus = pero_num_cus();
   int hpb = 1;
   for (int cand = (int)nh; cand >= 1; cand--)
-    if (nh % cand == 0 && N * (S / 128) * (nh / cand) >= 2LL * num_cus) { hpb = cand; break; }
+    if (nh % cand == 0 && N * ((S + 127) / 128) * (nh / cand) >= 2LL * num_cus) { hpb = cand; break; }
   return hpb;
 }
 
 extern "C" int pero_attention_fwd(const void* qkv, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads,
                                   int64_t head_dim, int dtype, void* stream) {
   PERO_REQUIRE(qkv && out && lse, "pero_attention_fwd: null pointer");
-  PERO_REQUIRE(dtype == PERO_BF16 && head_dim == 128 && S % 128 == 0 && S > 0 && N > 0 && num_heads > 0,
-               "pero_attention_fwd: fused kernel needs bf16, head_dim 128, S %% 128 == 0 (got hd=%lld S=%lld)", (long long)head_dim, (long long)S);
+  PERO_REQUIRE(dtype == PERO_BF16 && head_dim == 128 && S > 0 && N > 0 && num_heads > 0,
+               "pero_attention_fwd: fused kernel needs bf16, head_dim 128, S > 0 (got hd=%lld S=%lld)", (long long)head_dim, (long long)S);
   PERO_REQUIRE(aligned16(qkv) && aligned16(out), "pero_attention_fwd: 16-byte alignment");
   PERO_LDS_ATTR(attn_fwd_k, 2 * AT_TILE_BYTES);
-  PERO_LDS_ATTR(attn_fwd_p_k, 2 * AT_TILE_BYTES);
+  PERO_LDS_ATTR(attn_fwd_p_k<false>, 2 * AT_TILE_BYTES);
+  PERO_LDS_ATTR(attn_fwd_p_k<true>, 2 * AT_TILE_BYTES);
   const float c = (float)(1.4426950408889634 / sqrt((double)head_dim));
   const int hpb = attn_heads_per_block(N, S, num_heads);
-  hipLaunchKernelGGL(g_opt.attn_pipe ? attn_fwd_p_k : attn_fwd_k, dim3((unsigned)(N * (num_heads / hpb) * (S / 128))), dim3(256), 2 * AT_TILE_BYTES,
+  // a ragged S runs the pipelined kernel whatever "attn_pipe" says: the compiler-scheduled one has no ragged form
+  const auto kernel = S % 128 ? attn_fwd_p_k<true> : g_opt.attn_pipe ? attn_fwd_p_k<false> : attn_fwd_k;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(N * (num_heads / hpb) * ((S + 127) / 128))), dim3(256), 2 * AT_TILE_BYTES,
                      (hipStream_t)stream, (const bf16raw*)qkv, (bf16raw*)out, lse, (int)S, (int)num_heads, hpb, c);
   PERO_CHECK_LAUNCH("pero_attention_fwd");
   return PERO_OK;

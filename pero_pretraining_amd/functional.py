@@ -4,9 +4,10 @@ Token layout: every activation is a row-major (N*S, d) matrix of token rows (lin
 what the reference reaches after its `n d s -> s n d` / `s n d -> n d s` transposes
 (models/transformers.py:82-89) - those are pure layout and vanish here.
 
-Attention: bf16 with head_dim 128 and S % 128 == 0 runs the fused flash-style kernels of csrc/attention_fwd.hip / attention_bwd.hip / attention_lh.hip on the
-packed qkv tensor (scores never stored; one f32 log-sum-exp per query saved for the backward); f32 parity mode and other
-shapes take the unfused form of torch SDPA - per (line, head) batched GEMMs + a row softmax kernel, scores in f32.
+Attention: bf16 with head_dim 128 runs the fused flash-style kernels of csrc/attention_fwd.hip / attention_bwd.hip / attention_lh.hip on the
+packed qkv tensor at every line length S (128-row tiles, the last one ragged when S % 128 != 0; scores never stored; one f32 log-sum-exp
+per query saved for the backward); f32 parity mode and other
+head sizes take the unfused form of torch SDPA - per (line, head) batched GEMMs + a row softmax kernel, scores in f32.
 Every product of the backward pass is pero_gemm with a different operand-layout flag: input gradients as K-contiguous
 products on transposed bf16 weight copies, weight gradients as split-K products into the parameters' f32 `.grad`
 buffers - partial tiles summed in slice order through a caller-owned workspace (ops.gemm_workspace; run-to-run
@@ -199,7 +200,7 @@ def attention_bwd(qkv, p, dout, n, s, h):
 # ---------------------------------------------------------------------------------------------
 # one post-norm encoder layer (torch.nn.TransformerEncoderLayer semantics, models/transformers.py:36-43)
 # ---------------------------------------------------------------------------------------------
-FUSED_ATTENTION = True  # bf16, head_dim 128, S % 128 == 0: flash-style HIP kernels; else batched GEMM + softmax
+FUSED_ATTENTION = True  # bf16, head_dim 128, any S (ops.attention_fused_ok): flash-style HIP kernels; else batched GEMM + softmax
 
 
 FUSE_LN_FWD_MAX_K = 4096  # Linear + residual + LayerNorm as ONE launch (csrc/gemm_n.hip gemm_bf16_n512, pero_gemm_resid_layernorm) for reductions up to this

@@ -246,7 +246,7 @@ def softmax_bwd(p, dp, scale):
 
 def attention_fused_ok(qkv, s, h):
     d = qkv.shape[1] // 3
-    return qkv.dtype == torch.bfloat16 and d // h == 128 and d % h == 0 and s % 128 == 0
+    return qkv.dtype == torch.bfloat16 and d // h == 128 and d % h == 0 and s >= 1
 
 
 def attention_fwd_fused(qkv, n, s, h):
@@ -266,7 +266,7 @@ def attention_bwd_fused(qkv, out, dout, lse, n, s, h, dbias=None, dvec=None):
         dvec = torch.empty((n * s, h), device=qkv.device, dtype=torch.float32)
     else:
         out = None
-    work = torch.empty(3 * n * h * (s // 128) * 128, device=qkv.device, dtype=torch.float32) if dbias is not None else None
+    work = torch.empty(3 * n * h * ((s + 127) // 128) * 128, device=qkv.device, dtype=torch.float32) if dbias is not None else None
     call("pero_attention_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dvec), ptr(dqkv), ptr(dbias), ptr(work), n, s, h, d // h,
          dt(qkv), stream())
     return dqkv
