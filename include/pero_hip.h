@@ -73,7 +73,9 @@ int pero_abi_version(void);
  * 0: f32 atomics even when a workspace is passed), "splitk_table" (1: unaligned slice counts hand their work items out XCD by XCD), "gemm_nw" (0; 1: stored
  * N = 512 products with a bias / residual epilogue run on the row-complete 128 x 512 tile that pero_gemm_resid_layernorm uses - same bits),
  * "gemm_e256_min" (192: stored products with at least that many 256x256 tiles take the eight-phase kernel; 0 = never), "gemm_e_splitk_min" (4),
- * "splitk_xcd" (1), "splitk_nearest" (0), "splitk_items" (512).  Process-wide; not meant to be changed while products are in flight. */
+ * "splitk_xcd" (1), "splitk_nearest" (0), "splitk_items" (512).  Process-wide; not meant to be changed while products are in flight.
+ * "attn_pipe", "attn_bwd_pair", "attn_lh" and "attn_order" have no effect at head_dim 64: those kernels (csrc/attention_hd64.hip) have one form -
+ * compiler-scheduled loops, the dQ kernel then the dK / dV kernel whether D is computed or handed in. */
 int pero_set_option(const char* name, int value);
 
 /* ---- front end ------------------------------------------------------------------------------
@@ -180,18 +182,25 @@ int pero_softmax_fwd(const float* s, void* p, int64_t rows, int64_t cols, float 
 int pero_softmax_bwd(const void* p, const float* dp, void* ds, int64_t rows, int64_t cols, float scale, int dtype,
                      void* stream);
 
-/* ---- fused attention (bf16, head_dim 128, any S >= 1) on the packed qkv (N*S, 3*nh*128) tensor -------------------
- * out (N*S, nh*128) = softmax(q k^T / sqrt(hd)) v per (line, head); lse (N*nh, S) f32 = base-2 log-sum-exp of the
+/* ---- fused attention (bf16, head_dim hd = 128 or 64, any S >= 1) on the packed qkv (N*S, 3*nh*hd) tensor ---------
+ * out (N*S, nh*hd) = softmax(q k^T / sqrt(hd)) v per (line, head); lse (N*nh, S) f32 = base-2 log-sum-exp of the
  * scaled scores (kept for the backward kernels).  Scores never touch memory.  A line is cut into ceil(S/128) blocks of 128
  * rows; when S % 128 != 0 the last block is ragged: no address outside the line's S rows is read or written, and out,
- * lse, dvec and dqkv keep their unpadded shapes.  Other head dims / f32: use the batched pero_gemm + pero_softmax_* path. */
+ * lse, dvec and dqkv keep their unpadded shapes.  head_dim 128: csrc/attention_fwd.hip, attention_bwd.hip, attention_lh.hip; head_dim 64:
+ * csrc/attention_hd64.hip, same layouts.  Every other head_dim, and f32, is refused on the host before any launch (PERO_E_INVALID; the
+ * message names the accepted widths): use the batched pero_gemm + pero_softmax_* path. */
 int pero_attention_fwd(const void* qkv, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads,
                        int64_t head_dim, int dtype, void* stream);
-/* dqkv (N*S, 3d) from dout (N*S, d).  dvec (N*S, nh) f32: D[row][head] = sum over the head's 128 columns of dout*out -
+/* dqkv (N*S, 3d) from dout (N*S, d).  dvec (N*S, nh) f32: D[row][head] = sum over the head's hd columns of dout*out -
  * computed and stored by the call when `out` is given, or supplied by the caller (out == null; e.g. written by the
- * PERO_GEMM_ROWDOT epilogue of the product that produced dout).  dbias (f32 [3d], may be null):
+ * PERO_GEMM_ROWDOT epilogue of the product that produced dout - 128-column blocks, so head_dim 128 only).  At head_dim 64 the same two
+ * kernels run in both forms and dqkv is bit-identical between them.  dbias (f32 [3d], may be null):
  * the column sums of dqkv - in_proj's bias gradient - are ACCUMULATED into it: per-workgroup partial rows from the kernels'
- * staged output tiles into work (f32, 3 * N * nh * ceil(S/128) * 128 elements; required with dbias), then one small reduction. */
+ * staged output tiles into work (f32, 3 * N * nh * ceil(S/128) * 128 elements - head_dim 64 uses the first half; required with dbias), then
+ * one small reduction. */
+/* head_dim 64: how many heads of a line one forward workgroup walks for this shape on this process's device (>= 1; a divisor of num_heads;
+ * results do not depend on it).  For tests and tools. */
+int pero_attention_hd64_heads_per_block(int64_t N, int64_t S, int64_t num_heads);
 int pero_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
                        float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim, int dtype,
                        void* stream);

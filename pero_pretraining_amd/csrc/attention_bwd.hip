@@ -657,9 +657,15 @@ extern "C" int pero_attention_bwd(const void* qkv, const void* out, const void* 
                                   float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim, int dtype,
                                   void* stream) {
   PERO_REQUIRE(qkv && dout && lse && dvec && dqkv, "pero_attention_bwd: null pointer");
-  PERO_REQUIRE(dtype == PERO_BF16 && head_dim == 128 && S > 0 && N > 0 && num_heads > 0, "pero_attention_bwd: fused kernel needs bf16, head_dim 128, S > 0");
+  PERO_REQUIRE(dtype == PERO_BF16 && (head_dim == 64 || head_dim == 128) && S > 0 && N > 0 && num_heads > 0,
+               "pero_attention_bwd: fused kernel needs bf16, head_dim 64 or 128, S > 0 (got hd=%lld S=%lld)", (long long)head_dim, (long long)S);
   PERO_REQUIRE(aligned16(qkv) && (!out || aligned16(out)) && aligned16(dout) && aligned16(dqkv), "pero_attention_bwd: 16-byte alignment");
   PERO_REQUIRE(!dbias || work, "pero_attention_bwd: dbias needs the partial-sum workspace");
+  if (head_dim == 64) {   // attention_hd64.hip: the same two kernels whether D is computed here or handed in
+    attn64_bwd_launch(qkv, out, dout, lse, dvec, dqkv, dbias, work, N, S, num_heads, (hipStream_t)stream);
+    PERO_CHECK_LAUNCH("pero_attention_bwd");
+    return PERO_OK;
+  }
   static const bool lds_attrs_once = [] {
     const struct { const void* kernel; int bytes; } attrs[] = {
         {(const void*)attn_bwd_dq_k<false>, 2 * AT_TILE_BYTES}, {(const void*)attn_bwd_dq_k<true>, 2 * AT_TILE_BYTES},

@@ -246,3 +246,9 @@ __device__ __forceinline__ void lh_wait_lgkm_plain() {
 // and launches it; the caller checks the launch
 __attribute__((visibility("hidden"))) void attn_bwd_lh_launch(const void* qkv, const void* dout, const float* lse, const float* dvec, void* dqkv,
                                                               float* work, int64_t N, int64_t num_heads, float c, float scale, hipStream_t st);
+
+// attention_hd64.hip: the head_dim-64 kernels (compiler-scheduled, any S >= 1, one head per workgroup).  pero_attention_fwd / pero_attention_bwd
+// validate the arguments, dispatch on head_dim and check the launch.
+__attribute__((visibility("hidden"))) void attn64_fwd_launch(const void* qkv, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads, hipStream_t st);
+__attribute__((visibility("hidden"))) void attn64_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
+                                                             float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, hipStream_t st);

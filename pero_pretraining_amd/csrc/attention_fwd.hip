@@ -376,9 +376,14 @@ static int attn_heads_per_block(long long N, long long S, long long nh) {
 extern "C" int pero_attention_fwd(const void* qkv, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads,
                                   int64_t head_dim, int dtype, void* stream) {
   PERO_REQUIRE(qkv && out && lse, "pero_attention_fwd: null pointer");
-  PERO_REQUIRE(dtype == PERO_BF16 && head_dim == 128 && S > 0 && N > 0 && num_heads > 0,
-               "pero_attention_fwd: fused kernel needs bf16, head_dim 128, S > 0 (got hd=%lld S=%lld)", (long long)head_dim, (long long)S);
+  PERO_REQUIRE(dtype == PERO_BF16 && (head_dim == 64 || head_dim == 128) && S > 0 && N > 0 && num_heads > 0,
+               "pero_attention_fwd: fused kernel needs bf16, head_dim 64 or 128, S > 0 (got hd=%lld S=%lld)", (long long)head_dim, (long long)S);
   PERO_REQUIRE(aligned16(qkv) && aligned16(out), "pero_attention_fwd: 16-byte alignment");
+  if (head_dim == 64) {   // attention_hd64.hip
+    attn64_fwd_launch(qkv, out, lse, N, S, num_heads, (hipStream_t)stream);
+    PERO_CHECK_LAUNCH("pero_attention_fwd");
+    return PERO_OK;
+  }
   PERO_LDS_ATTR(attn_fwd_k, 2 * AT_TILE_BYTES);
   PERO_LDS_ATTR(attn_fwd_p_k<false>, 2 * AT_TILE_BYTES);
   PERO_LDS_ATTR(attn_fwd_p_k<true>, 2 * AT_TILE_BYTES);

@@ -4,7 +4,8 @@ Token layout: every activation is a row-major (N*S, d) matrix of token rows (lin
 what the reference reaches after its `n d s -> s n d` / `s n d -> n d s` transposes
 (models/transformers.py:82-89) - those are pure layout and vanish here.
 
-Attention: bf16 with head_dim 128 runs the fused flash-style kernels of csrc/attention_fwd.hip / attention_bwd.hip / attention_lh.hip on the
+Attention: bf16 with head_dim 128 runs the fused flash-style kernels of csrc/attention_fwd.hip / attention_bwd.hip / attention_lh.hip, bf16 with
+head_dim 64 those of csrc/attention_hd64.hip, on the
 packed qkv tensor at every line length S (128-row tiles, the last one ragged when S % 128 != 0; scores never stored; one f32 log-sum-exp
 per query saved for the backward); f32 parity mode and other
 head sizes take the unfused form of torch SDPA - per (line, head) batched GEMMs + a row softmax kernel, scores in f32.
@@ -200,7 +201,8 @@ def attention_bwd(qkv, p, dout, n, s, h):
 # ---------------------------------------------------------------------------------------------
 # one post-norm encoder layer (torch.nn.TransformerEncoderLayer semantics, models/transformers.py:36-43)
 # ---------------------------------------------------------------------------------------------
-FUSED_ATTENTION = True  # bf16, head_dim 128, any S (ops.attention_fused_ok): flash-style HIP kernels; else batched GEMM + softmax
+FUSED_ATTENTION = True  # bf16, head_dim 128 (ops.attention_fused_ok) or 64 (ops.attention_fused_hd64_ok), any S: flash-style HIP kernels; else batched
+                        # GEMM + softmax.  False turns both head widths off
 
 
 FUSE_LN_FWD_MAX_K = 4096  # Linear + residual + LayerNorm as ONE launch (csrc/gemm_n.hip gemm_bf16_n512, pero_gemm_resid_layernorm) for reductions up to this
@@ -281,7 +283,7 @@ def layer_fwd(t, L, n, s, h, dtype, save, force_keep_y=False):
     """force_keep_y: the LayerNorms keep their input rows for the backward even where the mode would run it from the output (ln_keep_rows)."""
     at = L.self_attn
     qkv = linear_fwd(t, at.in_proj_weight, at.in_proj_bias, dtype)
-    if FUSED_ATTENTION and ops.attention_fused_ok(qkv, s, h):
+    if FUSED_ATTENTION and (ops.attention_fused_ok(qkv, s, h) or ops.attention_fused_hd64_ok(qkv, s, h)):
         a, p = ops.attention_fwd_fused(qkv, n, s, h)   # p = base-2 log-sum-exp rows (N*h, S)
     else:
         a, p = attention_fwd(qkv, n, s, h)             # p = probabilities (N*h, S, S)
@@ -318,9 +320,10 @@ def layer_bwd(dt2, L, saved, n, s, h, dtype, side=None, dt2_is_dy2=False, prev=N
         dy1 = ln_bwd(dt1, y1, t1, mean1, rstd1, L.norm1, ensure_grad(at.out_proj.bias))
     fused_attn = p.dim() == 2
     dvec = None
-    if fused_attn and FUSE_ROWDOT and a.shape[1] % 128 == 0:
-        # D = rowsum(dO * O) per head out of the epilogue of the product that writes dO (the dQ kernel then skips the O rows)
-        dvec = torch.empty((a.shape[0], a.shape[1] // 128), device=a.device, dtype=torch.float32)
+    if fused_attn and FUSE_ROWDOT and a.shape[1] // h == 128:
+        # D = rowsum(dO * O) per head out of the epilogue of the product that writes dO (the dQ kernel then skips the O rows).  The epilogue sums
+        # 128-column blocks: one head per block, so head_dim 128 only - at head_dim 64 the dQ kernel computes D from the O rows itself
+        dvec = torch.empty((a.shape[0], h), device=a.device, dtype=torch.float32)
     da = linear_bwd(dy1, a, at.out_proj.weight, at.out_proj.bias, dtype, bias_grad_done=True, side=side,
                     dx_rowdot=(a, dvec) if dvec is not None else None)
     return _layer_bwd_attn(da, dvec, dy1, L, saved, n, s, h, dtype, side, prev)
@@ -417,15 +420,14 @@ def layer_bwd_rows(dtc, index, nrows, L, saved, n, s, h, dtype, side=None, prev=
     del dpre1c
     # out-projection (+ D = rowsum(dO * O) per head for the attention backward)
     ac = rows_of(a)
-    nh = a.shape[1] // 128
-    dvecc = torch.empty((n_pad, nh), device=a.device, dtype=torch.float32) if FUSE_ROWDOT and a.shape[1] % 128 == 0 else None
+    dvecc = torch.empty((n_pad, h), device=a.device, dtype=torch.float32) if FUSE_ROWDOT and a.shape[1] // h == 128 else None   # (head_dim 128 only: layer_bwd)
     dac = linear_bwd(dy1c, ac, at.out_proj.weight, at.out_proj.bias, dtype, bias_grad_done=True, side=side, dx_rowdot=(ac, dvecc) if dvecc is not None else None)
     # back to all positions: exact zeros elsewhere
     da = ops.scatter_add_rows(dac, index, ops.zeros((M, a.shape[1]), a.device, dtype))
     dy1 = ops.scatter_add_rows(dy1c, index, ops.zeros((M, d), a.device, dtype))
     dvec = None
     if dvecc is not None:
-        dvec = ops.zeros((M, nh), a.device, torch.float32)
+        dvec = ops.zeros((M, h), a.device, torch.float32)
         dvec[index] = dvecc[:nrows]
     global row_sparse_steps
     row_sparse_steps += 1

@@ -249,6 +249,17 @@ def attention_fused_ok(qkv, s, h):
     return qkv.dtype == torch.bfloat16 and d // h == 128 and d % h == 0 and s >= 1
 
 
+def attention_fused_hd64_ok(qkv, s, h):
+    """The head_dim-64 kernels (csrc/attention_hd64.hip): bf16, d // h == 64, every s >= 1 (faster than the unfused path at every measured s: DESIGN 8.0000)."""
+    d = qkv.shape[1] // 3
+    return qkv.dtype == torch.bfloat16 and d % h == 0 and d // h == 64 and s >= 1
+
+
+def attention_hd64_heads_per_block(n, s, h):
+    """Heads of a line that one head_dim-64 forward workgroup walks at this shape on the current device (tests assert the choice)."""
+    return int(_lib.lib().pero_attention_hd64_heads_per_block(n, s, h))
+
+
 def attention_fwd_fused(qkv, n, s, h):
     d = qkv.shape[1] // 3
     out = torch.empty((n * s, d), device=qkv.device, dtype=qkv.dtype)
