@@ -358,6 +358,39 @@ int pero_line_mean(const void* x, float* out, int64_t lines, int64_t S, int64_t 
 /* dst[l*S + s][c] += scale * src[l][c] for every row s of line l (the backward of pero_line_mean: scale = 1 / S); dst dtype, src f32 */
 int pero_add_line_rows(void* dst, const float* src, int64_t lines, int64_t S, int64_t d, float scale, int dtype, void* stream);
 
+/* ---- NT-Xent on collated batches (NTXentLoss(apply_masks=True), csrc/ntxent_ragged.hip) ---------------------------
+ * A position of line l is SELECTED in view v when shift_mask_v[l][p] == 1 and image_mask_v[l][p] == 1 (2 in a shift mask, "shared
+ * but padding", is not).  The k-th selected position of view 1 pairs with the k-th of view 2; m_l is their common number.  The
+ * selected rows are compacted to the front of a block of Sp >= S rows per line (Sp % 128 == 0 keeps the per-line products on
+ * pero_gemm's bf16 tile kernel); every row, column and gradient entry behind m_l is an explicit zero.
+ *
+ * masks u8 (lines, S): slot_v[l][p] (int32) = the rank of position p among the selected positions of view v, -1 when not selected;
+ * count[l] (int32) = m_l, -1 when the two views select different numbers.  One wave per line; S <= 4096. */
+int pero_ntxent_slots(const void* image_mask1, const void* image_mask2, const void* shift_mask1, const void* shift_mask2, int* slot1,
+                      int* slot2, int* count, int64_t lines, int64_t S, void* stream);
+/* x (lines, S, d), slot (lines, S), count (count_lines; line l uses count[l % count_lines]: the two views stacked are lines =
+ * 2 count_lines).  With m = max(count, 0):  xn[l][k] = x[l][p] / max(|x[l][p]|_2, 1e-12), inv[l][k] = 1 / max(|x[l][p]|_2, 1e-12) for
+ * slot[l][p] = k < m;  xn[l][k] = 0, inv[l][k] = 0 for m <= k < Sp.  xn (lines, Sp, d) dtype, inv (lines, Sp) f32: every element is
+ * written. */
+int pero_ntxent_rows_fwd(const void* x, const int* slot, const int* count, void* xn, float* inv, int64_t lines, int64_t count_lines,
+                         int64_t S, int64_t Sp, int64_t d, int dtype, void* stream);
+/* dx[l][p] = (dxn[l][k] - xn[l][k] <xn[l][k], dxn[l][k]>) inv[l][k] g  for slot[l][p] = k in [0, count);  dx[l][p] = 0 elsewhere.
+ * xn, dxn (lines, Sp, d), dx (lines, S, d): every element is written; g (f32 scalar on the device) may be null = 1. */
+int pero_ntxent_rows_bwd(const void* xn, const void* dxn, const float* inv, const int* slot, const int* count, const float* g, void* dx,
+                         int64_t lines, int64_t count_lines, int64_t S, int64_t Sp, int64_t d, int dtype, void* stream);
+/* sim (lines, Sp, Sp) f32, m = count[l]; cross (lines*Sp, L) f32 or null (then dcross null, L and own0 unused).
+ *   lse_j = log( sum_{i<m} exp(sim[l][i][j]) + sum_{l' != own0 + l} exp(cross[l*Sp + j][l']) )                      (j < m)
+ *   line_loss[l] = mean_{j<m} (lse_j - sim[l][j][j]),  loss_out[0] = mean_l line_loss[l],  w = 1 / (m lines)
+ *   dsim[l][i][j] = (exp(sim[l][i][j] - lse_j) - [i == j]) w   (i, j < m),  0 for every other entry of the Sp x Sp block
+ *   dcross[l*Sp + j][l'] = exp(cross[l*Sp + j][l'] - lse_j) w  (j < m, l' != own0 + l),  0 for every other entry
+ * m <= 0: line_loss[l] = NaN (so loss_out is NaN) and all of the line's gradient entries are 0.  dsim, dcross (dtype) may be null. */
+int pero_ntxent_cols_ragged(const float* sim, const int* count, const float* cross, float* line_loss, float* loss_out, void* dsim,
+                            void* dcross, int64_t lines, int64_t Sp, int64_t L, int64_t own0, int dtype, void* stream);
+/* out[l][c] (f32) = (1 / count[l]) sum_{s < count[l]} x[l*Sp + s][c]  (0 for count[l] <= 0); d % 8 == 0 */
+int pero_line_mean_ragged(const void* x, const int* count, float* out, int64_t lines, int64_t Sp, int64_t d, int dtype, void* stream);
+/* dst[l*Sp + s][c] += src[l][c] / count[l] for s < count[l] (the backward of pero_line_mean_ragged); dst dtype, src f32 */
+int pero_add_line_rows_ragged(void* dst, const float* src, const int* count, int64_t lines, int64_t Sp, int64_t d, int dtype, void* stream);
+
 /* ---- evaluation -------------------------------------------------------------
  * replaces masked_pretraining/tester.py:72-113 (_update_errors / _topk / _calculate_errors: host numpy argmax and
  * argsort over the full logit tensor).  For every row with mask == 1: gt = #{j : logit[j] > logit[label]},

@@ -67,6 +67,12 @@ SIGNATURES = {
     "pero_ntxent_cols_cross": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
     "pero_line_mean": [_vp, _vp, _i64, _i64, _i64, _i32, _vp],
     "pero_add_line_rows": [_vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp],
+    "pero_ntxent_slots": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp],
+    "pero_ntxent_rows_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp],
+    "pero_ntxent_rows_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp],
+    "pero_ntxent_cols_ragged": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
+    "pero_line_mean_ragged": [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp],
+    "pero_add_line_rows_ragged": [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp],
     "pero_vq_ema_update": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f64, _f64, _vp],
     "pero_rowdot_blocks": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
     "pero_gemm_resid_layernorm": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp],

@@ -1,8 +1,7 @@
 // Reduction kernels of the joint-embedding losses (joint_embedding_pretraining/losses.py of the reference).
 // The dense contractions (VICReg covariance SYRK, its backward, the per-line NT-Xent similarity matrices and
 // their backward products) run on pero_gemm; everything here is HBM-bound row/column work in f32 statistics.
-#include "common.hpp"
-#include <initializer_list>
+#include "losses_common.hpp"
 
 // --------------------------------------------------------------------------------------------
 // squared-difference sum of gathered rows (VICReg invariance, losses.py:14-16):
@@ -356,21 +355,6 @@ __global__ __launch_bounds__(256) void ntxent_cols_cross_k(const float* sim, con
   if (lane == 0) red[wave] = acc;
   __syncthreads();
   if (tid == 0) line_loss[l] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)S;
-}
-
-#define DISPATCH_T(dtype, NAME, ...)                                                              \
-  do {                                                                                            \
-    if (dtype == PERO_F32) { NAME(float, __VA_ARGS__); }                                          \
-    else if (dtype == PERO_BF16) { NAME(bf16raw, __VA_ARGS__); }                                  \
-    else PERO_REQUIRE(false, "bad dtype");                                                        \
-  } while (0)
-
-// 16-byte row accesses are possible when every row starts 16-byte aligned
-static inline bool v8_ok(int64_t d, int dtype, std::initializer_list<const void*> ptrs) {
-  const int esz = dtype == PERO_F32 ? 4 : 2;
-  if (d % 8 || (d * esz) % 16) return false;
-  for (const void* q : ptrs) if (!aligned16(q)) return false;
-  return true;
 }
 
 extern "C" int pero_sqdiff_rows(const void* x, const int64_t* ix, const void* y, const int64_t* iy, float* partial, float* out,

@@ -170,46 +170,80 @@ class VICRegLoss(torch.nn.Module):
         return self.process_group if self.process_group is not None else dist.group.WORLD
 
 
+def ntxent_slots_host(image_masks1, image_masks2, shift_masks1, shift_masks2):
+    """The selection of NTXentLoss(apply_masks=True) on the host (numpy; the twin of pero_ntxent_slots): a position of a line is selected
+    in a view when its shift mask AND its image mask are 1 there.  Returns (slot1, slot2, count), int32: slot_v[l][p] = the rank of
+    position p among the selected positions of line l in view v, -1 when not selected; count[l] = their number, -1 when the two views
+    select different numbers."""
+    sel1 = (np.asarray(shift_masks1) == 1) & (np.asarray(image_masks1) == 1)
+    sel2 = (np.asarray(shift_masks2) == 1) & (np.asarray(image_masks2) == 1)
+    slot1 = np.where(sel1, np.cumsum(sel1, axis=1) - 1, -1).astype(np.int32)
+    slot2 = np.where(sel2, np.cumsum(sel2, axis=1) - 1, -1).astype(np.int32)
+    c1, c2 = sel1.sum(axis=1), sel2.sum(axis=1)
+    return slot1, slot2, np.where(c1 == c2, c1, -1).astype(np.int32)
+
+
+def ragged_block_rows(s, dtype):
+    """Rows of a line's compact block: S in f32 parity mode; in bf16 the next multiple of 128, so that the three per-line products meet
+    the tile kernel's shape conditions (M % 128 == 0, N % 128 == 0, K % 64 == 0) at every line width."""
+    return ((s + 127) // 128) * 128 if dtype == torch.bfloat16 else s
+
+
 class _NTXentFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, y, temperature, dtype):
+    def forward(ctx, x, y, temperature, dtype, rag=None):
+        # rag = (slot (2n, S) int32, count (n) int32) of ops.ntxent_slots: only the selected positions of every line take part, compacted
+        # to the front of a block of sp rows per line (NTXentLoss(apply_masks=True)).  None: every position, sp = s.
         stacked = y is None   # x = both views stacked along dim 0: one normalisation launch, ONE gradient tensor
-        if stacked:
-            n, s, D = x.shape[0] // 2, x.shape[1], x.shape[2]
+        n, s, D = (x.shape[0] // 2, x.shape[1], x.shape[2]) if stacked else x.shape
+        sp = s if rag is None else ragged_block_rows(s, dtype)
+        if stacked and rag is None:
             xyn, invxy = ops.rownorm_fwd(_rows(x, dtype))
+        elif stacked:
+            xyn, invxy = ops.ntxent_rows_fwd(_rows(x, dtype), rag[0], rag[1], sp)
         else:
-            n, s, D = x.shape
             # (the two views normalised into the halves of one buffer: the backward then is the stacked one's)
-            xyn = torch.empty((2 * n * s, D), device=x.device, dtype=dtype)
-            invxy = torch.empty(2 * n * s, device=x.device, dtype=torch.float32)
-            ops.rownorm_fwd(_rows(x, dtype), out=(xyn[:n * s], invxy[:n * s]))
-            ops.rownorm_fwd(_rows(y, dtype), out=(xyn[n * s:], invxy[n * s:]))
-        xn, yn = xyn[:n * s], xyn[n * s:]
-        sim = torch.empty((n, s, s), device=x.device, dtype=torch.float32)
-        ops.gemm_raw(xn, yn, sim, s, s, D, D, D, s, batch=n, sA=(s * D, 0), sB=(s * D, 0), sC=(s * s, 0),
+            xyn = torch.empty((2 * n * sp, D), device=x.device, dtype=dtype)
+            invxy = torch.empty(2 * n * sp, device=x.device, dtype=torch.float32)
+            if rag is None:
+                ops.rownorm_fwd(_rows(x, dtype), out=(xyn[:n * s], invxy[:n * s]))
+                ops.rownorm_fwd(_rows(y, dtype), out=(xyn[n * s:], invxy[n * s:]))
+            else:
+                ops.ntxent_rows_fwd(_rows(x, dtype), rag[0][:n], rag[1], sp, out=(xyn[:n * sp], invxy[:n * sp]))
+                ops.ntxent_rows_fwd(_rows(y, dtype), rag[0][n:], rag[1], sp, out=(xyn[n * sp:], invxy[n * sp:]))
+        xn, yn = xyn[:n * sp], xyn[n * sp:]
+        sim = torch.empty((n, sp, sp), device=x.device, dtype=torch.float32)
+        ops.gemm_raw(xn, yn, sim, sp, sp, D, D, D, sp, batch=n, sA=(sp * D, 0), sB=(sp * D, 0), sC=(sp * sp, 0),
                      alpha=1.0 / temperature)
-        loss, _, dsim = ops.ntxent_cols(sim, dtype)
-        ctx.save_for_backward(xyn, invxy, dsim)
-        ctx.meta = ((n, s, D), temperature, stacked)
+        if rag is None:
+            loss, _, dsim = ops.ntxent_cols(sim, dtype)
+            ctx.save_for_backward(xyn, invxy, dsim)
+        else:
+            loss, _, dsim, _ = ops.ntxent_cols_ragged(sim, rag[1], dtype)
+            ctx.save_for_backward(xyn, invxy, dsim, *rag)
+        ctx.meta = ((n, s, D), temperature, stacked, sp)
         return loss[0]
 
     @staticmethod
     def backward(ctx, g):
-        xyn, invxy, dsim = ctx.saved_tensors
-        (n, s, D), temperature, stacked = ctx.meta
-        xn, yn = xyn[:n * s], xyn[n * s:]
+        xyn, invxy, dsim, *rag = ctx.saved_tensors
+        (n, s, D), temperature, stacked, sp = ctx.meta
+        xn, yn = xyn[:n * sp], xyn[n * sp:]
         gdev = g.detach().reshape(1).to(torch.float32)
         dxyn = torch.empty_like(xyn)
-        dxn, dyn = dxyn[:n * s], dxyn[n * s:]
+        dxn, dyn = dxyn[:n * sp], dxyn[n * sp:]
         # d xn = dsim @ yn / T ; d yn = dsim^T @ xn / T   (per line)
-        ops.gemm_raw(dsim, yn, dxn, s, D, s, s, D, D, batch=n, sA=(s * s, 0), sB=(s * D, 0), sC=(s * D, 0),
+        ops.gemm_raw(dsim, yn, dxn, sp, D, sp, sp, D, D, batch=n, sA=(sp * sp, 0), sB=(sp * D, 0), sC=(sp * D, 0),
                      alpha=1.0 / temperature, flags=GEMM_TRANS_B)
-        ops.gemm_raw(dsim, xn, dyn, s, D, s, s, D, D, batch=n, sA=(s * s, 0), sB=(s * D, 0), sC=(s * D, 0),
+        ops.gemm_raw(dsim, xn, dyn, sp, D, sp, sp, D, D, batch=n, sA=(sp * sp, 0), sB=(sp * D, 0), sC=(sp * D, 0),
                      alpha=1.0 / temperature, flags=GEMM_TRANS_A | GEMM_TRANS_B)
-        dxy = ops.rownorm_bwd(xyn, dxyn, invxy, gdev)     # both views: one launch, one tensor
+        if rag:   # both views: one launch, one tensor; the unselected positions receive explicit zeros
+            dxy = ops.ntxent_rows_bwd(xyn, dxyn, invxy, rag[0], rag[1], sp, gdev)
+        else:
+            dxy = ops.rownorm_bwd(xyn, dxyn, invxy, gdev)
         if stacked:
-            return dxy.view(2 * n, s, D), None, None, None
-        return dxy[:n * s].view(n, s, D), dxy[n * s:].view(n, s, D), None, None
+            return dxy.view(2 * n, s, D), None, None, None, None
+        return dxy[:n * s].view(n, s, D), dxy[n * s:].view(n, s, D), None, None, None
 
 
 def _is_nccl(group):
@@ -228,12 +262,20 @@ class _NTXentCrossFn(torch.autograd.Function):
     private copy).  The upstream gradient is applied once, at the end (it is the same scalar on every rank of a data-parallel step)."""
 
     @staticmethod
-    def forward(ctx, x, y, temperature, dtype, group):
+    def forward(ctx, x, y, temperature, dtype, group, rag=None):
+        # rag: as in _NTXentFn - the selected positions only, compacted per line into blocks of sp rows; the pooled embedding of a line
+        # is then the mean over its selected view-1 rows
         n, s, D = x.shape
         T = float(temperature)
-        xn, invx = ops.rownorm_fwd(_rows(x, dtype))
-        yn, invy = ops.rownorm_fwd(_rows(y, dtype))
-        pm = ops.line_mean(xn, n, s)                                   # (N, D) f32: mean of the normalised view-1 rows of a line
+        sp = s if rag is None else ragged_block_rows(s, dtype)
+        if rag is None:
+            xn, invx = ops.rownorm_fwd(_rows(x, dtype))
+            yn, invy = ops.rownorm_fwd(_rows(y, dtype))
+            pm = ops.line_mean(xn, n, s)                               # (N, D) f32: mean of the normalised view-1 rows of a line
+        else:
+            xn, invx = ops.ntxent_rows_fwd(_rows(x, dtype), rag[0][:n], rag[1], sp)
+            yn, invy = ops.ntxent_rows_fwd(_rows(y, dtype), rag[0][n:], rag[1], sp)
+            pm = ops.line_mean_ragged(xn, rag[1], sp)
         p, invp = ops.rownorm_fwd(pm)                                  # one bounded negative per line
         world, rank = 1, 0
         gathered = p
@@ -250,23 +292,26 @@ class _NTXentCrossFn(torch.autograd.Function):
             glp = ops.cast_to_bf16(gathered, torch.empty((L, D), device=p.device, dtype=torch.bfloat16))
         else:
             glp = gathered
-        sim = torch.empty((n, s, s), device=x.device, dtype=torch.float32)
-        ops.gemm_raw(xn, yn, sim, s, s, D, D, D, s, batch=n, sA=(s * D, 0), sB=(s * D, 0), sC=(s * s, 0), alpha=1.0 / T)
+        sim = torch.empty((n, sp, sp), device=x.device, dtype=torch.float32)
+        ops.gemm_raw(xn, yn, sim, sp, sp, D, D, D, sp, batch=n, sA=(sp * D, 0), sB=(sp * D, 0), sC=(sp * sp, 0), alpha=1.0 / T)
         cross = ops.gemm(yn, glp, alpha=1.0 / T, out_dtype=torch.float32)          # (N*S, L): y_j . p_l' / T
-        loss, _, dsim, dcross = ops.ntxent_cols_cross(sim, cross, rank * n, dtype)
-        ctx.save_for_backward(xn, yn, invx, invy, dsim, dcross, p, invp, glp)
-        ctx.meta = (n, s, D, T, group, world, rank)
+        if rag is None:
+            loss, _, dsim, dcross = ops.ntxent_cols_cross(sim, cross, rank * n, dtype)
+        else:
+            loss, _, dsim, dcross = ops.ntxent_cols_ragged(sim, rag[1], dtype, cross=cross, own0=rank * n)
+        ctx.save_for_backward(xn, yn, invx, invy, dsim, dcross, p, invp, glp, *(rag or ()))
+        ctx.meta = (n, s, D, T, group, world, rank, sp)
         return loss[0]
 
     @staticmethod
     def backward(ctx, g):
-        xn, yn, invx, invy, dsim, dcross, p, invp, glp = ctx.saved_tensors
-        n, s, D, T, group, world, rank = ctx.meta
+        xn, yn, invx, invy, dsim, dcross, p, invp, glp, *rag = ctx.saved_tensors
+        n, s, D, T, group, world, rank, sp = ctx.meta
         gdev = g.detach().reshape(1).to(torch.float32)
         dxn = torch.empty_like(xn)
         dyn = torch.empty_like(yn)
-        ops.gemm_raw(dsim, yn, dxn, s, D, s, s, D, D, batch=n, sA=(s * s, 0), sB=(s * D, 0), sC=(s * D, 0), alpha=1.0 / T, flags=GEMM_TRANS_B)
-        ops.gemm_raw(dsim, xn, dyn, s, D, s, s, D, D, batch=n, sA=(s * s, 0), sB=(s * D, 0), sC=(s * D, 0), alpha=1.0 / T,
+        ops.gemm_raw(dsim, yn, dxn, sp, D, sp, sp, D, D, batch=n, sA=(sp * sp, 0), sB=(sp * D, 0), sC=(sp * D, 0), alpha=1.0 / T, flags=GEMM_TRANS_B)
+        ops.gemm_raw(dsim, xn, dyn, sp, D, sp, sp, D, D, batch=n, sA=(sp * sp, 0), sB=(sp * D, 0), sC=(sp * D, 0), alpha=1.0 / T,
                      flags=GEMM_TRANS_A | GEMM_TRANS_B)
         # through the negatives: d yn += dcross @ P / T ;  d P = dcross^T @ yn / T  (f32: it is summed over the ranks)
         dyn = ops.gemm(dcross, glp, trans_b=True, alpha=1.0 / T, residual=dyn)
@@ -281,10 +326,15 @@ class _NTXentCrossFn(torch.autograd.Function):
         else:
             dp = dgath
         dpm = ops.rownorm_bwd(p, dp, invp)                              # through p = normalize(pm)
-        ops.add_line_rows_(dxn, dpm, n, s, 1.0 / s)                     # through pm = mean over the line's rows of xn
-        dx = ops.rownorm_bwd(xn, dxn, invx, gdev)
-        dy = ops.rownorm_bwd(yn, dyn, invy, gdev)
-        return dx.view(n, s, D), dy.view(n, s, D), None, None, None
+        if rag:
+            ops.add_line_rows_ragged_(dxn, dpm, rag[1], sp)             # through pm = mean over the line's selected rows of xn
+            dx = ops.ntxent_rows_bwd(xn, dxn, invx, rag[0][:n], rag[1], sp, gdev)
+            dy = ops.ntxent_rows_bwd(yn, dyn, invy, rag[0][n:], rag[1], sp, gdev)
+        else:
+            ops.add_line_rows_(dxn, dpm, n, s, 1.0 / s)                 # through pm = mean over the line's rows of xn
+            dx = ops.rownorm_bwd(xn, dxn, invx, gdev)
+            dy = ops.rownorm_bwd(yn, dyn, invy, gdev)
+        return dx.view(n, s, D), dy.view(n, s, D), None, None, None, None
 
 
 class NTXentLoss(torch.nn.Module):
@@ -300,35 +350,70 @@ class NTXentLoss(torch.nn.Module):
         loss_line = mean_j [ log( sum_i exp(x_i . y_j / T) + sum_{lines l' != line, all ranks} exp(p_l' . y_j / T) ) - x_j . y_j / T ].
     Gradients flow back through the gathered rows to the rank that owns them (sum over ranks), so the data-parallel average of
     the parameter gradients is the gradient of the mean loss over the global batch.  The restatement on the concatenated batch is
-    oracle/pero_oracle.py::ntxent_cross_loss; everything runs on HIP kernels (_NTXentCrossFn)."""
+    oracle/pero_oracle.py::ntxent_cross_loss; everything runs on HIP kernels (_NTXentCrossFn).
 
-    def __init__(self, temperature=0.1, cross_rank_negatives=False, process_group=None):
+    apply_masks=True (no reference counterpart that runs: what the reference's code evidently intends) makes the
+    loss usable on collated batches, whose masks are never all ones.  Per line l, X_l are the normalised view-1 rows at the positions
+    with shift_mask1 == 1 and image_mask1 == 1, Y_l the same for view 2 (2 in a shift mask, "shared but padding", is excluded); the
+    k-th selected row of X_l pairs with the k-th of Y_l, m_l pairs in all:
+        sim = X_l Y_l^T / T,  loss_line = mean_j (logsumexp_i sim[i][j] - sim[j][j]) over the m_l pairs,  loss = mean over ALL lines.
+    Gradients of unselected positions are exactly zero.  A line whose two views select different numbers of positions, or none, has
+    no such loss: when the masks carry host copies (ops.host_mask: what BatchCreator and the batch operators produce) forward raises
+    ValueError naming the first such line, without a device sync; masks that exist on the device only cost no sync either, and such
+    a line then makes the loss NaN (its gradients are zero).  With cross_rank_negatives=True the pooled embedding of a line is
+    normalize(mean over its SELECTED view-1 rows), and every selected column is normalised over the line's selected rows plus the
+    pooled embeddings of all other lines of all ranks.  On all-ones masks the values are those of apply_masks=False.  Default False:
+    the reference's behaviour, IndexError included."""
+
+    def __init__(self, temperature=0.1, cross_rank_negatives=False, process_group=None, apply_masks=False):
         super().__init__()
         self.temperature = temperature
         self.cross_rank_negatives = cross_rank_negatives
         self.process_group = process_group
+        self.apply_masks = apply_masks
 
     def forward(self, x, y, image_masks1, image_masks2, shift_masks1, shift_masks2):
         if not x.is_cuda:
             raise RuntimeError("pero_pretraining_amd losses run on the GPU only (HIP kernels, no CPU fallback)")
-        for m in (shift_masks1, shift_masks2, image_masks1, image_masks2):
-            h = host_mask(m)   # (checked on the host copy when there is one: no device sync)
-            if bool((np.asarray(h) != 1).any()) if h is not None else bool((torch.as_tensor(m) != 1).any()):
-                raise IndexError("The shape of the mask at index 0 does not match the shape of the indexed tensor "
-                                 "(NT-Xent of the reference is only defined for all-ones masks)")
+        rag = None
+        if self.apply_masks:
+            rag = self._slots(x.device, image_masks1, image_masks2, shift_masks1, shift_masks2)
+        else:
+            for m in (shift_masks1, shift_masks2, image_masks1, image_masks2):
+                h = host_mask(m)   # (checked on the host copy when there is one: no device sync)
+                if bool((np.asarray(h) != 1).any()) if h is not None else bool((torch.as_tensor(m) != 1).any()):
+                    raise IndexError("The shape of the mask at index 0 does not match the shape of the indexed tensor "
+                                     "(NT-Xent of the reference is only defined for all-ones masks)")
         if not self.cross_rank_negatives:
-            return {"loss": _NTXentFn.apply(x, y, float(self.temperature), compute_dtype())}
+            return {"loss": _NTXentFn.apply(x, y, float(self.temperature), compute_dtype(), rag)}
         if y is None:
             n = x.shape[0] // 2
             x, y = x[:n], x[n:]
-        return {"loss": self._cross(x, y)}
+        return {"loss": self._cross(x, y, rag)}
+
+    @staticmethod
+    def _slots(device, image_masks1, image_masks2, shift_masks1, shift_masks2):
+        """(slot, count) of ops.ntxent_slots for apply_masks=True.  Lines without a loss are reported from the masks' host copies when
+        all four have one (no device sync); otherwise they surface as a NaN loss."""
+        masks = (image_masks1, image_masks2, shift_masks1, shift_masks2)
+        hosts = [host_mask(m) for m in masks]
+        if all(h is not None for h in hosts):
+            count = ntxent_slots_host(*hosts)[2]
+            bad = np.flatnonzero(count <= 0)
+            if bad.size:
+                l = int(bad[0])
+                c1 = int(((np.asarray(hosts[2][l]) == 1) & (np.asarray(hosts[0][l]) == 1)).sum())
+                c2 = int(((np.asarray(hosts[3][l]) == 1) & (np.asarray(hosts[1][l]) == 1)).sum())
+                raise ValueError(f"NTXentLoss(apply_masks=True): line {l} selects {c1} positions in view 1 and {c2} in view 2 "
+                                 "(shift mask == 1 and image mask == 1); every line needs the same non-zero number in both views")
+        return ops.ntxent_slots(*masks, device=device)
 
     def forward_stacked(self, xy, image_masks1, image_masks2, shift_masks1, shift_masks2):
         """forward(xy[:n], xy[n:], ...) for the two views stacked along dim 0: same values, ONE gradient tensor for xy (see VICRegLoss)."""
         return self.forward(xy, None, image_masks1, image_masks2, shift_masks1, shift_masks2)
 
-    def _cross(self, x, y):
+    def _cross(self, x, y, rag=None):
         group = None
         if dist.is_available() and dist.is_initialized():
             group = self.process_group if self.process_group is not None else dist.group.WORLD
-        return _NTXentCrossFn.apply(x, y, float(self.temperature), compute_dtype(), group)
+        return _NTXentCrossFn.apply(x, y, float(self.temperature), compute_dtype(), group, rag)

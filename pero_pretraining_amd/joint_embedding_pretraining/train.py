@@ -14,15 +14,16 @@ from .tester import Tester
 from .trainer import Trainer
 
 
-def init_model(device, backbone_definition, head_definition, loss_type="vicreg", path=None, global_statistics=False):
-    """train.py:54-72."""
+def init_model(device, backbone_definition, head_definition, loss_type="vicreg", path=None, global_statistics=False,
+               ntxent_apply_masks=False):
+    """train.py:54-72.  ntxent_apply_masks: NTXentLoss(apply_masks=True), the form of NT-Xent that takes collated batches (losses.py)."""
     backbone = init_backbone(backbone_definition)
     head = init_head(head_definition)
     if loss_type == "vicreg":
         # global_statistics: VICReg mean / variance / covariance over the lines of all data-parallel ranks (losses.py)
         loss = VICRegLoss(global_statistics=global_statistics)
     elif loss_type == "ntxent":
-        loss = NTXentLoss()
+        loss = NTXentLoss(apply_masks=ntxent_apply_masks)
     else:
         raise ValueError(f"Unknown loss type: {loss_type}")
     model = JointEmbeddingTransformerEncoder(backbone, head, loss)

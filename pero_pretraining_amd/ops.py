@@ -618,6 +618,86 @@ def add_line_rows_(dst2, src, lines, S, scale):
     return dst2
 
 
+# ---- NT-Xent on collated batches (csrc/ntxent_ragged.hip) ---------------------------------------------------------
+def _mask_u8(m, device):
+    t = torch.as_tensor(m)
+    if t.dtype != torch.uint8:
+        t = t.to(torch.uint8)    # the masks hold 0, 1 and 2
+    return t.to(device, non_blocking=True).contiguous()
+
+
+def ntxent_slots(image_mask1, image_mask2, shift_mask1, shift_mask2, device=None):
+    """Four (lines, S) integer masks -> (slot (2*lines, S) int32: view 1's lines, then view 2's; count (lines) int32) - see
+    pero_ntxent_slots.  Masks of another integer dtype, or on the host, are converted / uploaded first."""
+    if device is None:
+        device = next(m.device for m in (image_mask1, image_mask2, shift_mask1, shift_mask2) if isinstance(m, torch.Tensor) and m.is_cuda)
+    im1, im2, sm1, sm2 = (_mask_u8(m, device) for m in (image_mask1, image_mask2, shift_mask1, shift_mask2))
+    lines, S = im1.shape
+    assert im2.shape == sm1.shape == sm2.shape == (lines, S)
+    slot = torch.empty((2 * lines, S), device=device, dtype=torch.int32)
+    count = torch.empty(lines, device=device, dtype=torch.int32)
+    call("pero_ntxent_slots", ptr(im1), ptr(im2), ptr(sm1), ptr(sm2), ptr(slot[:lines]), ptr(slot[lines:]), ptr(count), lines, S, stream())
+    return slot, count
+
+
+def ntxent_rows_fwd(x, slot, count, Sp, out=None):
+    """x (lines*S, d), slot (lines, S), count (lines or lines / 2) -> compact normalised rows (lines*Sp, d) and inv (lines*Sp) f32."""
+    lines, S = slot.shape
+    d = x.shape[1]
+    assert x.shape[0] == lines * S and x.is_contiguous() and slot.is_contiguous() and slot.dtype == count.dtype == torch.int32
+    if out is not None:
+        xn, inv = out
+        assert xn.shape == (lines * Sp, d) and xn.is_contiguous() and inv.numel() == lines * Sp and inv.is_contiguous()
+    else:
+        xn = torch.empty((lines * Sp, d), device=x.device, dtype=x.dtype)
+        inv = torch.empty(lines * Sp, device=x.device, dtype=torch.float32)
+    call("pero_ntxent_rows_fwd", ptr(x), ptr(slot), ptr(count), ptr(xn), ptr(inv), lines, count.numel(), S, Sp, d, dt(x), stream())
+    return xn, inv
+
+
+def ntxent_rows_bwd(xn, dxn, inv, slot, count, Sp, g=None):
+    """Compact xn, dxn (lines*Sp, d) -> dx (lines*S, d): rownorm_bwd at the selected positions, zeros elsewhere."""
+    lines, S = slot.shape
+    d = xn.shape[1]
+    assert xn.shape == dxn.shape == (lines * Sp, d) and xn.is_contiguous() and dxn.is_contiguous() and slot.is_contiguous()
+    dx = torch.empty((lines * S, d), device=xn.device, dtype=xn.dtype)
+    call("pero_ntxent_rows_bwd", ptr(xn), ptr(dxn), ptr(inv), ptr(slot), ptr(count), ptr(g), ptr(dx), lines, count.numel(), S, Sp, d, dt(xn),
+         stream())
+    return dx
+
+
+def ntxent_cols_ragged(sim, count, grad_dtype=None, cross=None, own0=0):
+    """sim (lines, Sp, Sp) f32, count (lines) int32, cross (lines*Sp, L) f32 or None -> (loss [1], line_loss, dsim, dcross) - see
+    pero_ntxent_cols_ragged.  grad_dtype None: no gradients."""
+    lines, Sp, _ = sim.shape
+    assert sim.is_contiguous() and count.numel() == lines and count.dtype == torch.int32
+    L = 0
+    if cross is not None:
+        L = cross.shape[1]
+        assert cross.shape == (lines * Sp, L) and cross.is_contiguous() and cross.dtype == torch.float32
+    line_loss = torch.empty(lines, device=sim.device, dtype=torch.float32)
+    loss = torch.empty(1, device=sim.device, dtype=torch.float32)
+    dsim = torch.empty(sim.shape, device=sim.device, dtype=grad_dtype) if grad_dtype is not None else None
+    dcross = torch.empty(cross.shape, device=sim.device, dtype=grad_dtype) if grad_dtype is not None and cross is not None else None
+    call("pero_ntxent_cols_ragged", ptr(sim), ptr(count), ptr(cross), ptr(line_loss), ptr(loss), ptr(dsim), ptr(dcross), lines, Sp, L, int(own0),
+         dt(grad_dtype) if grad_dtype is not None else PERO_F32, stream())
+    return loss, line_loss, dsim, dcross
+
+
+def line_mean_ragged(x2, count, Sp):
+    """x2 (lines*Sp, d), count (lines) int32 -> f32 (lines, d): mean over the first count[l] rows of each line's block."""
+    lines = count.numel()
+    out = torch.empty((lines, x2.shape[1]), device=x2.device, dtype=torch.float32)
+    call("pero_line_mean_ragged", ptr(x2), ptr(count), ptr(out), lines, Sp, x2.shape[1], dt(x2), stream())
+    return out
+
+
+def add_line_rows_ragged_(dst2, src, count, Sp):
+    """dst2 (lines*Sp, d)[l*Sp + s] += src[l] / count[l] for s < count[l]; in place."""
+    call("pero_add_line_rows_ragged", ptr(dst2), ptr(src), ptr(count), count.numel(), Sp, dst2.shape[1], dt(dst2), stream())
+    return dst2
+
+
 MAX_TOPK = 8
 
 
