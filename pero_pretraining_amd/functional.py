@@ -16,20 +16,12 @@ reproducible), f32 atomics only for short reductions.
 """
 import math
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 
 from . import lowp, ops
-from ._lib import GEMM_ATOMIC, GEMM_TRANS_A, GEMM_TRANS_B
-
-LN_EPS = 1e-5
-
-
-def _ksplit(rows, out_elems):
-    """Split the token (reduction) dimension of a weight-gradient GEMM so that the grid fills 256 CUs."""
-    tiles = max(1, out_elems // (128 * 128))
-    want = max(1, 512 // tiles)
-    return int(max(1, min(want, rows // 512 if rows >= 512 else 1)))
+from ._lib import GEMM_TRANS_A, GEMM_TRANS_B
 
 
 def ensure_grad(p):
@@ -39,14 +31,8 @@ def ensure_grad(p):
     return p.grad
 
 
-FWD_TILE_FLAGS = 0
-FUSE_B1_COLSUM = True    # linear1's bias gradient from the epilogue of linear2's input-gradient product (else: a column-sum pass on the side stream)
-DX_ON_WT = True          # input gradients on transposed weight copies (lowp.weight_t)
-DX_TILE_FLAGS = 0
 RELU_GATE_BITS = True    # linear1's ReLU leaves a bit mask (free in its epilogue); linear2's input gradient reads a byte per 8 columns, all of a
                          # tile's bytes ahead of the staging barriers, instead of eight dependent 16-byte gate rows: step -0.7 %
-
-
 RELU_BITS_TILED = True   # the mask per 256-column block ([N/256][M][32 B]) when N % 256 == 0: a tile's mask is whole cache lines, and linear1's product may walk its
                          # tiles like the other K = 512 products (ops.gemm bits_tiled; csrc/gemm_e.hip pero_launch_gemm_e256)
 
@@ -62,11 +48,10 @@ def relu_bits_ok(m, n, k, dtype):
 
 def linear_fwd(x, w, b, dtype, residual=None, relu=False, out_dtype=None, relu_bits=None):
     return ops.gemm(x, lowp.weight(w, dtype), relu_bits=relu_bits, bias=None if b is None else b.detach(), residual=residual, relu=relu,
-                    out_dtype=out_dtype, extra_flags=FWD_TILE_FLAGS, bits_tiled=relu_bits is not None and bits_tiled(w.shape[0]))
+                    out_dtype=out_dtype, bits_tiled=relu_bits is not None and bits_tiled(w.shape[0]))
 
 
 FUSE_ROWDOT = True     # attention backward's D = rowsum(dO * O) from the epilogue of the out-projection's dX product
-FUSE_BIAS_GRAD = True  # bias gradients that are column sums of a dX product's output come out of that product's epilogue
 SIDE_STREAM_DW = False  # weight / bias gradients on a second HIP stream (they are off the backward critical path).  Off since round 3: every
                         # product is a whole-chip kernel now (persistent dX tiles, 256 split-K work items), two of them side by side only
                         # share the CUs - B = 1536 step 115.6 ms with, 114.6 ms without (same box, interleaved); rounds 1-2 gained 0.5-1 ms
@@ -151,11 +136,10 @@ def linear_bwd(dy, x, w, b, dtype, need_dx=True, gate=None, residual=None, bias_
         grads()
     if not need_dx:
         return None
-    if DX_ON_WT and dtype == torch.bfloat16:
+    if dtype == torch.bfloat16:
         # dX = dY (W^T)^T on a transposed bf16 weight copy: both operands K-contiguous, 256x256x64 tiles
-        return ops.gemm(dy, lowp.weight_t(w), residual=residual, gate=None if gate_bits is not None else gate,
-                        relu_bits=gate_bits, colsum_into=dx_colsum_into, rowdot=dx_rowdot, extra_flags=DX_TILE_FLAGS,
-                        bits_tiled=gate_bits is not None and bits_tiled(w.shape[1]))
+        return ops.gemm(dy, lowp.weight_t(w), residual=residual, gate=None if gate_bits is not None else gate, relu_bits=gate_bits,
+                        colsum_into=dx_colsum_into, rowdot=dx_rowdot, bits_tiled=gate_bits is not None and bits_tiled(w.shape[1]))
     if gate_bits is not None:
         raise RuntimeError("linear_bwd: a bit-mask gate needs the bf16 transposed-weight path")
     return ops.gemm(dy, lowp.weight(w, dtype).view(w.shape[0], -1), trans_b=True, residual=residual, gate=gate,
@@ -203,14 +187,10 @@ def attention_bwd(qkv, p, dout, n, s, h):
 # ---------------------------------------------------------------------------------------------
 FUSED_ATTENTION = True  # bf16, head_dim 128 (ops.attention_fused_ok) or 64 (ops.attention_fused_hd64_ok), any S: flash-style HIP kernels; else batched
                         # GEMM + softmax.  False turns both head widths off
-
-
 FUSE_LN_FWD_MAX_K = 4096  # Linear + residual + LayerNorm as ONE launch (csrc/gemm_n.hip gemm_bf16_n512, pero_gemm_resid_layernorm) for reductions up to this
                           # length: at K = 512 (out-projection) the fused launch takes 509 us against 352 + 195 for the pair (524 288 rows), at
                           # K = 2048 (linear2) 1 133 against 931 + 190 - the row-complete tile runs 5 % behind the 256 x 256 one there; in the
                           # 2048-line step: never 147.7 ms, out-projection only 147.0, both 146.8.  0: never
-
-
 LN_BWD_FROM_OUT = True    # bf16 mode: the encoder layers' LayerNorms keep their OUTPUT t (the next Linear's input, saved anyway) and rstd for the backward,
                           # not their input rows y ("memory-efficient" LayerNorm: xhat = (t - beta) / gamma, pero_layernorm_bwd_out).  The fused
                           # Linear + residual + LayerNorm launch then does not store y at all: 24 x 537 MB per 2048-line step less written and kept.
@@ -265,18 +245,51 @@ FUSE_LN_BWD = True    # bf16 mode with LN_BWD_FROM_OUT: the LayerNorm backward o
 def linear_bwd_ln(dy, x, w, b, dtype, residual, t_ln, rstd_ln, norm, dxsum, side=None, bias_grad_done=False):
     """linear_bwd(dy, x, w, b, residual=residual) followed by the LayerNorm backward (from its output t_ln and rstd_ln) of `norm`, whose output
     x is: returns dy_norm.  Fused into one launch where the shape allows; None if it does not (the caller runs the pair)."""
-    if not (FUSE_LN_BWD and DX_ON_WT and dtype == torch.bfloat16 and ops.gemm_resid_layernorm_bwd_ok(dy, lowp.weight_t(w), residual, t_ln)):
+    if not (FUSE_LN_BWD and dtype == torch.bfloat16 and ops.gemm_resid_layernorm_bwd_ok(dy, lowp.weight_t(w), residual, t_ln)):
         return None
     linear_bwd(dy, x, w, b, dtype, need_dx=False, side=side, bias_grad_done=bias_grad_done)   # weight (and bias) gradients
     return ops.gemm_resid_layernorm_bwd(dy, lowp.weight_t(w), residual, t_ln, rstd_ln, norm.weight.detach(), norm.bias.detach(),
                                         ensure_grad(norm.weight), ensure_grad(norm.bias), dxsum)
 
 
-def ln_bwd(dt, y, t, mean, rstd, norm, dxsum):
-    """LayerNorm backward of an encoder layer's norm: from the saved input rows y, or - when the forward did not keep them - from its output t."""
+class LayerSaved(NamedTuple):
+    """What one encoder layer keeps for its backward, in the order the forward produces it."""
+    t: torch.Tensor                      # the layer's input (N*S, d)
+    qkv: torch.Tensor
+    attn_stat: torch.Tensor              # fused attention: base-2 log-sum-exp rows (N*h, S); else the probabilities (N*h, S, S)
+    a: torch.Tensor                      # attention output
+    y1: Optional[torch.Tensor]           # norm1's input rows, None when the norms run their backward from the output
+    mean1: torch.Tensor
+    rstd1: torch.Tensor
+    t1: torch.Tensor                     # norm1's output
+    hdn: torch.Tensor                    # linear1's output behind the ReLU
+    y2: Optional[torch.Tensor]
+    mean2: torch.Tensor
+    rstd2: torch.Tensor
+    relu_bits: Optional[torch.Tensor]    # the ReLU's gate as a bit mask (relu_bits_ok) or None
+    t2: torch.Tensor                     # norm2's output = the layer's output
+
+    @property
+    def fused_attention(self):
+        """The fused attention kernels ran: attn_stat holds one log-sum-exp per query, not the probabilities."""
+        return self.attn_stat.dim() == 2
+
+    @property
+    def ln_from_out(self):
+        """norm1 AND norm2 run their backward from their outputs t1 / t2, no input rows were kept: one keep_y in layer_fwd governs y1 and y2, so one answer serves both."""
+        return self.y1 is None
+
+
+# patch rows a0, the intermediate norm's input y0 and statistics, a LayerSaved per layer (backbone_bwd drops each as soon as that layer's backward is enqueued), lines, S
+BackboneSaved = NamedTuple("BackboneSaved", [("a0", torch.Tensor), ("y0", torch.Tensor), ("mean0", torch.Tensor), ("rstd0", torch.Tensor), ("layers", list), ("n", int), ("s", int)])
+
+
+def ln_bwd(dt, get, k, t, rstd, norm, dxsum):
+    """LayerNorm backward of a layer's norm1 / norm2 (k = "1" / "2"): from the saved input rows y, or - when the forward did not keep them - from its output t."""
+    y = get("y" + k)
     if y is None:
         return ops.layernorm_bwd_out(dt, t, rstd, norm.weight.detach(), norm.bias.detach(), ensure_grad(norm.weight), ensure_grad(norm.bias), dxsum)
-    return ops.layernorm_bwd(dt, y, mean, rstd, norm.weight.detach(), ensure_grad(norm.weight), ensure_grad(norm.bias), dxsum)
+    return ops.layernorm_bwd(dt, y, get("mean" + k), rstd, norm.weight.detach(), ensure_grad(norm.weight), ensure_grad(norm.bias), dxsum)
 
 
 def layer_fwd(t, L, n, s, h, dtype, save, force_keep_y=False):
@@ -290,57 +303,73 @@ def layer_fwd(t, L, n, s, h, dtype, save, force_keep_y=False):
     keep_y = force_keep_y or not (save and ln_from_out(dtype))
     y1, t1, mean1, rstd1 = linear_resid_ln_fwd(a, at.out_proj.weight, at.out_proj.bias, t, L.norm1, dtype, keep_y=keep_y)
     bits = None
-    if save and DX_ON_WT and relu_bits_ok(t1.shape[0], L.linear1.weight.shape[0], t1.shape[1], dtype) and \
+    if save and relu_bits_ok(t1.shape[0], L.linear1.weight.shape[0], t1.shape[1], dtype) and \
             relu_bits_ok(t1.shape[0], L.linear1.weight.shape[0], L.linear2.weight.shape[0], dtype):
         bits = torch.empty((t1.shape[0], L.linear1.weight.shape[0] // 8), device=t1.device, dtype=torch.uint8)
     hdn = linear_fwd(t1, L.linear1.weight, L.linear1.bias, dtype, relu=True, relu_bits=bits)
     y2, t2, mean2, rstd2 = linear_resid_ln_fwd(hdn, L.linear2.weight, L.linear2.bias, t1, L.norm2, dtype, keep_y=keep_y)
-    saved = (t, qkv, p, a, y1, mean1, rstd1, t1, hdn, y2, mean2, rstd2, bits, t2) if save else None
-    return t2, saved
+    return t2, LayerSaved(t, qkv, p, a, y1, mean1, rstd1, t1, hdn, y2, mean2, rstd2, bits, t2) if save else None
+
+
+def _layer_bwd_rowwise(dt2, L, saved, get, h, dtype, side, held, dt2_is_dy2=False, gathered=False):
+    """The row-wise half of a layer's backward: norm2, linear2, linear1 (+ norm1), the out-projection (+ D for the attention backward).  get(field): a tensor
+    of `saved` - itself (layer_bwd), or its listed rows, gathered when asked for (layer_bwd_rows: `gathered`; no bit mask, the ReLU gate comes from the hidden rows).
+    dt2: gradient of the layer's output on those rows, or with dt2_is_dy2 already the one behind norm2.  Returns (da, dvec, dy1): gradient of the attention output, its
+    row dots with the output per head or None, gradient behind norm1.  `held` receives what stays allocated until the caller has enqueued the attention backward;
+    gathered hidden rows and their gradient go as soon as they are read, which bounds the peak."""
+    at = L.self_attn
+    t2, dt1, dy2 = None, None, dt2
+    if not dt2_is_dy2:   # norm2 (its dx column sums are linear2's bias gradient)
+        t2 = get("t2")
+        dy2 = ln_bwd(dt2, get, "2", t2, get("rstd2"), L.norm2, ensure_grad(L.linear2.bias))
+    # linear2; linear1's bias gradient = column sums of dpre1: accumulated by the epilogue of the product that writes dpre1
+    hdn = get("hdn")
+    fuse_b1 = dtype == torch.bfloat16 and L.linear1.bias is not None and L.linear1.bias.requires_grad
+    dpre1 = linear_bwd(dy2, hdn, L.linear2.weight, L.linear2.bias, dtype, gate=hdn, gate_bits=get("relu_bits"), bias_grad_done=True, side=side,
+                       dx_colsum_into=ensure_grad(L.linear1.bias) if fuse_b1 else None)
+    del hdn
+    # linear1 + norm1
+    t1, rstd1 = get("t1"), get("rstd1")
+    dy1 = None if not saved.ln_from_out else linear_bwd_ln(   # norm1's backward in the epilogue of linear1's input-gradient product
+        dpre1, t1, L.linear1.weight, L.linear1.bias, dtype, dy2, t1, rstd1, L.norm1, ensure_grad(at.out_proj.bias), side=side, bias_grad_done=fuse_b1)
+    if dy1 is None:
+        dt1 = linear_bwd(dpre1, t1, L.linear1.weight, L.linear1.bias, dtype, residual=dy2, side=side, bias_grad_done=fuse_b1)
+        dy1 = ln_bwd(dt1, get, "1", t1, rstd1, L.norm1, ensure_grad(at.out_proj.bias))
+    dpre1 = None if gathered else dpre1
+    # out-projection
+    a = get("a")
+    dvec = None
+    if saved.fused_attention and FUSE_ROWDOT and a.shape[1] // h == 128:
+        # D = rowsum(dO * O) per head out of the epilogue of the product that writes dO (the dQ kernel then skips the O rows).  The epilogue sums
+        # 128-column blocks: one head per block, so head_dim 128 only - at head_dim 64 the dQ kernel computes D from the O rows itself
+        dvec = torch.empty((a.shape[0], h), device=a.device, dtype=torch.float32)
+    da = linear_bwd(dy1, a, at.out_proj.weight, at.out_proj.bias, dtype, bias_grad_done=True, side=side,
+                    dx_rowdot=(a, dvec) if dvec is not None else None)
+    held += (t2, dy2, dpre1, t1, rstd1, dt1, a)
+    return da, dvec, dy1
 
 
 def layer_bwd(dt2, L, saved, n, s, h, dtype, side=None, dt2_is_dy2=False, prev=None):
     """dt2: gradient of the layer's output - or, with dt2_is_dy2, already the gradient behind norm2's backward (the layer above ran it in the
     epilogue of its last product).  prev = (rstd2, layer) of the layer BELOW: its norm2's backward is then fused into this layer's last product
     where the shape allows.  Returns (gradient for the layer below, whether that is already behind the lower layer's norm2 backward)."""
-    t, qkv, p, a, y1, mean1, rstd1, t1, hdn, y2, mean2, rstd2, bits, t2 = saved
-    at = L.self_attn
-    # LN2 (its dx column sums are linear2's bias gradient)
-    dy2 = dt2 if dt2_is_dy2 else ln_bwd(dt2, y2, t2, mean2, rstd2, L.norm2, ensure_grad(L.linear2.bias))
-    # linear1's bias gradient = column sums of dpre1: accumulated by the epilogue of the product that writes dpre1
-    fuse_b1 = FUSE_BIAS_GRAD and FUSE_B1_COLSUM and dtype == torch.bfloat16 and L.linear1.bias is not None and L.linear1.bias.requires_grad
-    dpre1 = linear_bwd(dy2, hdn, L.linear2.weight, L.linear2.bias, dtype, gate=hdn, gate_bits=bits, bias_grad_done=True, side=side,
-                       dx_colsum_into=ensure_grad(L.linear1.bias) if fuse_b1 else None)
-    dy1 = None
-    if y1 is None:   # norm1's backward in the epilogue of linear1's input-gradient product
-        dy1 = linear_bwd_ln(dpre1, t1, L.linear1.weight, L.linear1.bias, dtype, dy2, t1, rstd1, L.norm1, ensure_grad(at.out_proj.bias),
-                            side=side, bias_grad_done=fuse_b1)
-    if dy1 is None:
-        dt1 = linear_bwd(dpre1, t1, L.linear1.weight, L.linear1.bias, dtype, residual=dy2, side=side, bias_grad_done=fuse_b1)
-        dy1 = ln_bwd(dt1, y1, t1, mean1, rstd1, L.norm1, ensure_grad(at.out_proj.bias))
-    fused_attn = p.dim() == 2
-    dvec = None
-    if fused_attn and FUSE_ROWDOT and a.shape[1] // h == 128:
-        # D = rowsum(dO * O) per head out of the epilogue of the product that writes dO (the dQ kernel then skips the O rows).  The epilogue sums
-        # 128-column blocks: one head per block, so head_dim 128 only - at head_dim 64 the dQ kernel computes D from the O rows itself
-        dvec = torch.empty((a.shape[0], h), device=a.device, dtype=torch.float32)
-    da = linear_bwd(dy1, a, at.out_proj.weight, at.out_proj.bias, dtype, bias_grad_done=True, side=side,
-                    dx_rowdot=(a, dvec) if dvec is not None else None)
+    held = []
+    da, dvec, dy1 = _layer_bwd_rowwise(dt2, L, saved, saved.__getattribute__, h, dtype, side, held, dt2_is_dy2=dt2_is_dy2)
     return _layer_bwd_attn(da, dvec, dy1, L, saved, n, s, h, dtype, side, prev)
 
 
 def _layer_bwd_attn(da, dvec, dy1, L, saved, n, s, h, dtype, side, prev):
     """The rest of a layer's backward behind the out-projection: attention and in_proj (da: gradient of the attention output, dvec: its row dots with
     the output per head or None, dy1: the gradient that joins as the residual)."""
-    t, qkv, p, a = saved[0], saved[1], saved[2], saved[3]
+    t, qkv = saved.t, saved.qkv
     at = L.self_attn
     fuse_bq = False
-    if p.dim() == 2:
+    if saved.fused_attention:
         # in_proj's bias gradient = column sums of dqkv: out of the attention kernels' staged output tiles
-        fuse_bq = FUSE_BIAS_GRAD and at.in_proj_bias is not None and at.in_proj_bias.requires_grad
-        dqkv = ops.attention_bwd_fused(qkv, a, da, p, n, s, h, dbias=ensure_grad(at.in_proj_bias) if fuse_bq else None, dvec=dvec)
+        fuse_bq = at.in_proj_bias is not None and at.in_proj_bias.requires_grad
+        dqkv = ops.attention_bwd_fused(qkv, saved.a, da, saved.attn_stat, n, s, h, dbias=ensure_grad(at.in_proj_bias) if fuse_bq else None, dvec=dvec)
     else:
-        dqkv = attention_bwd(qkv, p, da, n, s, h)
+        dqkv = attention_bwd(qkv, saved.attn_stat, da, n, s, h)
     if prev is not None:   # the lower layer's norm2 (its output is this layer's input t) in the epilogue of in_proj's input-gradient product
         rstd2_prev, Lp = prev
         dy2_prev = linear_bwd_ln(dqkv, t, at.in_proj_weight, at.in_proj_bias, dtype, dy1, t, rstd2_prev, Lp.norm2, ensure_grad(Lp.linear2.bias),
@@ -385,49 +414,28 @@ def take_row_grad_hint(dense):
 def layer_bwd_rows(dtc, index, nrows, L, saved, n, s, h, dtype, side=None, prev=None):
     """layer_bwd for a gradient of the layer's output that is nonzero on the rows `index` only: dtc = those rows (then zero rows up to a multiple of 256).
     Returns what layer_bwd returns, or None when this layer's saved state does not allow it (the caller then runs layer_bwd on the dense gradient)."""
-    t, qkv, p, a, y1, mean1, rstd1, t1, hdn, y2, mean2, rstd2, bits, t2 = saved
-    if dtype != torch.bfloat16 or y1 is not None or y2 is not None or p.dim() != 2 or dtc.shape[0] % 256 or not DX_ON_WT:
+    if dtype != torch.bfloat16 or not saved.ln_from_out or not saved.fused_attention or dtc.shape[0] % 256:
         return None
-    at = L.self_attn
-    n_pad, M, d = dtc.shape[0], t.shape[0], t.shape[1]
+    n_pad, (M, d), dev = dtc.shape[0], saved.t.shape, saved.t.device
 
-    def rows_of(x):
-        return ops.gather_rows(x, index, n_rows_out=n_pad)
-
-    def vec_of(v):   # a per-row f32 statistic of the listed rows (pad rows: 1)
-        out = torch.ones(n_pad, device=v.device, dtype=v.dtype)
-        out[:nrows] = v[index]
+    def get(field):   # the listed rows of a saved tensor (a per-row f32 statistic: 1 on the pad rows), gathered now; no bit mask: it is laid out for whole tiles
+        x = getattr(saved, field)
+        if x is None or field == "relu_bits":
+            return None
+        if x.dim() == 2:
+            return ops.gather_rows(x, index, n_rows_out=n_pad)
+        out = torch.ones(n_pad, device=x.device, dtype=x.dtype)
+        out[:nrows] = x[index]
         return out
 
-    # norm2 (its dx column sums are linear2's bias gradient)
-    t2c = rows_of(t2)
-    dy2c = ops.layernorm_bwd_out(dtc, t2c, vec_of(rstd2), L.norm2.weight.detach(), L.norm2.bias.detach(), ensure_grad(L.norm2.weight), ensure_grad(L.norm2.bias),
-                                 ensure_grad(L.linear2.bias))
-    # linear2: the ReLU gate from the hidden rows themselves (their bit mask is laid out for whole tiles)
-    hdnc = rows_of(hdn)
-    fuse_b1 = FUSE_BIAS_GRAD and FUSE_B1_COLSUM and L.linear1.bias is not None and L.linear1.bias.requires_grad
-    dpre1c = linear_bwd(dy2c, hdnc, L.linear2.weight, L.linear2.bias, dtype, gate=hdnc, bias_grad_done=True, side=side,
-                        dx_colsum_into=ensure_grad(L.linear1.bias) if fuse_b1 else None)
-    del hdnc
-    # linear1 + norm1
-    t1c, r1c = rows_of(t1), vec_of(rstd1)
-    dy1c = linear_bwd_ln(dpre1c, t1c, L.linear1.weight, L.linear1.bias, dtype, dy2c, t1c, r1c, L.norm1, ensure_grad(at.out_proj.bias), side=side,
-                         bias_grad_done=fuse_b1)
-    if dy1c is None:
-        dt1c = linear_bwd(dpre1c, t1c, L.linear1.weight, L.linear1.bias, dtype, residual=dy2c, side=side, bias_grad_done=fuse_b1)
-        dy1c = ops.layernorm_bwd_out(dt1c, t1c, r1c, L.norm1.weight.detach(), L.norm1.bias.detach(), ensure_grad(L.norm1.weight), ensure_grad(L.norm1.bias),
-                                     ensure_grad(at.out_proj.bias))
-    del dpre1c
-    # out-projection (+ D = rowsum(dO * O) per head for the attention backward)
-    ac = rows_of(a)
-    dvecc = torch.empty((n_pad, h), device=a.device, dtype=torch.float32) if FUSE_ROWDOT and a.shape[1] // h == 128 else None   # (head_dim 128 only: layer_bwd)
-    dac = linear_bwd(dy1c, ac, at.out_proj.weight, at.out_proj.bias, dtype, bias_grad_done=True, side=side, dx_rowdot=(ac, dvecc) if dvecc is not None else None)
+    held = []
+    dac, dvecc, dy1c = _layer_bwd_rowwise(dtc, L, saved, get, h, dtype, side, held, gathered=True)
     # back to all positions: exact zeros elsewhere
-    da = ops.scatter_add_rows(dac, index, ops.zeros((M, a.shape[1]), a.device, dtype))
-    dy1 = ops.scatter_add_rows(dy1c, index, ops.zeros((M, d), a.device, dtype))
+    da = ops.scatter_add_rows(dac, index, ops.zeros((M, saved.a.shape[1]), dev, dtype))
+    dy1 = ops.scatter_add_rows(dy1c, index, ops.zeros((M, d), dev, dtype))
     dvec = None
     if dvecc is not None:
-        dvec = ops.zeros((M, h), a.device, torch.float32)
+        dvec = ops.zeros((M, h), dev, torch.float32)
         dvec[index] = dvecc[:nrows]
     global row_sparse_steps
     row_sparse_steps += 1
@@ -466,8 +474,7 @@ def backbone_fwd(mod, x, mask, offsets, dtype, save):
             xc = xc.float().contiguous()
         a0 = ops.patches_from_f32(xc, mask, tile, P, dtype, pitch)
     s = w // P
-    y0 = ops.gemm(a0[:, :kp], lowp.weight(mod.conv_layer.weight, dtype).view(d, -1), bias=mod.conv_layer.bias.detach(),
-                  extra_flags=FWD_TILE_FLAGS)
+    y0 = ops.gemm(a0[:, :kp], lowp.weight(mod.conv_layer.weight, dtype).view(d, -1), bias=mod.conv_layer.bias.detach())
     pe = mod.position_model.pe_table(x.device)
     t, mean0, rstd0 = ops.layernorm_fwd(y0, mod.intermediate_norm.weight.detach(), mod.intermediate_norm.bias.detach(),
                                         mod.intermediate_norm.eps, pe=pe, offsets=offsets, S=s)
@@ -475,32 +482,28 @@ def backbone_fwd(mod, x, mask, offsets, dtype, save):
     for i, L in enumerate(mod.encoder_layers.layers):
         t, sv = layer_fwd(t, L, n, s, mod.num_heads, dtype, save, force_keep_y=keep is not None and keep[i])
         layers.append(sv)
-    saved = (a0, y0, mean0, rstd0, layers, n, s) if save else None
-    return t, saved
+    return t, BackboneSaved(a0, y0, mean0, rstd0, layers, n, s) if save else None
 
 
 def backbone_bwd(mod, saved, dt, dtype, on_layer_done=None, rows=None):
     """rows = (index, compact, nrows): dt is zero outside the rows `index`, whose values are compact[:nrows] (take_row_grad_hint)."""
-    a0, y0, mean0, rstd0, layers, n, s = saved
+    a0, layers, n, s = saved.a0, saved.layers, saved.n, saved.s
     nl = len(layers)
     side = SideStream(dt.device)
     is_dy2 = False
     for i in range(nl - 1, -1, -1):
-        prev = None
-        if i > 0 and layers[i - 1][9] is None:   # the lower layer kept no pre-norm rows: its norm2 backward runs from its output (= this layer's input)
-            prev = (layers[i - 1][11], mod.encoder_layers.layers[i - 1])
+        # the lower layer kept no pre-norm rows: its norm2 backward runs from its output (= this layer's input)
+        prev = (layers[i - 1].rstd2, mod.encoder_layers.layers[i - 1]) if i > 0 and layers[i - 1].ln_from_out else None
         res = None
         if i == nl - 1 and rows is not None:
             res = layer_bwd_rows(rows[1], rows[0], rows[2], mod.encoder_layers.layers[i], layers[i], n, s, mod.num_heads, dtype, side, prev=prev)
-        if res is None:
-            res = layer_bwd(dt, mod.encoder_layers.layers[i], layers[i], n, s, mod.num_heads, dtype, side, dt2_is_dy2=is_dy2, prev=prev)
-        dt, is_dy2 = res
+        dt, is_dy2 = res or layer_bwd(dt, mod.encoder_layers.layers[i], layers[i], n, s, mod.num_heads, dtype, side, dt2_is_dy2=is_dy2, prev=prev)
         layers[i] = None
         if on_layer_done is not None:
             with side.comm_context():  # sees the layer's gradient kernels on the main and the side streams
                 on_layer_done(i)
     nrm = mod.intermediate_norm
-    dy0 = ops.layernorm_bwd(dt, y0, mean0, rstd0, nrm.weight.detach(), ensure_grad(nrm.weight), ensure_grad(nrm.bias),
+    dy0 = ops.layernorm_bwd(dt, saved.y0, saved.mean0, saved.rstd0, nrm.weight.detach(), ensure_grad(nrm.weight), ensure_grad(nrm.bias),
                             ensure_grad(mod.conv_layer.bias))
     cw = mod.conv_layer.weight
     kp = cw[0].numel()

@@ -37,6 +37,14 @@ def _req_cuda(*ts):
 # optional launch timeline for bench.py's roofline leg: list of (start_event, end_event, flops, kernel tag)
 gemm_timeline = None
 
+
+def _timeline(e0=None, flops=None, tag=None):
+    """Called while the timeline is on: before a launch -> its recorded start event; behind it, with that event -> records the end and appends the entry."""
+    e = torch.cuda.Event(enable_timing=True)
+    e.record()
+    return e if e0 is None else gemm_timeline.append((e0, e, flops, tag))
+
+
 # Split-K workspaces (partial tiles of the weight-gradient products, pero_gemm's `workspace`): the C ABI never allocates, so the
 # caller - this module - keeps one buffer per (device, stream) from PyTorch's caching allocator, grown on demand.  Products on one
 # stream run one after the other and may share it; the weight-gradient side stream and the autograd threads' streams get their own.
@@ -73,17 +81,14 @@ def gemm_raw(A, B, C, M, N, K, lda, ldb, ldc, *, bias=None, residual=None, gate=
     if flags & GEMM_ATOMIC:
         need = _lib.lib().pero_gemm_workspace_bytes(M, N, K, batch, int(flags), int(k_split), idt, odt)
         ws = gemm_workspace(need, A.device if isinstance(A, torch.Tensor) else torch.device("cuda", torch.cuda.current_device()))
-    if gemm_timeline is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = None if gemm_timeline is None else _timeline()
     call("pero_gemm", ptr(A), ptr(B), ptr(C), ptr(bias), ptr(residual), ptr(gate), M, N, K, lda, ldb, ldc, ldr, ldg,
          batch, batch_inner, sA[0], sA[1], sB[0], sB[1], sC[0], sC[1], float(alpha), int(flags), int(k_split),
          idt, odt, ptr(ws), ws.numel() if ws is not None else 0, stream())
-    if gemm_timeline is not None:
-        e1.record()
+    if e0 is not None:
         fast = idt == PERO_BF16 and M % 128 == 0 and N % 128 == 0 and K % 64 == 0 and not (flags & GEMM_FORCE_GENERIC)
         lay = ("T" if flags & GEMM_TRANS_A else "N") + ("T" if flags & GEMM_TRANS_B else "N")
-        gemm_timeline.append((e0, e1, 2.0 * M * N * K * batch, ("gemm_bf16_tile" if fast else "gemm_generic") + ":" + lay))
+        _timeline(e0, 2.0 * M * N * K * batch, ("gemm_bf16_tile" if fast else "gemm_generic") + ":" + lay)
 
 
 def gemm(a, b, out=None, *, bias=None, residual=None, gate=None, trans_a=False, trans_b=False, relu=False,
@@ -152,23 +157,17 @@ def gemm_resid_layernorm(a, w, bias, residual, gamma, beta, eps, store_y=True):
     t = torch.empty((M, 512), device=a.device, dtype=torch.bfloat16)
     mean = torch.empty(M, device=a.device, dtype=torch.float32)
     rstd = torch.empty(M, device=a.device, dtype=torch.float32)
-    if gemm_timeline is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = None if gemm_timeline is None else _timeline()
     call("pero_gemm_resid_layernorm", ptr(a), ptr(w), ptr(bias), ptr(residual), ptr(gamma), ptr(beta), ptr(y), ptr(t), ptr(mean), ptr(rstd),
          M, 512, K, a.stride(0), w.stride(0), y.stride(0) if y is not None else 0, residual.stride(0), t.stride(0), float(eps), stream())
-    if gemm_timeline is not None:   # counted with the tile GEMMs of bench.py's roofline: the product's flops over the WHOLE launch (LayerNorm included)
-        e1.record()
-        gemm_timeline.append((e0, e1, 2.0 * M * 512 * K, "gemm_bf16_tile_ln_fwd:NN"))
+    if e0 is not None:   # counted with the tile GEMMs of bench.py's roofline: the product's flops over the WHOLE launch (LayerNorm included)
+        _timeline(e0, 2.0 * M * 512 * K, "gemm_bf16_tile_ln_fwd:NN")
     return y, t, mean, rstd
 
 
 def gemm_resid_layernorm_bwd_ok(a, w_t, residual, t):
     """Shapes the fused input-gradient + LayerNorm-backward launch takes (csrc/gemm_n.hip gemm_bf16_n512, EP_RESID_LNB)."""
-    return (a.dtype == torch.bfloat16 and a.dim() == 2 and w_t.dim() == 2 and w_t.shape[0] == 512 and a.shape[0] % 128 == 0 and a.shape[1] % 64 == 0 and
-            a.shape[1] >= 192 and a.shape[1] == w_t.shape[1] and residual is not None and residual.shape == (a.shape[0], 512) and
-            t is not None and t.shape == (a.shape[0], 512) and a.stride(1) == 1 and w_t.stride(1) == 1 and residual.stride(1) == 1 and t.stride(1) == 1 and
-            a.stride(0) % 8 == 0 and w_t.stride(0) % 8 == 0 and residual.stride(0) % 8 == 0 and t.stride(0) % 8 == 0)
+    return gemm_resid_layernorm_ok(a, w_t, residual) and t is not None and t.shape == (a.shape[0], 512) and t.stride(1) == 1 and t.stride(0) % 8 == 0
 
 
 def gemm_resid_layernorm_bwd(a, w_t, residual, t, rstd, gamma, beta, dgamma, dbeta, dxsum=None):
@@ -178,14 +177,11 @@ def gemm_resid_layernorm_bwd(a, w_t, residual, t, rstd, gamma, beta, dgamma, dbe
     M, K = a.shape
     dx = torch.empty((M, 512), device=a.device, dtype=torch.bfloat16)
     work = torch.empty(3 * _lib.LN_BWD_BLOCKS * 512, device=a.device, dtype=torch.float32)
-    if gemm_timeline is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = None if gemm_timeline is None else _timeline()
     call("pero_gemm_resid_layernorm_bwd", ptr(a), ptr(w_t), ptr(residual), ptr(t), ptr(rstd), ptr(gamma), ptr(beta), ptr(dx), ptr(dgamma), ptr(dbeta),
          ptr(dxsum), ptr(work), M, 512, K, a.stride(0), w_t.stride(0), residual.stride(0), t.stride(0), dx.stride(0), stream())
-    if gemm_timeline is not None:   # the product's flops over the WHOLE launch (LayerNorm backward and the reduce included)
-        e1.record()
-        gemm_timeline.append((e0, e1, 2.0 * M * 512 * K, "gemm_bf16_tile_ln_bwd:NN"))
+    if e0 is not None:   # the product's flops over the WHOLE launch (LayerNorm backward and the reduce included)
+        _timeline(e0, 2.0 * M * 512 * K, "gemm_bf16_tile_ln_bwd:NN")
     return dx
 
 
