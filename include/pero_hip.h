@@ -257,6 +257,31 @@ int pero_scale(void* x, int64_t n, float scale, int dtype, void* stream);
  * writes the bf16 copy of the updated parameters (p_bf16 may be null). */
 int pero_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, double lr,
                    double beta1, double beta2, double eps, int64_t step, double grad_scale, void* stream);
+/* The same launch with torch.optim.Adam's remaining arguments and a fused global-norm clip.  Per element, in torch's order
+ * (bc1 = 1 - beta1^step, bc2 = 1 - beta2^step; lr / bc1, 1 / sqrt(bc2) and 1 - lr * weight_decay are formed in f64 on the host):
+ *   g = grad * grad_scale
+ *   grad_norm != null:  g *= min(1, max_norm / (*grad_norm + 1e-6))           (torch.nn.utils.clip_grad_norm_)
+ *   maximize:           g = -g
+ *   weight_decay != 0:  decoupled ? p *= 1 - lr * weight_decay : g += weight_decay * p        (AdamW : Adam)
+ *   m = beta1 * m + (1 - beta1) * g ;  v = beta2 * v + (1 - beta2) * g * g
+ *   vmax != null (amsgrad):  vmax = max(vmax, v) ; denom = sqrt(vmax) / sqrt(bc2) + eps ;  else denom = sqrt(v) / sqrt(bc2) + eps
+ *   p -= (lr / bc1) * m / denom ;  p_bf16 = round-to-nearest-even(p)
+ * vmax: f32, the length and alignment of v.  grad_norm: DEVICE pointer to one f32, the global gradient norm already multiplied by
+ * grad_scale (pero_grad_norm_finish writes it); every thread reads it, no host copy of it exists.  decoupled, maximize: 0 or 1.
+ * With weight_decay = 0, maximize = 0, vmax = null and grad_norm = null the results are bit-identical to pero_adam_step. */
+int pero_adam_step_ex(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, double lr,
+                      double beta1, double beta2, double eps, int64_t step, double grad_scale, double weight_decay,
+                      int decoupled, float* vmax, int maximize, const float* grad_norm, double max_norm, void* stream);
+/* Global L2 norm of one or several flat f32 buffers in two kinds of launch, without float atomics: every addition has a fixed place,
+ * so the same input gives the same bits from run to run and from device to device.
+ * pero_sumsq_partials: partials[b] = sum of x[i]^2 over the elements of workgroup b, b < pero_sumsq_num_partials(n) (a function of n
+ * alone: min(ceil(ceil(n / 4) / 1024), 2048); returns that count, not a status).  x 16-byte aligned; the caller lays the partials of
+ * several buffers one behind the other in one workspace.
+ * pero_grad_norm_finish: norm[0] = (f32)(scale * sqrt(sum_i partials[i])), the sum in f64 in index order (256 contiguous runs, then the
+ * run sums), one workgroup. */
+int pero_sumsq_num_partials(int64_t n);
+int pero_sumsq_partials(const float* x, int64_t n, float* partials, void* stream);
+int pero_grad_norm_finish(const float* partials, int64_t count, double scale, float* norm, void* stream);
 
 /* ---- quantizers (models/autoencoders.py:212-217 ; scripts/produce_kmeans_labels.py:72-76) ---------------
  * indices[m] = argmin_k ( sum(x_m^2) + sum(e_k^2) - 2 x_m . e_k )  in exact f32, first minimum wins.

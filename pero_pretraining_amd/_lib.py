@@ -50,6 +50,10 @@ SIGNATURES = {
     "pero_cast_bf16_f32": [_vp, _vp, _i64, _vp],
     "pero_scale": [_vp, _i64, _f32, _i32, _vp],
     "pero_adam_step": [_vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _vp],
+    "pero_adam_step_ex": [_vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _f64, _i32, _vp, _i32, _vp, _f64, _vp],
+    "pero_sumsq_num_partials": [_i64],   # returns the count, not a status
+    "pero_sumsq_partials": [_vp, _i64, _vp, _vp],
+    "pero_grad_norm_finish": [_vp, _i64, _f64, _vp, _vp],
     "pero_vq_argmin": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp],
     "pero_vq_gather": [_vp, _vp, _vp, _vp, _i64, _i64, _vp],
     "pero_gather_rows": [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp],

@@ -23,7 +23,8 @@ def get_training_state_path(checkpoints_directory, iteration):
 
 def save_training_state(path, optimizer, iteration, device=None):
     """Everything besides the model weights (which stay in the reference's own checkpoint file / format).  Only tensors,
-    numbers, strings, lists and dicts: the file loads with torch.load(weights_only=True)."""
+    numbers, strings, lists and dicts: the file loads with torch.load(weights_only=True).  The optimizer's state_dict carries every
+    parameter group's moments (amsgrad's running maximum included) and hyper-parameters (weight decay, its mode, max_grad_norm)."""
     kind, keys, pos, has_gauss, cached = np.random.get_state()
     state = {"iteration": int(iteration), "optimizer": optimizer.state_dict(),
              "numpy_rng": {"kind": kind, "keys": torch.from_numpy(keys.astype(np.int64)), "pos": int(pos),

@@ -13,7 +13,7 @@ import torch
 
 from ..common.helpers import (get_checkpoint_path, get_training_state_path, load_training_state, save_training_state)
 from ..common.lr_scheduler import WarmupSchleduler
-from ..optim import FusedAdam
+from ..optim import FusedAdam, FusedAdamW, decay_groups
 from .batch_operator import BatchOperator
 from .model import MaskedCrossEntropyLoss, MaskedTransformerEncoder, init_backbone, init_head
 from .tester import Tester
@@ -79,9 +79,14 @@ def view_step_handler(iteration, model, elapsed_time, iteration_count, trn_teste
 
 
 def init_training(batch_operator, model, dataset, trn_tester, tst_tester, learning_rate, warmup_iterations,
-                  checkpoints_directory, bfloat16=False, clearml_logger=None, data_parallel=None):
-    """train.py:144-163 with FusedAdam in place of torch.optim.Adam (same hyper-parameters)."""
-    optimizer = FusedAdam(model.parameters(), lr=learning_rate)
+                  checkpoints_directory, bfloat16=False, clearml_logger=None, data_parallel=None, weight_decay=0.0, max_grad_norm=None):
+    """train.py:144-163 with FusedAdam in place of torch.optim.Adam (same hyper-parameters).
+    weight_decay > 0 (not in the reference): FusedAdamW over decay_groups(model, weight_decay) - decoupled decay of the matrices, none of
+    the biases and norm weights; max_grad_norm: global-norm clip inside the optimizer's launches (optim.py)."""
+    if weight_decay > 0:
+        optimizer = FusedAdamW(decay_groups(model, weight_decay), lr=learning_rate, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+    else:
+        optimizer = FusedAdam(model.parameters(), lr=learning_rate, max_grad_norm=max_grad_norm)
     scheduler = WarmupSchleduler(optimizer, learning_rate, warmup_iterations, 1)
     trainer = Trainer(batch_operator, model, dataset, optimizer, scheduler, bfloat16=bfloat16, data_parallel=data_parallel)
     trainer.on_view_step = partial(view_step_handler, trn_tester=trn_tester, tst_tester=tst_tester,

@@ -415,6 +415,50 @@ def adam_step(p, g, m, v, p_bf16, lr, beta1, beta2, eps, step, grad_scale=1.0):
          float(eps), int(step), float(grad_scale), stream())
 
 
+def adam_step_ex(p, g, m, v, p_bf16, lr, beta1, beta2, eps, step, grad_scale=1.0, weight_decay=0.0, decoupled=False, vmax=None,
+                 maximize=False, grad_norm=None, max_norm=0.0):
+    """pero_adam_step_ex: vmax (f32, like v) switches amsgrad on; grad_norm (one f32 on the device, see grad_norm_finish) the clip at
+    max_norm.  With the defaults it is adam_step, bit for bit."""
+    call("pero_adam_step_ex", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_bf16), p.numel(), float(lr), float(beta1), float(beta2),
+         float(eps), int(step), float(grad_scale), float(weight_decay), int(bool(decoupled)), ptr(vmax), int(bool(maximize)),
+         ptr(grad_norm), float(max_norm), stream())
+
+
+# layout of the norm's first pass (csrc/optim.hip): 16-byte pieces, 256 lanes per workgroup, one workgroup per 1024 pieces up to a cap
+SUMSQ_LANES, SUMSQ_PIECES_PER_BLOCK, SUMSQ_MAX_BLOCKS = 256, 1024, 2048
+
+
+def sumsq_num_partials(n):
+    """Number of partial sums pero_sumsq_partials writes for n elements (a function of n alone)."""
+    return int(_lib.lib().pero_sumsq_num_partials(int(n)))
+
+
+def sumsq_chain(n):
+    """Longest chain of f32 additions one partial goes through for n elements: the lane's running sum over its pieces, the fold of the
+    piece's four elements (2), the wave butterfly (6), the four waves (3)."""
+    nv = (n + 3) // 4
+    blocks = max(1, min((nv + SUMSQ_PIECES_PER_BLOCK - 1) // SUMSQ_PIECES_PER_BLOCK, SUMSQ_MAX_BLOCKS))
+    return (nv + blocks * SUMSQ_LANES - 1) // (blocks * SUMSQ_LANES) + 2 + 6 + 3
+
+
+def sumsq_partials(x, partials):
+    """partials[b] = sum of squares of workgroup b's share of the flat f32 buffer x; partials: f32 view of sumsq_num_partials(n) elements."""
+    _req_cuda(x, partials)
+    if x.dtype != torch.float32 or partials.dtype != torch.float32 or not x.is_contiguous() or not partials.is_contiguous():
+        raise TypeError("sumsq_partials: contiguous f32 tensors")
+    if partials.numel() != sumsq_num_partials(x.numel()):
+        raise ValueError(f"sumsq_partials: {x.numel()} elements give {sumsq_num_partials(x.numel())} partials, the view holds {partials.numel()}")
+    call("pero_sumsq_partials", ptr(x), x.numel(), ptr(partials), stream())
+
+
+def grad_norm_finish(partials, scale, out):
+    """out[0] = scale * sqrt(sum(partials)) (f64 sum in index order, one f32 result on the device)."""
+    _req_cuda(partials, out)
+    if partials.dtype != torch.float32 or out.dtype != torch.float32 or not partials.is_contiguous():
+        raise TypeError("grad_norm_finish: contiguous f32 tensors")
+    call("pero_grad_norm_finish", ptr(partials), partials.numel(), float(scale), ptr(out), stream())
+
+
 def vq_argmin(x, codebook, want_dist=False):
     _req_cuda(x, codebook)
     M, D = x.shape

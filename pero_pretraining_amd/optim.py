@@ -4,6 +4,16 @@ masked_pretraining/train.py:146, by ONE HIP launch per step that also refreshes 
 Drop-in: same constructor arguments and param_groups protocol as torch.optim.Adam (the reference's
 WarmupSchleduler writes param_group["lr"]); parameters keep their identity, names and shapes - only their
 storage is moved into the flat buffer, so state_dict()/load_state_dict() of the model are unaffected.
+
+Every hyper-parameter is read per parameter group at each step, as torch does: lr, betas, eps, weight_decay (coupled as in
+torch.optim.Adam, or decoupled as in torch.optim.AdamW with decoupled_weight_decay=True), amsgrad, maximize.  FusedAdamW mirrors
+torch.optim.AdamW; decay_groups(model, weight_decay) builds the usual decay / no-decay pair of groups.
+
+max_grad_norm clips by the global L2 norm over ALL groups inside the Adam launches: one sum-of-squares launch per group, one
+finishing launch, and the Adam kernels read the norm from the device.  `optimizer.grad_norm` is that device tensor (one f32): the norm
+before clipping, the value torch.nn.utils.clip_grad_norm_ returns, with grad_scale applied - under parallel.DataParallel the norm of
+the averaged gradient, identical on every rank.  Nothing reads it on the host.  Unlike clip_grad_norm_, `.grad` itself is left
+unscaled: the coefficient is applied to the gradient on its way into the moments, so a `.grad` read after step() still holds the raw sum.
 """
 import torch
 
@@ -11,15 +21,21 @@ from . import lowp, ops
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False):
-        if weight_decay != 0 or amsgrad or maximize:
-            raise ValueError("FusedAdam: weight_decay / amsgrad / maximize are not implemented (the reference uses none)")
-        # the remaining keys are torch.optim.Adam's group defaults, carried so that state_dict()s are interchangeable
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False, *,
+                 decoupled_weight_decay=False, max_grad_norm=None):
+        if lr < 0 or eps < 0 or weight_decay < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1:
+            raise ValueError(f"FusedAdam: invalid lr / betas / eps / weight_decay: {lr}, {betas}, {eps}, {weight_decay}")
+        if max_grad_norm is not None and not max_grad_norm >= 0:
+            raise ValueError(f"FusedAdam: invalid max_grad_norm: {max_grad_norm}")
+        # the remaining keys are torch.optim.Adam's group defaults, carried so that state_dict()s are interchangeable; max_grad_norm is
+        # this class's own (torch keeps an unknown group key and ignores it)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
                                       foreach=None, capturable=False, differentiable=False, fused=None,
-                                      decoupled_weight_decay=False))
-        self._flat = []  # per group: dict(p, g, m, v, lp, step)
+                                      decoupled_weight_decay=decoupled_weight_decay, max_grad_norm=max_grad_norm))
+        self._flat = []  # per group: dict(p, g, m, v, vmax, lp, step)
         self.grad_scale = 1.0
+        self.grad_norm = None   # one f32 on the device: the global gradient norm of the last clipped step, before clipping
+        self._partials = None   # workspace of the norm: the partial sums of every group, one group behind the other
         self._flatten()
 
     def _flatten(self):
@@ -59,7 +75,8 @@ class FusedAdam(torch.optim.Optimizer):
                 for p, o in zip(ps, offs):
                     if p.dim() >= 2:
                         lowp.put_t(p, flpt[o:o + p.numel()].view(p.numel() // p.shape[0], p.shape[0]))
-            self._flat.append(dict(p=fp, g=fg, m=ops.zeros((total,), dev, torch.float32), v=ops.zeros((total,), dev, torch.float32), lp=flp, step=0,
+            self._flat.append(dict(p=fp, g=fg, m=ops.zeros((total,), dev, torch.float32), v=ops.zeros((total,), dev, torch.float32),
+                                   vmax=ops.zeros((total,), dev, torch.float32) if group["amsgrad"] else None, lp=flp, step=0,
                                    params=ps, offsets=offs, lpt=flpt, ttable=ttable, ttiles=ttiles))
 
     def refresh_lowp(self):
@@ -97,9 +114,10 @@ class FusedAdam(torch.optim.Optimizer):
                 if p.grad is None or p.grad.data_ptr() != f["g"].data_ptr() + 4 * o:
                     p.grad = f["g"][o:o + p.numel()].view(p.shape)
 
-    # ---- checkpointing: the layout of torch.optim.Adam's state_dict (per-parameter 'step', 'exp_avg', 'exp_avg_sq'),
-    # so optimizer state moves between this class and torch.optim.Adam (the reference's optimizer,
-    # masked_pretraining/train.py:146) in both directions.  The reference itself never saves it.
+    # ---- checkpointing: the layout of torch.optim.Adam's state_dict (per-parameter 'step', 'exp_avg', 'exp_avg_sq' and, in an amsgrad
+    # group, 'max_exp_avg_sq'; the group keys carry the real hyper-parameters), so optimizer state moves between this class and
+    # torch.optim.Adam / AdamW (the reference's optimizer, masked_pretraining/train.py:146) in both directions.  The reference itself
+    # never saves it.
     def state_dict(self):
         state, groups, idx = {}, [], 0
         for group, f in zip(self.param_groups, self._flat):
@@ -111,6 +129,8 @@ class FusedAdam(torch.optim.Optimizer):
                     state[idx] = {"step": torch.tensor(float(f["step"])),
                                   "exp_avg": f["m"][o:o + n].view(p.shape).clone(),
                                   "exp_avg_sq": f["v"][o:o + n].view(p.shape).clone()}
+                    if group["amsgrad"]:
+                        state[idx]["max_exp_avg_sq"] = self._vmax(f)[o:o + n].view(p.shape).clone()
                 ids.append(idx)
                 idx += 1
             g = {k: v for k, v in group.items() if k != "params"}
@@ -125,8 +145,6 @@ class FusedAdam(torch.optim.Optimizer):
         for group, saved, f in zip(self.param_groups, groups, self._flat):
             if len(saved["params"]) != len(group["params"]):
                 raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
-            if saved.get("weight_decay", 0) != 0 or saved.get("amsgrad", False) or saved.get("maximize", False):
-                raise ValueError("FusedAdam: the loaded group uses weight_decay / amsgrad / maximize")
             for k, v in saved.items():
                 if k != "params":
                     group[k] = v
@@ -134,6 +152,10 @@ class FusedAdam(torch.optim.Optimizer):
                 continue
             offs = {id(p): o for p, o in zip(f["params"], f["offsets"])}
             f["m"].zero_(); f["v"].zero_()
+            if group["amsgrad"]:
+                self._vmax(f).zero_()
+            else:
+                f["vmax"] = None
             steps = set()
             for p, idx in zip(group["params"], saved["params"]):
                 st = state_dict["state"].get(idx)
@@ -142,14 +164,42 @@ class FusedAdam(torch.optim.Optimizer):
                 o, n = offs[id(p)], p.numel()
                 f["m"][o:o + n].copy_(st["exp_avg"].reshape(-1))
                 f["v"][o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
+                if group["amsgrad"]:  # a state saved without amsgrad starts its running maximum at v, where the next step's max() puts it anyway
+                    f["vmax"][o:o + n].copy_(st.get("max_exp_avg_sq", st["exp_avg_sq"]).reshape(-1))
                 steps.add(int(float(st["step"])))
             if len(steps) > 1:
                 raise ValueError(f"FusedAdam keeps one step counter per group, got {sorted(steps)}")
             f["step"] = steps.pop() if steps else 0
 
+    @staticmethod
+    def _vmax(f):
+        """The amsgrad running maximum of a group's flat buffers, made on first use (a group may turn amsgrad on after construction)."""
+        if f["vmax"] is None:
+            f["vmax"] = ops.zeros((f["v"].numel(),), f["v"].device, torch.float32)
+        return f["vmax"]
+
+    def _global_norm(self):
+        """grad_norm <- grad_scale * ||all flat gradient buffers||_2: one partial-sums launch per group, one finishing launch, no host read."""
+        flats = [f for f in self._flat if f is not None]
+        devices = {f["g"].device for f in flats}
+        if len(devices) > 1:
+            raise RuntimeError(f"FusedAdam: max_grad_norm needs every parameter group on one device, got {sorted(map(str, devices))}")
+        counts = [ops.sumsq_num_partials(f["g"].numel()) for f in flats]
+        dev = flats[0]["g"].device
+        if self._partials is None or self._partials.numel() != sum(counts) or self._partials.device != dev:
+            self._partials = torch.empty(sum(counts), device=dev, dtype=torch.float32)
+        if self.grad_norm is None or self.grad_norm.device != dev:
+            self.grad_norm = torch.zeros(1, device=dev, dtype=torch.float32)
+        start = 0
+        for f, c in zip(flats, counts):
+            ops.sumsq_partials(f["g"], self._partials[start:start + c])
+            start += c
+        ops.grad_norm_finish(self._partials, self.grad_scale, self.grad_norm)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        clipped = False
         for group, f in zip(self.param_groups, self._flat):
             if f is None:
                 continue
@@ -165,9 +215,35 @@ class FusedAdam(torch.optim.Optimizer):
                                            "model.zero_grad(set_to_none=True) / `p.grad = ...`")
                     f["g"][o:o + p.numel()].copy_(p.grad.reshape(-1))
                     p.grad = f["g"][o:o + p.numel()].view(p.shape)
+            clipped = clipped or group.get("max_grad_norm") is not None
+        if clipped:   # over ALL groups, whichever of them clip, and after every gradient is in its flat buffer
+            self._global_norm()
+        for group, f in zip(self.param_groups, self._flat):
+            if f is None:
+                continue
             f["step"] += 1
             b1, b2 = group["betas"]
-            ops.adam_step(f["p"], f["g"], f["m"], f["v"], f["lp"], group["lr"], b1, b2, group["eps"], f["step"],
-                          self.grad_scale)
+            max_norm = group.get("max_grad_norm")
+            ops.adam_step_ex(f["p"], f["g"], f["m"], f["v"], f["lp"], group["lr"], b1, b2, group["eps"], f["step"], self.grad_scale,
+                             weight_decay=group["weight_decay"], decoupled=group.get("decoupled_weight_decay", False),
+                             vmax=self._vmax(f) if group["amsgrad"] else None, maximize=group["maximize"],
+                             grad_norm=self.grad_norm if max_norm is not None else None, max_norm=max_norm or 0.0)
             self._transpose(f)
         return loss
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW's defaults on the same kernels: weight_decay=1e-2, decoupled (p *= 1 - lr * weight_decay before the update)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, maximize=False, *,
+                 decoupled_weight_decay=True, max_grad_norm=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                         decoupled_weight_decay=decoupled_weight_decay, max_grad_norm=max_grad_norm)
+
+
+def decay_groups(model, weight_decay):
+    """The usual two parameter groups: tensors with dim() >= 2 (matrices, convolution kernels, embeddings) are decayed, biases and
+    LayerNorm / BatchNorm weights (dim() < 2) are not.  Inside each group the parameters keep the order of model.parameters()."""
+    params = list(model.parameters())
+    return [{"params": [p for p in params if p.dim() >= 2], "weight_decay": weight_decay},
+            {"params": [p for p in params if p.dim() < 2], "weight_decay": 0.0}]
