@@ -182,6 +182,12 @@ int pero_softmax_fwd(const float* s, void* p, int64_t rows, int64_t cols, float 
 int pero_softmax_bwd(const void* p, const float* dp, void* ds, int64_t rows, int64_t cols, float scale, int dtype,
                      void* stream);
 
+/* pero_softmax_fwd over the keys [k0, k1) of each row's line: key_ranges is int32 (lines, 2) on the device, line = row / rows_per_line
+ * (rows_per_line = num_heads * S for scores laid out (N * num_heads, S, S)); the ranges are clamped as for pero_attention_fwd_keys.  p is exactly 0
+ * outside the range, so pero_softmax_bwd serves unchanged. */
+int pero_softmax_fwd_keys(const float* s, const int* key_ranges, void* p, int64_t rows, int64_t cols, int64_t rows_per_line, float scale,
+                          int dtype, void* stream);
+
 /* ---- fused attention (bf16, head_dim hd = 128 or 64, any S >= 1) on the packed qkv (N*S, 3*nh*hd) tensor ---------
  * out (N*S, nh*hd) = softmax(q k^T / sqrt(hd)) v per (line, head); lse (N*nh, S) f32 = base-2 log-sum-exp of the
  * scaled scores (kept for the backward kernels).  Scores never touch memory.  A line is cut into ceil(S/128) blocks of 128
@@ -204,6 +210,22 @@ int pero_attention_hd64_heads_per_block(int64_t N, int64_t S, int64_t num_heads)
 int pero_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
                        float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim, int dtype,
                        void* stream);
+
+/* ---- fused attention with per-line key ranges (the src_key_padding_mask of a padded, collated batch, as an interval per line).
+ * key_ranges: contiguous int32 (N, 2) on the device; line b attends to the keys [k0_b, k1_b) only:
+ *   out[q] = sum over k in [k0, k1) of softmax_k(q . k / sqrt(hd)) v_k   for EVERY query q in [0, S), padded ones included
+ * (torch scaled_dot_product_attention with a boolean attn_mask of shape (N, 1, 1, S)); lse is the base-2 log-sum-exp over the same keys.
+ * Backward: the dK and dV rows outside the range are exact zeros, dQ is computed for every query.  The library never reads device data on
+ * the host, so the KERNELS clamp a bad range: k0 into [0, S - 1], then k1 into [k0 + 1, S] - an empty or inverted range means "the single
+ * key k0".  Only intervals: no per-key masks, causal masks, biases or dropout.  The other arguments, the `out` / `dvec` conventions, the
+ * dbias accumulation and the size of `work` are those of pero_attention_fwd / pero_attention_bwd.  A full range [0, S) on every line gives
+ * the bits of the calls without ranges.  head_dim 128 always runs the pipelined ragged bodies (KEYS instantiations: csrc/attention_fwd.hip,
+ * attention_bwd.hip), at every S and whatever "attn_pipe" / "attn_lh" say; key tiles without a live key are not visited. */
+int pero_attention_fwd_keys(const void* qkv, const int* key_ranges, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads,
+                            int64_t head_dim, int dtype, void* stream);
+int pero_attention_bwd_keys(const void* qkv, const int* key_ranges, const void* out, const void* dout, const float* lse, float* dvec,
+                            void* dqkv, float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim,
+                            int dtype, void* stream);
 
 /* ---- masked cross entropy (masked_pretraining/model.py:72-95) -------------------------------------------
  * logits (rows, V); labels, mask int64 (rows).  loss_out[0] = mean CE over mask==1 rows

@@ -37,6 +37,9 @@ SIGNATURES = {
     "pero_attention_fwd": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
     "pero_attention_hd64_heads_per_block": [_i64, _i64, _i64],   # returns the count, not a status
     "pero_attention_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
+    "pero_attention_fwd_keys": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
+    "pero_attention_bwd_keys": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
+    "pero_softmax_fwd_keys": [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp],
     "pero_softmax_fwd": [_vp, _vp, _i64, _i64, _f32, _i32, _vp],
     "pero_softmax_bwd": [_vp, _vp, _vp, _i64, _i64, _f32, _i32, _vp],
     "pero_masked_ce_fwd": [_vp, _vp, _vp, _f32, _vp, _vp, _i64, _i64, _i32, _vp],

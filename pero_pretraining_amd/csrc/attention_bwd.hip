@@ -197,10 +197,12 @@ __device__ __forceinline__ constexpr int dq_after(int j) {   // LDS instructions
   for (int k = j + 1; k <= j + DQ_DEPTH && k < 48; k++) n += dq_ninstr(k);
   return n;
 }
-template <bool RAGGED>
+// KEYS (with RAGGED; pero_attention_bwd_keys): the sweep takes the 64-key halves h0 .. that intersect the line's [k0, k1) only, and the 0 select of dS^T covers
+// the dead keys of the first and the last of them.  dQ is computed for every query < S.
+template <bool RAGGED, bool KEYS = false>
 __device__ __forceinline__ void attn_bwd_dq_body_p(unsigned char* smem, int lh, int qb, const bf16raw* qkv, const bf16raw* out,
                                                    const bf16raw* dout, const float* lse2, float* dvec, bf16raw* dqkv, float* dbias, int S,
-                                                   int nh, float c, float scale) {
+                                                   int nh, float c, float scale, const int* kr = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h5 = lane >> 5, r = lane & 31;
   const int nqb = RAGGED ? (S + 127) >> 7 : S >> 7;
   const int line = lh / nh, head = lh % nh;
@@ -210,9 +212,12 @@ __device__ __forceinline__ void attn_bwd_dq_body_p(unsigned char* smem, int lh, 
   const bf16raw* Vg = base + 2 * d;
   const int q = qb * 128 + wave * 32 + r;
   const int qc = RAGGED ? (q < S - 1 ? q : S - 1) : q;   // ragged: a query >= S reads the line's last row; its dS is forced to 0 below
+  at_key_range rng = {0, S};
+  if constexpr (KEYS) rng = at_load_key_range(kr, line, S);
+  const int h0 = KEYS ? rng.k0 >> 6 : 0;   // the line's first live 64-key half
 
-  attn_glds_img<4, RAGGED>(Kg, ld, smem, wave, lane, S - 1);
-  attn_glds_img<4, RAGGED>(Vg, ld, smem + AT_HALF_BYTES, wave, lane, S - 1);
+  attn_glds_img<4, RAGGED>(Kg + (long long)h0 * 64 * ld, ld, smem, wave, lane, S - 1 - h0 * 64);
+  attn_glds_img<4, RAGGED>(Vg + (long long)h0 * 64 * ld, ld, smem + AT_HALF_BYTES, wave, lane, S - 1 - h0 * 64);
 
   bf8v qf[8], gf[8];
   float dsum = 0.f;
@@ -261,15 +266,15 @@ __device__ __forceinline__ void attn_bwd_dq_body_p(unsigned char* smem, int lh, 
   f16v dq[4];
 #pragma unroll
   for (int t = 0; t < 4; t++) dq[t] = (f16v){0};
-  const int nhalf = RAGGED ? (S + 63) >> 6 : S >> 6;   // ragged: a last half without a key is not swept
-  for (int hk = 0; hk < nhalf; hk++) {
+  const int nhalf = KEYS ? ((rng.k1 + 63) >> 6) - h0 : RAGGED ? (S + 63) >> 6 : S >> 6;   // ragged: a last half without a key is not swept; keys: live halves only
+  for (int hk = 0; hk < nhalf; hk++) {   // half h0 + hk of the line, in buffer hk & 1
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // half hk landed; every wave is done with the other buffer
     const unsigned stage = s0 + (hk & 1) * 2 * AT_HALF_BYTES;
     if (hk + 1 < nhalf) {
       unsigned char* nb = smem + ((hk + 1) & 1) * 2 * AT_HALF_BYTES;
-      attn_glds_img<4, RAGGED>(Kg + (long long)(hk + 1) * 64 * ld, ld, nb, wave, lane, S - 1 - (hk + 1) * 64);
-      attn_glds_img<4, RAGGED>(Vg + (long long)(hk + 1) * 64 * ld, ld, nb + AT_HALF_BYTES, wave, lane, S - 1 - (hk + 1) * 64);
+      attn_glds_img<4, RAGGED>(Kg + (long long)(h0 + hk + 1) * 64 * ld, ld, nb, wave, lane, S - 1 - (h0 + hk + 1) * 64);
+      attn_glds_img<4, RAGGED>(Vg + (long long)(h0 + hk + 1) * 64 * ld, ld, nb + AT_HALF_BYTES, wave, lane, S - 1 - (h0 + hk + 1) * 64);
     }
     bf8v fr[8];
     f16v s, dp;
@@ -299,7 +304,19 @@ __device__ __forceinline__ void attn_bwd_dq_body_p(unsigned char* smem, int lh, 
           const float p = __builtin_amdgcn_exp2f(fmaf(s[e], c, -lq));
           s[e] = p * (dp[e] - dsum) * scale;
         }
-        if (RAGGED && (hk == nhalf - 1 || qb == nqb - 1)) {
+        if constexpr (KEYS) {
+          if (hk == 0 || hk == nhalf - 1 || qb == nqb - 1) {
+            // dS^T selected to 0 for keys outside [k0, k1) (the first and the last live half) and queries >= S (the last query block)
+            constexpr int t = j / 24;
+            const int lo = rng.k0 - (h0 + hk) * 64 - t * 32 - 4 * h5;
+            const int hi = q < S ? rng.k1 - (h0 + hk) * 64 - t * 32 - 4 * h5 : lo;
+#pragma unroll
+            for (int e = 0; e < 16; e++) {
+              const int k = 8 * (e >> 2) + (e & 3);
+              s[e] = (k >= lo && k < hi) ? s[e] : 0.f;
+            }
+          }
+        } else if (RAGGED && (hk == nhalf - 1 || qb == nqb - 1)) {
           // dS^T selected to 0 for keys >= S (the line's last half) and queries >= S (its last query block): the staged dQ rows of such
           // queries are exact zeros.  Key of s[e] inside the sub-tile = 8 (e >> 2) + 4 h5 + (e & 3)
           constexpr int t = j / 24;
@@ -439,10 +456,13 @@ __device__ __forceinline__ void attn_bwd_dkv2_body(unsigned char* smem, int lh, 
 #define DKV_TD (DKV_POOL - 1)        // transposed fragments in flight: 5 .. 7
 #define DKV_RDEPTH (DKV_POOL - 2)   // row fragments in flight (a dP product holds two pool entries: dO and V); transposed fragments: 7
                                     // in flight (two LDS instructions each: 14 of the 15 the counter can hold)
-template <bool RAGGED>
+// KEYS (with RAGGED; pero_attention_bwd_keys): every query < S is swept; the staged dK / dV rows of the keys outside the line's [k0, k1) are zeroed the way keys >= S
+// are (a dead key's P may overflow: it stays in that key's MFMA column and is SELECTED away).  A tile wholly outside the range sweeps nothing and still stores
+// zero rows for its real keys (dqkv arrives uninitialised) and zero partial rows of the bias gradient.
+template <bool RAGGED, bool KEYS = false>
 __device__ __forceinline__ void attn_bwd_dkv2_body_p(unsigned char* smem, int lh, int kb, long long nwg, const bf16raw* qkv, const bf16raw* dout,
                                                      const float* lse2, const float* dvec, bf16raw* dqkv, float* dbias, int S, int nh, float c,
-                                                     float scale) {
+                                                     float scale, const int* kr = nullptr) {
   unsigned char* vimg = smem + 4 * AT_SUB_BYTES;
   float* lds_ld = (float*)(smem + 4 * AT_SUB_BYTES + AT_TILE_BYTES);  // [2 buffers][32 lse2 | 32 D]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h5 = lane >> 5, r = lane & 31;
@@ -495,7 +515,10 @@ __device__ __forceinline__ void attn_bwd_dkv2_body_p(unsigned char* smem, int lh
   f16v dv[4], dk[4];
 #pragma unroll
   for (int t = 0; t < 4; t++) { dv[t] = (f16v){0}; dk[t] = (f16v){0}; }
-  const int nsub = RAGGED ? (S + 31) >> 5 : S >> 5;   // ragged: stages without a query are not swept
+  at_key_range rng = {0, S};
+  if constexpr (KEYS) rng = at_load_key_range(kr, line, S);
+  const bool dead_tile = KEYS && (kb * 128 >= rng.k1 || kb * 128 + 128 <= rng.k0);
+  const int nsub = dead_tile ? 0 : RAGGED ? (S + 31) >> 5 : S >> 5;   // ragged: stages without a query are not swept
   for (int sq = 0; sq < nsub; sq++) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // stage sq (Q / dO rows + statistics) landed; every wave is done with the other buffers
@@ -590,8 +613,9 @@ __device__ __forceinline__ void attn_bwd_dkv2_body_p(unsigned char* smem, int lh
     AT_PRIO(0);
     if (sq + 1 < nsub && tid < 64) lds_ld[((sq + 1) & 1) * 64 + tid] = nstat;  // visible after the next barrier
   }
-  if constexpr (RAGGED) {   // keys >= S computed on a copy of the last key: their staged dK / dV rows are exact zeros
-    const bool live = key < S;
+  if constexpr (KEYS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // a dead tile ran no stage: its prologue's LDS-DMA must land before the staging writes
+  if constexpr (RAGGED) {   // keys >= S computed on a copy of the last key (keys outside the range: on dead operands): their staged dK / dV rows are exact zeros
+    const bool live = KEYS ? (key >= rng.k0 && key < rng.k1) : key < S;
 #pragma unroll
     for (int t = 0; t < 4; t++)
 #pragma unroll
@@ -615,12 +639,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv2_k(const bf16raw* qkv, co
 // workgroups of a (line, head) - its dQ blocks and its dK / dV blocks, which all read the same Q, K, V and dO rows - sit next to
 // each other in one XCD's dispatch order, so the rows come from HBM once and the other readers find them in that XCD's L2
 // (FETCH_SIZE of the backward at 256 lines: 534 MB as two launches, 308 MB paired, 267 MB = each row once; 789 -> 740 us at 1024 lines).
-template <bool PIPE, bool RAGGED = false>
-__global__ __launch_bounds__(256, 2) void attn_bwd_pair_k(const bf16raw* qkv, const bf16raw* dout, const float* lse2, float* dvec,
-                                                          bf16raw* dqkv, float* dbias, int S, int nh, float c, float scale, int order) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int nb = RAGGED ? (S + 127) >> 7 : S >> 7;
-  int lh, blk;
+__device__ __forceinline__ void attn_pair_map(int nb, int order, int& lh, int& blk) {
   attn_block_map(blockIdx.x, 2 * nb, gridDim.x / (2 * nb), lh, blk);
   {   // Dispatch order inside an XCD (pero_set_option("attn_order", n); default 32): chunks of 32 units whose 64 dK / dV blocks - one round of the XCD's 64 workgroup
       // places - go out ahead of their 64 dQ blocks, so that the CUs of an XCD run ONE kind of block at a time: medians of six launches (tools/attn_order_ab.py, 2048 lines)
@@ -643,6 +662,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pair_k(const bf16raw* qkv, co
       }
     }
   }
+}
+template <bool PIPE, bool RAGGED = false>
+__global__ __launch_bounds__(256, 2) void attn_bwd_pair_k(const bf16raw* qkv, const bf16raw* dout, const float* lse2, float* dvec,
+                                                          bf16raw* dqkv, float* dbias, int S, int nh, float c, float scale, int order) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int nb = RAGGED ? (S + 127) >> 7 : S >> 7;
+  int lh, blk;
+  attn_pair_map(nb, order, lh, blk);
   if (blk < nb) {
     if (PIPE) attn_bwd_dq_body_p<RAGGED>(smem, lh, blk, qkv, nullptr, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
     else attn_bwd_dq_body(smem, lh, blk, qkv, nullptr, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
@@ -650,6 +677,32 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pair_k(const bf16raw* qkv, co
     if (PIPE) attn_bwd_dkv2_body_p<RAGGED>(smem, lh, blk - nb, (long long)(gridDim.x >> 1), qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
     else attn_bwd_dkv2_body(smem, lh, blk - nb, (long long)(gridDim.x >> 1), qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
   }
+}
+// ---- the three launches with per-line key ranges: the KEYS instantiations of the pipelined ragged bodies
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_keys_k(const bf16raw* qkv, const int* kr, const bf16raw* out, const bf16raw* dout, const float* lse2,
+                                                             float* dvec, bf16raw* dqkv, float* dbias, int S, int nh, float c, float scale) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int nqb = (S + 127) >> 7;
+  int lh, qb;
+  attn_block_map(blockIdx.x, nqb, gridDim.x / nqb, lh, qb);
+  attn_bwd_dq_body_p<true, true>(smem, lh, qb, qkv, out, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale, kr);
+}
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkv2_keys_k(const bf16raw* qkv, const int* kr, const bf16raw* dout, const float* lse2, const float* dvec,
+                                                               bf16raw* dqkv, float* dbias, int S, int nh, float c, float scale) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int nkb = (S + 127) >> 7;
+  int lh, kb;
+  attn_block_map(blockIdx.x, nkb, gridDim.x / nkb, lh, kb);
+  attn_bwd_dkv2_body_p<true, true>(smem, lh, kb, gridDim.x, qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale, kr);
+}
+__global__ __launch_bounds__(256, 2) void attn_bwd_pair_keys_k(const bf16raw* qkv, const int* kr, const bf16raw* dout, const float* lse2, float* dvec,
+                                                               bf16raw* dqkv, float* dbias, int S, int nh, float c, float scale, int order) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int nb = (S + 127) >> 7;
+  int lh, blk;
+  attn_pair_map(nb, order, lh, blk);
+  if (blk < nb) attn_bwd_dq_body_p<true, true>(smem, lh, blk, qkv, nullptr, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale, kr);
+  else attn_bwd_dkv2_body_p<true, true>(smem, lh, blk - nb, (long long)(gridDim.x >> 1), qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale, kr);
 }
 
 constexpr int AT_PAIR_LDS = AT_DKV2_LDS > 2 * AT_TILE_BYTES ? AT_DKV2_LDS : 2 * AT_TILE_BYTES;   // a paired workgroup runs either body
@@ -707,5 +760,43 @@ extern "C" int pero_attention_bwd(const void* qkv, const void* out, const void* 
   if (dbias)
     hipLaunchKernelGGL(attn_bias_reduce_k, dim3((unsigned)num_heads, 3, (N * nb >= 4096) ? 128 : (N * nb >= 1024) ? 64 : 16), dim3(128), 0, st, work, dbias, (int)N, (int)num_heads, (int)nb);
   PERO_CHECK_LAUNCH("pero_attention_bwd");
+  return PERO_OK;
+}
+
+// The same with per-line key ranges (include/pero_hip.h): always the KEYS instantiations of the pipelined ragged bodies - two launches when D is computed
+// here, the paired launch when it is handed in - at every S and whatever "attn_pipe", "attn_lh" say; "attn_order" only orders the paired dispatch.
+extern "C" int pero_attention_bwd_keys(const void* qkv, const int* key_ranges, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
+                                       float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim, int dtype, void* stream) {
+  PERO_REQUIRE(qkv && key_ranges && dout && lse && dvec && dqkv, "pero_attention_bwd_keys: null pointer");
+  PERO_REQUIRE(dtype == PERO_BF16 && (head_dim == 64 || head_dim == 128) && S > 0 && N > 0 && num_heads > 0,
+               "pero_attention_bwd_keys: fused kernel needs bf16, head_dim 64 or 128, S > 0 (got hd=%lld S=%lld)", (long long)head_dim, (long long)S);
+  PERO_REQUIRE(aligned16(qkv) && (!out || aligned16(out)) && aligned16(dout) && aligned16(dqkv), "pero_attention_bwd_keys: 16-byte alignment");
+  PERO_REQUIRE(!dbias || work, "pero_attention_bwd_keys: dbias needs the partial-sum workspace");
+  hipStream_t st = (hipStream_t)stream;
+  if (head_dim == 64) {   // attention_hd64.hip
+    attn64_bwd_keys_launch(qkv, key_ranges, out, dout, lse, dvec, dqkv, dbias, work, N, S, num_heads, st);
+    PERO_CHECK_LAUNCH("pero_attention_bwd_keys");
+    return PERO_OK;
+  }
+  PERO_LDS_ATTR(attn_bwd_dq_keys_k, 2 * AT_TILE_BYTES);
+  PERO_LDS_ATTR(attn_bwd_dkv2_keys_k, AT_DKV2_LDS);
+  PERO_LDS_ATTR(attn_bwd_pair_keys_k, AT_PAIR_LDS);
+  const float scale = (float)(1.0 / sqrt((double)head_dim));
+  const float c = (float)(1.4426950408889634 / sqrt((double)head_dim));
+  const int64_t nb = (S + 127) / 128;
+  dim3 grid((unsigned)(N * num_heads * nb)), block(256);
+  const bf16raw *q_ = (const bf16raw*)qkv, *o_ = (const bf16raw*)out, *g_ = (const bf16raw*)dout;
+  bf16raw* dq_ = (bf16raw*)dqkv;
+  float* const part = dbias ? work : nullptr;
+  if (!out && g_opt.attn_bwd_pair) {
+    hipLaunchKernelGGL(attn_bwd_pair_keys_k, dim3(2 * grid.x), block, AT_PAIR_LDS, st, q_, key_ranges, g_, lse, dvec, dq_, part, (int)S, (int)num_heads, c, scale,
+                       g_opt.attn_order);
+  } else {
+    hipLaunchKernelGGL(attn_bwd_dq_keys_k, grid, block, 2 * AT_TILE_BYTES, st, q_, key_ranges, o_, g_, lse, dvec, dq_, part, (int)S, (int)num_heads, c, scale);
+    hipLaunchKernelGGL(attn_bwd_dkv2_keys_k, grid, block, AT_DKV2_LDS, st, q_, key_ranges, g_, lse, dvec, dq_, part, (int)S, (int)num_heads, c, scale);
+  }
+  if (dbias)
+    hipLaunchKernelGGL(attn_bias_reduce_k, dim3((unsigned)num_heads, 3, (N * nb >= 4096) ? 128 : (N * nb >= 1024) ? 64 : 16), dim3(128), 0, st, work, dbias, (int)N, (int)num_heads, (int)nb);
+  PERO_CHECK_LAUNCH("pero_attention_bwd_keys");
   return PERO_OK;
 }

@@ -1,7 +1,7 @@
 // What the three attention kernel families share: the forward (attention_fwd.hip), the tiled backward (attention_bwd.hip) and the persistent
 // (line, head) backward (attention_lh.hip).  Fused multi-head attention for the encoder layers (torch SDPA inside
-// TransformerEncoderLayer._sa_block, reference models/transformers.py:36-43,86): softmax(q k^T / sqrt(hd)) v over all S keys of a line, no
-// masks; bf16, head_dim 128, any S >= 1, operating directly on the packed qkv (N*S, 3d) tensor.
+// TransformerEncoderLayer._sa_block, reference models/transformers.py:36-43,86): softmax(q k^T / sqrt(hd)) v over all S keys of a line - or,
+// opt-in, over one interval of keys per line (KEYS: "Per-line key ranges" below); bf16, head_dim 128, any S >= 1, operating directly on the packed qkv (N*S, 3d) tensor.
 // Ragged S (S % 128 != 0): a line has nb = ceil(S / 128) query blocks and key tiles, the last one with S - 128 (nb - 1) rows.  The launchers then
 // start the RAGGED = true instantiations of the PIPELINED bodies (attn_fwd_p_k, attn_bwd_dq_body_p, attn_bwd_dkv2_body_p) whatever "attn_pipe"
 // says - the compiler-scheduled bodies have no ragged form - under three rules: (1) every row index that feeds a global address is clamped to
@@ -106,6 +106,18 @@ __device__ __forceinline__ bf8v img_tr_frag(const unsigned char* img, int rb, in
   s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s4v, b));
   s8v v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf8v, v);
+}
+
+// ---- Per-line key ranges (pero_attention_fwd_keys / pero_attention_bwd_keys): line b attends to the keys [k0, k1) of key_ranges[b] only.  Rule (2) of
+// the header comment then reads "P is selected to 0 wherever the key is outside [k0, k1)" - k1 <= S covers the keys >= S - and the key walks
+// (forward: 128-key tiles, dQ: 64-key halves) visit only the tiles that intersect the range; rules (1) and (3) stay.  Nothing on the host reads
+// the ranges, so the kernels make a bad one harmless: k0 is clamped into [0, S - 1], k1 into [k0 + 1, S] - an empty range means "the key k0".
+struct at_key_range { int k0, k1; };
+__device__ __forceinline__ at_key_range at_load_key_range(const int* kr, int line, int S) {
+  int k0 = kr[2 * line], k1 = kr[2 * line + 1];   // uniform per workgroup: scalar loads
+  k0 = k0 < 0 ? 0 : (k0 > S - 1 ? S - 1 : k0);
+  k1 = k1 < k0 + 1 ? k0 + 1 : (k1 > S ? S : k1);
+  return {k0, k1};
 }
 
 // Workgroup -> ((line, head), block) so that the blocks of one (line, head) - which read the same K / V (or Q / dO) rows -
@@ -252,3 +264,6 @@ __attribute__((visibility("hidden"))) void attn_bwd_lh_launch(const void* qkv, c
 __attribute__((visibility("hidden"))) void attn64_fwd_launch(const void* qkv, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads, hipStream_t st);
 __attribute__((visibility("hidden"))) void attn64_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
                                                              float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, hipStream_t st);
+__attribute__((visibility("hidden"))) void attn64_fwd_keys_launch(const void* qkv, const int* kr, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads, hipStream_t st);
+__attribute__((visibility("hidden"))) void attn64_bwd_keys_launch(const void* qkv, const int* kr, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
+                                                                  float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, hipStream_t st);

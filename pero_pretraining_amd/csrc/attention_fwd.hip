@@ -1,7 +1,7 @@
 // Forward of the fused attention: attn_fwd_k (compiler-scheduled loop), attn_fwd_p_k (the same loop with software-pipelined operand reads,
 // the default: pero_set_option("attn_pipe")) and their launcher pero_attention_fwd.  One workgroup = 128 queries of one (line, head); 4 waves x
 // 32 queries.  Keys are processed in tiles of 128 (online softmax across tiles).  S % 128 != 0 always runs attn_fwd_p_k<RAGGED = true> (the
-// ragged last tile: attention_common.hpp); attn_fwd_k takes S % 128 == 0 only.  Everything is computed TRANSPOSED so that a query lives
+// ragged last tile: attention_common.hpp); attn_fwd_k takes S % 128 == 0 only; attn_fwd_keys_k = the pipelined ragged body with per-line key ranges.  Everything is computed TRANSPOSED so that a query lives
 // on a LANE and keys / head-dim live on registers (guide section 3 "an accumulator tile as the next MFMA's operand"):
 //   S^T tile (32 keys x 32 q)  = mfma_32x32x16(A = K rows from LDS, B = Q^T from registers)
 //   row max / sum of a query    = in-lane reduction over its 64 score registers + ONE lane^32 exchange
@@ -173,8 +173,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(const bf16raw* qkv, bf16raw
 // (six in flight), the first seven transposed V fragments in flight while the exponentials run, then rolling.  Same MFMAs in the
 // same order: out and lse are bit-identical to attn_fwd_k.
 #define FW_POOL 8
-template <bool RAGGED>
-__global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16raw* out, float* lse2, int S, int nh, int hpb, float c) {
+// KEYS (pero_attention_fwd_keys, with RAGGED): line b attends to the keys [k0, k1) of `kr` only (at_key_range: clamped).  The stream of a head walks
+// the key tiles kt0 .. kt_last that intersect the range - a tile without a live key is never visited: its scores would all be -inf and the
+// running maximum with them, exp2(-inf - -inf) - and the -inf select covers the dead keys of the first and the last of them (k1 <= S: the keys
+// >= S too).  With [0, S) the walk and every MFMA are those of the unmasked kernel and no select fires: same bits.
+template <bool RAGGED, bool KEYS>
+__device__ __forceinline__ void attn_fwd_p_body(const bf16raw* qkv, const int* kr, bf16raw* out, float* lse2, int S, int nh, int hpb, float c) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* kimg = smem;
   unsigned char* vimg = smem + AT_TILE_BYTES;
@@ -186,10 +190,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
   const long long d = (long long)nh * 128, ld = 3 * d;
   const bf16raw* lbase = qkv + (long long)line * S * ld;  // + head * 128 : q ; + d : k ; + 2d : v
   const int q = qb * 128 + wave * 32 + r;  // this lane's query (both lane halves hold the same query)
-  const int nkt = nqb, units = hpb * nkt;
+  at_key_range rng = {0, S};
+  if constexpr (KEYS) rng = at_load_key_range(kr, line, S);
+  const int kt0 = KEYS ? rng.k0 >> 7 : 0;                          // the line's first live key tile
+  const int nkt = KEYS ? ((rng.k1 + 127) >> 7) - kt0 : nqb;        // live key tiles of a head
+  const int kt_last = kt0 + nkt - 1, units = hpb * nkt;
 
-  attn_glds_tile<false, RAGGED>(lbase + head0 * 128 + d, ld, kimg, wave, lane, S - 1);
-  attn_glds_tile<true, RAGGED>(lbase + head0 * 128 + 2 * d, ld, vimg, wave, lane, S - 1);
+  attn_glds_tile<false, RAGGED>(lbase + head0 * 128 + d + (long long)kt0 * 128 * ld, ld, kimg, wave, lane, S - 1 - kt0 * 128);
+  attn_glds_tile<true, RAGGED>(lbase + head0 * 128 + 2 * d + (long long)kt0 * 128 * ld, ld, vimg, wave, lane, S - 1 - kt0 * 128);
 
   // this lane's Q row fragments by loads the compiler does not see (it waits vmcnt(0) for its own loads once LDS-DMA is in flight, which
   // would also wait for the V tile the loop top lets fly): uniform base + 32-bit lane offset
@@ -217,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
   float m = -INFINITY, l = 0.f;
 
   for (int u = 0; u < units; u++) {
-    const int head = head0 + u / nkt, kt = u % nkt;
+    const int head = head0 + u / nkt, kt = kt0 + u % nkt;
     if (u > 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // K(u) (and the head's Q rows); V(u), the newest eight, may still fly
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]), "+v"(qf[4]), "+v"(qf[5]), "+v"(qf[6]), "+v"(qf[7]) :: "memory");   // (older than V(u): landed)
@@ -245,7 +253,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own part of V(u)
     lh_barrier();  // every wave is done with the K image; V(u) landed
     if (u + 1 < units) {
-      const int nhd = head0 + (u + 1) / nkt, nkt_i = (u + 1) % nkt;
+      const int nhd = head0 + (u + 1) / nkt, nkt_i = kt0 + (u + 1) % nkt;
       attn_glds_tile<false, RAGGED>(lbase + nhd * 128 + d + (long long)nkt_i * 128 * ld, ld, kimg, wave, lane, S - 1 - nkt_i * 128);
     }
     // ---- transposed V fragments: m = (t, sub, dt), seven in flight; the first seven go out in front of the softmax arithmetic
@@ -256,7 +264,19 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
     };
     at_static_for<0, 7>(issue_v);
 
-    if (RAGGED && kt == nkt - 1) {
+    if constexpr (KEYS) {
+      if (kt == kt0 || kt == kt_last) {
+        // the first and the last live tile: scores of keys outside [k0, k1) become -inf, so their P is exactly 0; each of the two holds a live key
+        const int lo = rng.k0 - kt * 128 - 4 * h5, hi = rng.k1 - kt * 128 - 4 * h5;
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+          for (int e = 0; e < 16; e++) {
+            const int k = 32 * t + 8 * (e >> 2) + (e & 3);
+            s[t][e] = (k >= lo && k < hi) ? s[t][e] : -INFINITY;
+          }
+      }
+    } else if (RAGGED && kt == nkt - 1) {
       // the line's last key tile: scores of keys >= S (copies of the last key's) become -inf in front of the running maximum, so their P is exactly
       // 0; the tile holds at least one real key, so the maximum stays finite.  Key of s[t][e] = 32 t + 8 (e >> 2) + 4 h5 + (e & 3)
       const int lim = S - kt * 128 - 4 * h5;
@@ -293,7 +313,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
     }
     l = l * alpha + ps;
     m = mn;
-    if (kt != 0) {  // (a head's first tile: O is still zero)
+    if (kt != kt0) {  // (a head's first tile: O is still zero)
 #pragma unroll
       for (int t = 0; t < 4; t++)
 #pragma unroll
@@ -312,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
       o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[mm % FW_POOL], pf, o[dt], 0, 0, 0);
     });
     AT_PRIO(0);
-    if (kt == nkt - 1) {
+    if (kt == kt_last) {
       // ---- head finished: O[q][d] = o[dt][reg] / l, staged through the (now free) V image so that HBM sees whole 256-byte rows in
       // 16-byte lanes.  Image: 128 rows x 256 B, 8-byte granule index XORed with (row & 31).  (LDS accesses by asm: see the note in front of the kernel)
       lh_barrier();  // every wave is done with the V image
@@ -358,10 +378,18 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16r
     }
     if (u + 1 < units) {
       lh_barrier();  // every wave is done with the V image (and with the O staging reads)
-      const int nhd = head0 + (u + 1) / nkt, nkt_i = (u + 1) % nkt;
+      const int nhd = head0 + (u + 1) / nkt, nkt_i = kt0 + (u + 1) % nkt;
       attn_glds_tile<true, RAGGED>(lbase + nhd * 128 + 2 * d + (long long)nkt_i * 128 * ld, ld, vimg, wave, lane, S - 1 - nkt_i * 128);
     }
   }
+}
+
+template <bool RAGGED>
+__global__ __launch_bounds__(256, 2) void attn_fwd_p_k(const bf16raw* qkv, bf16raw* out, float* lse2, int S, int nh, int hpb, float c) {
+  attn_fwd_p_body<RAGGED, false>(qkv, nullptr, out, lse2, S, nh, hpb, c);
+}
+__global__ __launch_bounds__(256, 2) void attn_fwd_keys_k(const bf16raw* qkv, const int* kr, bf16raw* out, float* lse2, int S, int nh, int hpb, float c) {
+  attn_fwd_p_body<true, true>(qkv, kr, out, lse2, S, nh, hpb, c);
 }
 
 // heads per workgroup: as many as keep >= 2 workgroups per CU busy
@@ -394,5 +422,26 @@ extern "C" int pero_attention_fwd(const void* qkv, void* out, float* lse, int64_
   hipLaunchKernelGGL(kernel, dim3((unsigned)(N * (num_heads / hpb) * ((S + 127) / 128))), dim3(256), 2 * AT_TILE_BYTES,
                      (hipStream_t)stream, (const bf16raw*)qkv, (bf16raw*)out, lse, (int)S, (int)num_heads, hpb, c);
   PERO_CHECK_LAUNCH("pero_attention_fwd");
+  return PERO_OK;
+}
+
+// The same with per-line key ranges (include/pero_hip.h): always the pipelined ragged body, at every S and whatever "attn_pipe" says.
+extern "C" int pero_attention_fwd_keys(const void* qkv, const int* key_ranges, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads,
+                                       int64_t head_dim, int dtype, void* stream) {
+  PERO_REQUIRE(qkv && key_ranges && out && lse, "pero_attention_fwd_keys: null pointer");
+  PERO_REQUIRE(dtype == PERO_BF16 && (head_dim == 64 || head_dim == 128) && S > 0 && N > 0 && num_heads > 0,
+               "pero_attention_fwd_keys: fused kernel needs bf16, head_dim 64 or 128, S > 0 (got hd=%lld S=%lld)", (long long)head_dim, (long long)S);
+  PERO_REQUIRE(aligned16(qkv) && aligned16(out), "pero_attention_fwd_keys: 16-byte alignment");
+  if (head_dim == 64) {   // attention_hd64.hip
+    attn64_fwd_keys_launch(qkv, key_ranges, out, lse, N, S, num_heads, (hipStream_t)stream);
+    PERO_CHECK_LAUNCH("pero_attention_fwd_keys");
+    return PERO_OK;
+  }
+  PERO_LDS_ATTR(attn_fwd_keys_k, 2 * AT_TILE_BYTES);
+  const float c = (float)(1.4426950408889634 / sqrt((double)head_dim));
+  const int hpb = attn_heads_per_block(N, S, num_heads);
+  hipLaunchKernelGGL(attn_fwd_keys_k, dim3((unsigned)(N * (num_heads / hpb) * ((S + 127) / 128))), dim3(256), 2 * AT_TILE_BYTES,
+                     (hipStream_t)stream, (const bf16raw*)qkv, key_ranges, (bf16raw*)out, lse, (int)S, (int)num_heads, hpb, c);
+  PERO_CHECK_LAUNCH("pero_attention_fwd_keys");
   return PERO_OK;
 }

@@ -116,7 +116,11 @@ __device__ __forceinline__ void a64_store_tile(const f16v (&acc)[2], unsigned ch
 // first LDS read behind every DMA, here the first V fragment of the P V cluster - so K(kt + 1) is waited for in the middle of tile kt, under
 // the softmax only, not under the P V MFMAs (the plain bodies' behaviour described in attention_common.hpp, "Software-pipelined operand
 // reads").  Correct either way; it is part of the 12-23 % by which these loops trail the inline-asm head_dim-128 ones.
-__global__ __launch_bounds__(256, 2) void attn64_fwd_k(const bf16raw* qkv, bf16raw* out, float* lse2, int S, int nh, int hpb, float c) {
+// KEYS (pero_attention_fwd_keys): line b attends to the keys [k0, k1) of `kr` only (at_key_range, attention_common.hpp: clamped).  A head's stream walks the key
+// tiles kt0 .. kt_last that intersect the range - a tile without a live key would leave the running maximum at -inf - and the -inf select covers the dead keys
+// of the first and the last of them.  With [0, S): the walk, the MFMAs and the bits of the unmasked kernel.
+template <bool KEYS>
+__device__ __forceinline__ void attn64_fwd_body(const bf16raw* qkv, const int* kr, bf16raw* out, float* lse2, int S, int nh, int hpb, float c) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* kimg = smem;
   unsigned char* vimg = smem + A64_TILE_BYTES;
@@ -130,12 +134,17 @@ __global__ __launch_bounds__(256, 2) void attn64_fwd_k(const bf16raw* qkv, bf16r
   const long long d = (long long)nh * 64, ld = 3 * d;
   const bf16raw* lbase = qkv + (long long)line * S * ld;
   const bf16raw* base = lbase + head0 * 64;
-  const int units = hpb * nb;  // q ; + d : k ; + 2d : v
+  at_key_range rng = {0, S};
+  if constexpr (KEYS) rng = at_load_key_range(kr, line, S);
+  const int kt0 = KEYS ? rng.k0 >> 7 : 0;                       // the line's first live key tile
+  const int nkt = KEYS ? ((rng.k1 + 127) >> 7) - kt0 : nb;      // live key tiles of a head
+  const int kt_last = kt0 + nkt - 1;
+  const int units = hpb * nkt;  // q ; + d : k ; + 2d : v
   const int q = qb * 128 + wave * 32 + r;  // this lane's query (both lane halves hold the same query)
   const int qc = q < S - 1 ? q : S - 1;    // a query >= S computes on a copy of the line's last row and stores nothing
 
-  a64_glds<4>(base + d, ld, kimg, wave, lane, S - 1);
-  a64_glds<4>(base + 2 * d, ld, vimg, wave, lane, S - 1);
+  a64_glds<4>(base + d + (long long)kt0 * 128 * ld, ld, kimg, wave, lane, S - 1 - kt0 * 128);
+  a64_glds<4>(base + 2 * d + (long long)kt0 * 128 * ld, ld, vimg, wave, lane, S - 1 - kt0 * 128);
   bf8v qf[4];
   {
     const bf16raw* qrow = base + (long long)qc * ld + 8 * h5;
@@ -148,7 +157,7 @@ __global__ __launch_bounds__(256, 2) void attn64_fwd_k(const bf16raw* qkv, bf16r
   float m = -INFINITY, l = 0.f;
 
   for (int u = 0; u < units; u++) {
-    const int head = head0 + u / nb, kt = u % nb;
+    const int head = head0 + u / nkt, kt = kt0 + u % nkt;
     if (u > 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // K(kt) landed
@@ -164,10 +173,22 @@ __global__ __launch_bounds__(256, 2) void attn64_fwd_k(const bf16raw* qkv, bf16r
     AT_PRIO(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own part of V(kt)
     __syncthreads();  // every wave is done with the K image; V(kt) landed
-    const int nhd = head0 + (u + 1) / nb, nkt = (u + 1) % nb;
-    if (u + 1 < units) a64_glds<4>(lbase + nhd * 64 + d + (long long)nkt * 128 * ld, ld, kimg, wave, lane, S - 1 - nkt * 128);
+    const int nhd = head0 + (u + 1) / nkt, nkt_i = kt0 + (u + 1) % nkt;
+    if (u + 1 < units) a64_glds<4>(lbase + nhd * 64 + d + (long long)nkt_i * 128 * ld, ld, kimg, wave, lane, S - 1 - nkt_i * 128);
 
-    if (kt == nb - 1 && (S & 127)) {
+    if constexpr (KEYS) {
+      if (kt == kt0 || kt == kt_last) {
+        // the first and the last live tile: scores of keys outside [k0, k1) become -inf, so their P is exactly 0; each of the two holds a live key
+        const int lo = rng.k0 - kt * 128 - 4 * h5, hi = rng.k1 - kt * 128 - 4 * h5;
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+          for (int e = 0; e < 16; e++) {
+            const int k = 32 * t + 8 * (e >> 2) + (e & 3);
+            s[t][e] = (k >= lo && k < hi) ? s[t][e] : -INFINITY;
+          }
+      }
+    } else if (kt == nb - 1 && (S & 127)) {
       // the line's ragged last key tile: scores of keys >= S (copies of the last key's) become -inf in front of the running maximum, so their
       // P is exactly 0; the tile holds at least one real key.  Key of s[t][e] = 32 t + 8 (e >> 2) + 4 h5 + (e & 3)
       const int lim = S - kt * 128 - 4 * h5;
@@ -204,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void attn64_fwd_k(const bf16raw* qkv, bf16r
     }
     l = l * alpha + ps;
     m = mn;
-    if (kt != 0) {  // (the first tile: O is still zero)
+    if (kt != kt0) {  // (the first tile: O is still zero)
 #pragma unroll
       for (int t = 0; t < 2; t++)
 #pragma unroll
@@ -224,7 +245,7 @@ __global__ __launch_bounds__(256, 2) void attn64_fwd_k(const bf16raw* qkv, bf16r
       }
     }
     AT_PRIO(0);
-    if (kt == nb - 1) {
+    if (kt == kt_last) {
       const float inv = 1.0f / l;
 #pragma unroll
       for (int t = 0; t < 2; t++)
@@ -244,9 +265,15 @@ __global__ __launch_bounds__(256, 2) void attn64_fwd_k(const bf16raw* qkv, bf16r
     }
     if (u + 1 < units) {
       __syncthreads();  // every wave is done with the V image (and with the O staging reads)
-      a64_glds<4>(lbase + nhd * 64 + 2 * d + (long long)nkt * 128 * ld, ld, vimg, wave, lane, S - 1 - nkt * 128);
+      a64_glds<4>(lbase + nhd * 64 + 2 * d + (long long)nkt_i * 128 * ld, ld, vimg, wave, lane, S - 1 - nkt_i * 128);
     }
   }
+}
+__global__ __launch_bounds__(256, 2) void attn64_fwd_k(const bf16raw* qkv, bf16raw* out, float* lse2, int S, int nh, int hpb, float c) {
+  attn64_fwd_body<false>(qkv, nullptr, out, lse2, S, nh, hpb, c);
+}
+__global__ __launch_bounds__(256, 2) void attn64_fwd_keys_k(const bf16raw* qkv, const int* kr, bf16raw* out, float* lse2, int S, int nh, int hpb, float c) {
+  attn64_fwd_body<true>(qkv, kr, out, lse2, S, nh, hpb, c);
 }
 
 // ---- backward, dQ: 128 queries of a (line, head), query on the lane, sweeps the keys in 32-key sub-tiles of 64-key halves (K and V half,
@@ -254,9 +281,11 @@ __global__ __launch_bounds__(256, 2) void attn64_fwd_k(const bf16raw* qkv, bf16r
 // the first LDS read behind it, inside the first MFMA cluster, waits for it there, so only the issue is early, not the overlap; the same holds
 // for the next (Q, dO) stage of the dK / dV kernel): S^T = K Q^T, dP^T = V dO^T, dS^T = P^T (dP^T - D) scale,
 // dQ^T += K^T dS^T.  Writes D[q] = sum_d dO[q][d] O[q][d] into dvec[(line*S + q)*nh + head] when `out` is given, reads it when `out` is null.
-__global__ __launch_bounds__(256, 2) void attn64_bwd_dq_k(const bf16raw* qkv, const bf16raw* out, const bf16raw* dout, const float* lse2,
-                                                          float* dvec, bf16raw* dqkv, float* part, int S, int nh, float c, float scale) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// KEYS (pero_attention_bwd_keys): the sweep takes the 64-key halves h0 .. that intersect the line's [k0, k1) only; the 0 select of dS^T covers the dead keys of the
+// first and the last of them.  dQ is computed for every query < S.
+template <bool KEYS>
+__device__ __forceinline__ void attn64_bwd_dq_body(unsigned char* smem, const bf16raw* qkv, const int* kr, const bf16raw* out, const bf16raw* dout, const float* lse2,
+                                                   float* dvec, bf16raw* dqkv, float* part, int S, int nh, float c, float scale) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h5 = lane >> 5, r = lane & 31;
   const int nb = (S + 127) >> 7;
   int lh, qb;
@@ -268,9 +297,12 @@ __global__ __launch_bounds__(256, 2) void attn64_bwd_dq_k(const bf16raw* qkv, co
   const bf16raw* Vg = base + 2 * d;
   const int q = qb * 128 + wave * 32 + r;
   const int qc = q < S - 1 ? q : S - 1;   // a query >= S reads the line's last row; its dS is forced to 0 below
+  at_key_range rng = {0, S};
+  if constexpr (KEYS) rng = at_load_key_range(kr, line, S);
+  const int h0 = KEYS ? rng.k0 >> 6 : 0;   // the line's first live 64-key half
 
-  a64_glds<2>(Kg, ld, smem, wave, lane, S - 1);
-  a64_glds<2>(Vg, ld, smem + A64_HALF_BYTES, wave, lane, S - 1);
+  a64_glds<2>(Kg + (long long)h0 * 64 * ld, ld, smem, wave, lane, S - 1 - h0 * 64);
+  a64_glds<2>(Vg + (long long)h0 * 64 * ld, ld, smem + A64_HALF_BYTES, wave, lane, S - 1 - h0 * 64);
 
   bf8v qf[4], gf[4];
   float dsum = 0.f;
@@ -302,16 +334,16 @@ __global__ __launch_bounds__(256, 2) void attn64_bwd_dq_k(const bf16raw* qkv, co
   f16v dq[2];
   dq[0] = (f16v){0};
   dq[1] = (f16v){0};
-  const int nhalf = (S + 63) >> 6;   // a last half without a key is not swept
-  for (int hk = 0; hk < nhalf; hk++) {
+  const int nhalf = KEYS ? ((rng.k1 + 63) >> 6) - h0 : (S + 63) >> 6;   // a last half without a key is not swept; keys: live halves only
+  for (int hk = 0; hk < nhalf; hk++) {   // half h0 + hk of the line, in buffer hk & 1
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // half hk landed; every wave is done with the other buffer
     const unsigned char* kimg = smem + (hk & 1) * 2 * A64_HALF_BYTES;
     const unsigned char* vimg = kimg + A64_HALF_BYTES;
     if (hk + 1 < nhalf) {
       unsigned char* nbuf = smem + ((hk + 1) & 1) * 2 * A64_HALF_BYTES;
-      a64_glds<2>(Kg + (long long)(hk + 1) * 64 * ld, ld, nbuf, wave, lane, S - 1 - (hk + 1) * 64);
-      a64_glds<2>(Vg + (long long)(hk + 1) * 64 * ld, ld, nbuf + A64_HALF_BYTES, wave, lane, S - 1 - (hk + 1) * 64);
+      a64_glds<2>(Kg + (long long)(h0 + hk + 1) * 64 * ld, ld, nbuf, wave, lane, S - 1 - (h0 + hk + 1) * 64);
+      a64_glds<2>(Vg + (long long)(h0 + hk + 1) * 64 * ld, ld, nbuf + A64_HALF_BYTES, wave, lane, S - 1 - (h0 + hk + 1) * 64);
     }
 #pragma unroll
     for (int t = 0; t < 2; t++) {  // 32-key sub-tile
@@ -328,7 +360,18 @@ __global__ __launch_bounds__(256, 2) void attn64_bwd_dq_k(const bf16raw* qkv, co
         const float p = __builtin_amdgcn_exp2f(fmaf(s[e], c, -lq));
         s[e] = p * (dp[e] - dsum) * scale;  // dS^T
       }
-      if (hk == nhalf - 1 || qb == nb - 1) {
+      if constexpr (KEYS) {
+        if (hk == 0 || hk == nhalf - 1 || qb == nb - 1) {
+          // dS^T selected to 0 for keys outside [k0, k1) (the first and the last live half) and queries >= S (the last query block)
+          const int lo = rng.k0 - (h0 + hk) * 64 - t * 32 - 4 * h5;
+          const int hi = q < S ? rng.k1 - (h0 + hk) * 64 - t * 32 - 4 * h5 : lo;
+#pragma unroll
+          for (int e = 0; e < 16; e++) {
+            const int k = 8 * (e >> 2) + (e & 3);
+            s[e] = (k >= lo && k < hi) ? s[e] : 0.f;
+          }
+        }
+      } else if (hk == nhalf - 1 || qb == nb - 1) {
         // dS^T selected to 0 for keys >= S (the line's last half) and queries >= S (its last query block): the staged dQ rows of such
         // queries are exact zeros.  Key of s[e] inside the sub-tile = 8 (e >> 2) + 4 h5 + (e & 3)
         const int lim = q < S ? S - hk * 64 - t * 32 - 4 * h5 : 0;
@@ -350,12 +393,25 @@ __global__ __launch_bounds__(256, 2) void attn64_bwd_dq_k(const bf16raw* qkv, co
   a64_store_tile(dq, smem, dqkv + ((long long)line * S + qb * 128) * ld + head * 64, ld, part ? part + ((long long)lh * nb + qb) * 64 : nullptr,
                  tid, wave, r, h5, S - qb * 128);
 }
+__global__ __launch_bounds__(256, 2) void attn64_bwd_dq_k(const bf16raw* qkv, const bf16raw* out, const bf16raw* dout, const float* lse2,
+                                                          float* dvec, bf16raw* dqkv, float* part, int S, int nh, float c, float scale) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  attn64_bwd_dq_body<false>(smem, qkv, nullptr, out, dout, lse2, dvec, dqkv, part, S, nh, c, scale);
+}
+__global__ __launch_bounds__(256, 2) void attn64_bwd_dq_keys_k(const bf16raw* qkv, const int* kr, const bf16raw* out, const bf16raw* dout, const float* lse2,
+                                                               float* dvec, bf16raw* dqkv, float* part, int S, int nh, float c, float scale) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  attn64_bwd_dq_body<true>(smem, qkv, kr, out, dout, lse2, dvec, dqkv, part, S, nh, c, scale);
+}
 
 // ---- backward, dK and dV in one pass: 128 keys, key on the lane, the workgroup's V tile resident in LDS, Q / dO in 32-query stages
 // (double-buffered) with their row statistics (lse2, D): S = Q K^T, P, dP = dO V^T, dS; dV^T += dO^T P, dK^T += Q^T dS.
-__global__ __launch_bounds__(256, 2) void attn64_bwd_dkv_k(const bf16raw* qkv, const bf16raw* dout, const float* lse2, const float* dvec,
-                                                           bf16raw* dqkv, float* part, int S, int nh, float c, float scale) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// KEYS (pero_attention_bwd_keys): every query < S is swept; the staged dK / dV rows of the keys outside the line's [k0, k1) are zeroed the way keys >= S are (a dead
+// key's P may overflow: it stays in that key's MFMA column and is SELECTED away).  A tile wholly outside the range sweeps nothing and still stores zero rows for
+// its real keys (dqkv arrives uninitialised) and zero partial rows of the bias gradient.
+template <bool KEYS>
+__device__ __forceinline__ void attn64_bwd_dkv_body(unsigned char* smem, const bf16raw* qkv, const int* kr, const bf16raw* dout, const float* lse2, const float* dvec,
+                                                    bf16raw* dqkv, float* part, int S, int nh, float c, float scale) {
   unsigned char* vimg = smem + 4 * A64_SUB_BYTES;
   float* lds_ld = (float*)(smem + 4 * A64_SUB_BYTES + A64_TILE_BYTES);  // [2 buffers][32 lse2 | 32 D]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h5 = lane >> 5, r = lane & 31;
@@ -389,7 +445,10 @@ __global__ __launch_bounds__(256, 2) void attn64_bwd_dkv_k(const bf16raw* qkv, c
   f16v dv[2], dk[2];  // dV^T, dK^T: 32 d x 32 keys per tile, key on the lane
 #pragma unroll
   for (int t = 0; t < 2; t++) { dv[t] = (f16v){0}; dk[t] = (f16v){0}; }
-  const int nsub = (S + 31) >> 5;   // stages without a query are not swept
+  at_key_range rng = {0, S};
+  if constexpr (KEYS) rng = at_load_key_range(kr, line, S);
+  const bool dead_tile = KEYS && (kb * 128 >= rng.k1 || kb * 128 + 128 <= rng.k0);
+  const int nsub = dead_tile ? 0 : (S + 31) >> 5;   // stages without a query are not swept
   for (int sq = 0; sq < nsub; sq++) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // stage sq (Q / dO rows + statistics) landed; every wave is done with the other buffers
@@ -439,8 +498,9 @@ __global__ __launch_bounds__(256, 2) void attn64_bwd_dkv_k(const bf16raw* qkv, c
     AT_PRIO(0);
     if (sq + 1 < nsub && tid < 64) lds_ld[((sq + 1) & 1) * 64 + tid] = nstat;  // visible after the next barrier
   }
-  {   // keys >= S computed on a copy of the last key: their staged dK / dV rows are exact zeros
-    const bool live = key < S;
+  if constexpr (KEYS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // a dead tile ran no stage: its prologue's LDS-DMA must land before the staging writes
+  {   // keys >= S computed on a copy of the last key (keys outside the range: on dead operands): their staged dK / dV rows are exact zeros
+    const bool live = KEYS ? (key >= rng.k0 && key < rng.k1) : key < S;
 #pragma unroll
     for (int t = 0; t < 2; t++)
 #pragma unroll
@@ -450,6 +510,16 @@ __global__ __launch_bounds__(256, 2) void attn64_bwd_dkv_k(const bf16raw* qkv, c
   // planes 1 (dK) and 2 (dV) of the partial-sum workspace, nwg = (line, head) x key blocks entries each
   a64_store_tile(dk, smem, tile_o, ld, part ? part + (nwg + (long long)lh * nb + kb) * 64 : nullptr, tid, wave, r, h5, S - kb * 128);
   a64_store_tile(dv, smem, tile_o + d, ld, part ? part + (2 * nwg + (long long)lh * nb + kb) * 64 : nullptr, tid, wave, r, h5, S - kb * 128);
+}
+__global__ __launch_bounds__(256, 2) void attn64_bwd_dkv_k(const bf16raw* qkv, const bf16raw* dout, const float* lse2, const float* dvec,
+                                                           bf16raw* dqkv, float* part, int S, int nh, float c, float scale) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  attn64_bwd_dkv_body<false>(smem, qkv, nullptr, dout, lse2, dvec, dqkv, part, S, nh, c, scale);
+}
+__global__ __launch_bounds__(256, 2) void attn64_bwd_dkv_keys_k(const bf16raw* qkv, const int* kr, const bf16raw* dout, const float* lse2, const float* dvec,
+                                                                bf16raw* dqkv, float* part, int S, int nh, float c, float scale) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  attn64_bwd_dkv_body<true>(smem, qkv, kr, dout, lse2, dvec, dqkv, part, S, nh, c, scale);
 }
 
 // dbias[which * d + head * 64 + c] += sum over the workgroups (line, block) of partial[which][(lh, blk)][c], lh = line * nh + head: the
@@ -510,6 +580,29 @@ void attn64_bwd_launch(const void* qkv, const void* out, const void* dout, const
   hipLaunchKernelGGL(attn64_bwd_dq_k, grid, block, A64_DQ_LDS, st, (const bf16raw*)qkv, (const bf16raw*)out, (const bf16raw*)dout, lse, dvec,
                      (bf16raw*)dqkv, part, (int)S, (int)num_heads, c, scale);
   hipLaunchKernelGGL(attn64_bwd_dkv_k, grid, block, A64_DKV_LDS, st, (const bf16raw*)qkv, (const bf16raw*)dout, lse, dvec, (bf16raw*)dqkv, part,
+                     (int)S, (int)num_heads, c, scale);
+  if (dbias)
+    hipLaunchKernelGGL(attn64_bias_reduce_k, dim3((unsigned)num_heads, 3, (N * nb >= 4096) ? 128 : (N * nb >= 1024) ? 64 : 16), dim3(64), 0, st,
+                       work, dbias, (int)N, (int)num_heads, (int)nb);
+}
+// ---- the same with per-line key ranges (pero_attention_fwd_keys / pero_attention_bwd_keys): same grids, same heads per workgroup
+void attn64_fwd_keys_launch(const void* qkv, const int* kr, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads, hipStream_t st) {
+  const float c = (float)(1.4426950408889634 / sqrt(64.0));
+  const int64_t nb = (S + 127) / 128;
+  const int hpb = a64_heads_per_block(N, S, num_heads);
+  hipLaunchKernelGGL(attn64_fwd_keys_k, dim3((unsigned)(N * (num_heads / hpb) * nb)), dim3(256), A64_FWD_LDS, st, (const bf16raw*)qkv, kr, (bf16raw*)out, lse,
+                     (int)S, (int)num_heads, hpb, c);
+}
+void attn64_bwd_keys_launch(const void* qkv, const int* kr, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv, float* dbias, float* work,
+                            int64_t N, int64_t S, int64_t num_heads, hipStream_t st) {
+  const float scale = (float)(1.0 / sqrt(64.0));
+  const float c = (float)(1.4426950408889634 / sqrt(64.0));
+  const int64_t nb = (S + 127) / 128;
+  const dim3 grid((unsigned)(N * num_heads * nb)), block(256);
+  float* const part = dbias ? work : nullptr;
+  hipLaunchKernelGGL(attn64_bwd_dq_keys_k, grid, block, A64_DQ_LDS, st, (const bf16raw*)qkv, kr, (const bf16raw*)out, (const bf16raw*)dout, lse, dvec,
+                     (bf16raw*)dqkv, part, (int)S, (int)num_heads, c, scale);
+  hipLaunchKernelGGL(attn64_bwd_dkv_keys_k, grid, block, A64_DKV_LDS, st, (const bf16raw*)qkv, kr, (const bf16raw*)dout, lse, dvec, (bf16raw*)dqkv, part,
                      (int)S, (int)num_heads, c, scale);
   if (dbias)
     hipLaunchKernelGGL(attn64_bias_reduce_k, dim3((unsigned)num_heads, 3, (N * nb >= 4096) ? 128 : (N * nb >= 1024) ? 64 : 16), dim3(64), 0, st,

@@ -444,6 +444,39 @@ extern "C" int pero_softmax_fwd(const float* s, void* p, int64_t rows, int64_t c
   PERO_CHECK_LAUNCH("pero_softmax_fwd");
   return PERO_OK;
 }
+// The same over the keys [k0, k1) of the row's line only (line = row / rows_per_line; the range clamped as in the fused kernels: k0 into [0, cols - 1], k1 into
+// [k0 + 1, cols]): the probabilities outside the range are exact zeros, so softmax_bwd_k and the products around it need no change.
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_fwd_keys_k(const float* s, const int* kr, T* p, long long rows, int cols, long long rows_per_line, float scale) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long line = row / rows_per_line;
+  int k0 = kr[2 * line], k1 = kr[2 * line + 1];
+  k0 = k0 < 0 ? 0 : (k0 > cols - 1 ? cols - 1 : k0);
+  k1 = k1 < k0 + 1 ? k0 + 1 : (k1 > cols ? cols : k1);
+  const float* sr = s + row * cols;
+  float mx = -INFINITY;
+  for (int c = k0 + lane; c < k1; c += 64) mx = fmaxf(mx, sr[c] * scale);
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int c = k0 + lane; c < k1; c += 64) sum += expf(sr[c] * scale - mx);
+  sum = wave_sum(sum);
+  const float inv = 1.0f / sum;
+  for (int c = lane; c < cols; c += 64) Elem<T>::st(p + row * cols + c, (c >= k0 && c < k1) ? expf(sr[c] * scale - mx) * inv : 0.f);
+}
+extern "C" int pero_softmax_fwd_keys(const float* s, const int* key_ranges, void* p, int64_t rows, int64_t cols, int64_t rows_per_line, float scale, int dtype,
+                                     void* stream) {
+  PERO_REQUIRE(s && key_ranges && p && rows > 0 && cols > 0 && rows_per_line > 0, "pero_softmax_fwd_keys: bad arguments");
+  dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  if (dtype == PERO_F32)
+    hipLaunchKernelGGL((softmax_fwd_keys_k<float>), grid, block, 0, (hipStream_t)stream, s, key_ranges, (float*)p, (long long)rows, (int)cols, (long long)rows_per_line, scale);
+  else if (dtype == PERO_BF16)
+    hipLaunchKernelGGL((softmax_fwd_keys_k<bf16raw>), grid, block, 0, (hipStream_t)stream, s, key_ranges, (bf16raw*)p, (long long)rows, (int)cols, (long long)rows_per_line, scale);
+  else PERO_REQUIRE(false, "pero_softmax_fwd_keys: bad dtype");
+  PERO_CHECK_LAUNCH("pero_softmax_fwd_keys");
+  return PERO_OK;
+}
 extern "C" int pero_softmax_bwd(const void* p, const float* dp, void* ds, int64_t rows, int64_t cols, float scale, int dtype, void* stream) {
   PERO_REQUIRE(p && dp && ds && rows > 0 && cols > 0, "pero_softmax_bwd: bad arguments");
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);

@@ -9,6 +9,7 @@ head_dim 64 those of csrc/attention_hd64.hip, on the
 packed qkv tensor at every line length S (128-row tiles, the last one ragged when S % 128 != 0; scores never stored; one f32 log-sum-exp
 per query saved for the backward); f32 parity mode and other
 head sizes take the unfused form of torch SDPA - per (line, head) batched GEMMs + a row softmax kernel, scores in f32.
+Opt-in `key_ranges` (int32 (N, 2) on the device): every layer's attention takes the keys [k0, k1) of a line only, on all three paths.
 Every product of the backward pass is pero_gemm with a different operand-layout flag: input gradients as K-contiguous
 products on transposed bf16 weight copies, weight gradients as split-K products into the parameters' f32 `.grad`
 buffers - partial tiles summed in slice order through a caller-owned workspace (ops.gemm_workspace; run-to-run
@@ -149,13 +150,14 @@ def linear_bwd(dy, x, w, b, dtype, need_dx=True, gate=None, residual=None, bias_
 # ---------------------------------------------------------------------------------------------
 # attention on the packed qkv tensor
 # ---------------------------------------------------------------------------------------------
-def attention_fwd(qkv, n, s, h, need_p=True):
+def attention_fwd(qkv, n, s, h, need_p=True, key_ranges=None):
     d = qkv.shape[1] // 3
     hd = d // h
     scores = torch.empty((n * h, s, s), device=qkv.device, dtype=torch.float32)
     ops.gemm_raw(qkv, qkv[:, d:], scores, s, s, hd, 3 * d, 3 * d, s, batch=n * h, batch_inner=h,
                  sA=(s * 3 * d, hd), sB=(s * 3 * d, hd), sC=(h * s * s, s * s))
-    p = ops.softmax_fwd(scores, 1.0 / math.sqrt(hd), qkv.dtype)
+    # key_ranges: the softmax takes each line's keys [k0, k1) only and leaves exact zeros elsewhere, so the products around it - and attention_bwd - stay as they are
+    p = ops.softmax_fwd(scores, 1.0 / math.sqrt(hd), qkv.dtype, **({} if key_ranges is None else {"key_ranges": key_ranges, "rows_per_line": h * s}))
     out = torch.empty((n * s, d), device=qkv.device, dtype=qkv.dtype)
     ops.gemm_raw(p, qkv[:, 2 * d:], out, s, hd, s, s, 3 * d, d, batch=n * h, batch_inner=h,
                  sA=(h * s * s, s * s), sB=(s * 3 * d, hd), sC=(s * d, hd), flags=GEMM_TRANS_B)
@@ -268,6 +270,7 @@ class LayerSaved(NamedTuple):
     rstd2: torch.Tensor
     relu_bits: Optional[torch.Tensor]    # the ReLU's gate as a bit mask (relu_bits_ok) or None
     t2: torch.Tensor                     # norm2's output = the layer's output
+    key_ranges: Optional[torch.Tensor] = None   # int32 (N, 2): the keys [k0, k1) each line attends to (one tensor for all layers), None: all S
 
     @property
     def fused_attention(self):
@@ -292,14 +295,15 @@ def ln_bwd(dt, get, k, t, rstd, norm, dxsum):
     return ops.layernorm_bwd(dt, y, get("mean" + k), rstd, norm.weight.detach(), ensure_grad(norm.weight), ensure_grad(norm.bias), dxsum)
 
 
-def layer_fwd(t, L, n, s, h, dtype, save, force_keep_y=False):
-    """force_keep_y: the LayerNorms keep their input rows for the backward even where the mode would run it from the output (ln_keep_rows)."""
+def layer_fwd(t, L, n, s, h, dtype, save, force_keep_y=False, key_ranges=None):
+    """key_ranges: int32 (N, 2) device tensor, line b attends to the keys [k0, k1) only (ops.key_ranges_from_masks); the choice of the attention path does not depend on it.
+    force_keep_y: the LayerNorms keep their input rows for the backward even where the mode would run it from the output (ln_keep_rows)."""
     at = L.self_attn
     qkv = linear_fwd(t, at.in_proj_weight, at.in_proj_bias, dtype)
     if FUSED_ATTENTION and (ops.attention_fused_ok(qkv, s, h) or ops.attention_fused_hd64_ok(qkv, s, h)):
-        a, p = ops.attention_fwd_fused(qkv, n, s, h)   # p = base-2 log-sum-exp rows (N*h, S)
+        a, p = ops.attention_fwd_fused(qkv, n, s, h, **ops.key_ranges_kw(key_ranges))   # p = base-2 log-sum-exp rows (N*h, S)
     else:
-        a, p = attention_fwd(qkv, n, s, h)             # p = probabilities (N*h, S, S)
+        a, p = attention_fwd(qkv, n, s, h, **ops.key_ranges_kw(key_ranges))             # p = probabilities (N*h, S, S)
     keep_y = force_keep_y or not (save and ln_from_out(dtype))
     y1, t1, mean1, rstd1 = linear_resid_ln_fwd(a, at.out_proj.weight, at.out_proj.bias, t, L.norm1, dtype, keep_y=keep_y)
     bits = None
@@ -308,7 +312,7 @@ def layer_fwd(t, L, n, s, h, dtype, save, force_keep_y=False):
         bits = torch.empty((t1.shape[0], L.linear1.weight.shape[0] // 8), device=t1.device, dtype=torch.uint8)
     hdn = linear_fwd(t1, L.linear1.weight, L.linear1.bias, dtype, relu=True, relu_bits=bits)
     y2, t2, mean2, rstd2 = linear_resid_ln_fwd(hdn, L.linear2.weight, L.linear2.bias, t1, L.norm2, dtype, keep_y=keep_y)
-    return t2, LayerSaved(t, qkv, p, a, y1, mean1, rstd1, t1, hdn, y2, mean2, rstd2, bits, t2) if save else None
+    return t2, LayerSaved(t, qkv, p, a, y1, mean1, rstd1, t1, hdn, y2, mean2, rstd2, bits, t2, key_ranges) if save else None
 
 
 def _layer_bwd_rowwise(dt2, L, saved, get, h, dtype, side, held, dt2_is_dy2=False, gathered=False):
@@ -367,7 +371,8 @@ def _layer_bwd_attn(da, dvec, dy1, L, saved, n, s, h, dtype, side, prev):
     if saved.fused_attention:
         # in_proj's bias gradient = column sums of dqkv: out of the attention kernels' staged output tiles
         fuse_bq = at.in_proj_bias is not None and at.in_proj_bias.requires_grad
-        dqkv = ops.attention_bwd_fused(qkv, saved.a, da, saved.attn_stat, n, s, h, dbias=ensure_grad(at.in_proj_bias) if fuse_bq else None, dvec=dvec)
+        dqkv = ops.attention_bwd_fused(qkv, saved.a, da, saved.attn_stat, n, s, h, dbias=ensure_grad(at.in_proj_bias) if fuse_bq else None, dvec=dvec,
+                                       **ops.key_ranges_kw(saved.key_ranges))
     else:
         dqkv = attention_bwd(qkv, saved.attn_stat, da, n, s, h)
     if prev is not None:   # the lower layer's norm2 (its output is this layer's input t) in the epilogue of in_proj's input-gradient product
@@ -445,8 +450,9 @@ def layer_bwd_rows(dtc, index, nrows, L, saved, n, s, h, dtype, side=None, prev=
 # ---------------------------------------------------------------------------------------------
 # whole backbone: front end + L layers
 # ---------------------------------------------------------------------------------------------
-def backbone_fwd(mod, x, mask, offsets, dtype, save):
+def backbone_fwd(mod, x, mask, offsets, dtype, save, key_ranges=None):
     """x: uint8 (N,H,W,C) line images, or float32 (N,C,H,W) (the reference's model input).
+    key_ranges: int32 (N, 2) device tensor or None - every layer's attention takes the keys [k0, k1) of a line only (the backward reads it from the layers' saved state).
     Returns (tokens (N*S, d) in `dtype`, saved activations or None)."""
     keep = None
     if save and ln_from_out(dtype):
@@ -480,7 +486,7 @@ def backbone_fwd(mod, x, mask, offsets, dtype, save):
                                         mod.intermediate_norm.eps, pe=pe, offsets=offsets, S=s)
     layers = []
     for i, L in enumerate(mod.encoder_layers.layers):
-        t, sv = layer_fwd(t, L, n, s, mod.num_heads, dtype, save, force_keep_y=keep is not None and keep[i])
+        t, sv = layer_fwd(t, L, n, s, mod.num_heads, dtype, save, force_keep_y=keep is not None and keep[i], key_ranges=key_ranges)
         layers.append(sv)
     return t, BackboneSaved(a0, y0, mean0, rstd0, layers, n, s) if save else None
 

@@ -116,6 +116,11 @@ BATCH_VIEWS = True  # encode the two views as one 2N-line batch
 class JointEmbeddingTransformerEncoder(torch.nn.Module):
     """joint_embedding_pretraining/model.py:33-66."""
 
+    # True: the encoder layers attend to each line's valid positions only - view 1's from image_masks1, view 2's from image_masks2 (the hull of the
+    # positions equal to 1: ops.key_ranges_from_masks) - instead of all S positions, padding included, as the reference does.  The companion of
+    # NTXentLoss(apply_masks=True); off: the reference's arithmetic, bit for bit.
+    attend_valid_only = False
+
     def __init__(self, backbone, head, loss):
         super().__init__()
         self.backbone, self.head, self.loss = backbone, head, loss
@@ -124,7 +129,10 @@ class JointEmbeddingTransformerEncoder(torch.nn.Module):
         if BATCH_VIEWS and images1.shape == images2.shape and images1.dtype == images2.dtype and images1.is_cuda:
             # both views through one pass of 2N lines; same weights, same per-view RNG draws
             n = images1.shape[0]
-            tokens = self.backbone.encode_tokens_views([images1, images2])
+            kr = None
+            if self.attend_valid_only:
+                kr = [ops.key_ranges_from_masks(m, device=images1.device) for m in (image_masks1, image_masks2)]
+            tokens = self.backbone.encode_tokens_views([images1, images2], **ops.key_ranges_kw(kr))
             out = self.head(tokens.view(2 * n, -1, tokens.shape[-1]))
             if hasattr(self.loss, "forward_stacked"):
                 # the loss reads both views from the ONE tensor the head wrote and returns one gradient for it (slicing them apart made
@@ -133,14 +141,17 @@ class JointEmbeddingTransformerEncoder(torch.nn.Module):
                 return {"output1": out[:n].detach(), "output2": out[n:].detach(), **loss}
             output1, output2 = out[:n], out[n:]
         else:
-            output1 = self.encode(images1)
-            output2 = self.encode(images2)
+            kr1 = kr2 = None
+            if self.attend_valid_only:
+                kr1, kr2 = (ops.key_ranges_from_masks(m, device=images1.device) for m in (image_masks1, image_masks2))
+            output1 = self.encode(images1, **ops.key_ranges_kw(kr1))
+            output2 = self.encode(images2, **ops.key_ranges_kw(kr2))
         loss = self.loss(output1, output2, image_masks1, image_masks2, shift_masks1, shift_masks2)
         return {"output1": output1.detach(), "output2": output2.detach(), **loss}
 
-    def encode(self, images):
+    def encode(self, images, key_ranges=None):
         n = images.shape[0]
-        tokens = self.backbone.encode_tokens(images, None)
+        tokens = self.backbone.encode_tokens(images, None, **ops.key_ranges_kw(key_ranges))
         return self.head(tokens.view(n, -1, tokens.shape[-1]))
 
     def save(self, path):

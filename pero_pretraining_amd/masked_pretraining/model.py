@@ -199,6 +199,21 @@ class MaskedTransformerEncoder(torch.nn.Module):
     # built from the host twin of an uploaded mask - is compared with the mask ON THE DEVICE; a mask edited in place after its upload, or a
     # caller's list that misses positions, raises instead of giving a loss over the wrong rows.
     check_masked_rows = False
+    # True: the encoder layers attend to each line's VALID positions only - the hull of `labels >= 0`, the positions the loss already calls valid (the
+    # collator pads every line to the batch width and labels the padding -1) - instead of all S positions, padding included, as the reference does
+    # (it hands torch.nn.TransformerEncoder no src_key_padding_mask).  A line's tokens, loss and gradients then no longer depend on the batch's width,
+    # the padding's place or its pixels.  Needs `labels`; explicit `key_ranges` of forward() / encode() win.  Off: the reference's arithmetic, bit for bit.
+    attend_valid_only = False
+
+    def _ranges(self, x, labels, key_ranges):
+        """The key ranges of this step: the caller's, else (attend_valid_only) the hull of labels >= 0 - on the device for device labels (no
+        synchronisation: works inside a captured step), on the host for host labels (a line without a valid label raises there)."""
+        if key_ranges is not None or not self.attend_valid_only or labels is None:
+            return key_ranges
+        if isinstance(labels, torch.Tensor) and labels.is_cuda:
+            return ops.key_ranges_from_masks((labels >= 0).to(torch.uint8))
+        lab = labels.numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        return ops.key_ranges_from_masks((lab >= 0).astype(np.uint8), device=x.device)
 
     def _check_rows(self, mask, index):
         m = torch.as_tensor(mask)
@@ -213,14 +228,14 @@ class MaskedTransformerEncoder(torch.nn.Module):
         self.head = head
         self.loss = MaskedCrossEntropyLoss() if loss is None else loss
 
-    def _forward_masked_rows(self, x, labels, mask, rows=None):
+    def _forward_masked_rows(self, x, labels, mask, rows=None, key_ranges=None):
         index = masked_row_list(mask, rows)   # caller's list, or from the mask's host original: never a device sync
         if index is None:
             return None  # a device-only mask: the dense path (a torch.nonzero round trip per step would cost more than it saves)
         n = index.numel()
         if n == 0:
             return None  # the dense path reproduces the reference's NaN for an empty selection
-        tokens = self.backbone.encode_tokens(x, mask)                # (N*S, d)
+        tokens = self.backbone.encode_tokens(x, mask, **ops.key_ranges_kw(key_ranges))   # (N*S, d)
         index = index.to(tokens.device)
         if self.check_masked_rows:
             self._check_rows(mask, index)
@@ -234,10 +249,13 @@ class MaskedTransformerEncoder(torch.nn.Module):
         loss = self.loss(logits.view(1, n_pad, -1), row_labels.view(1, n_pad), row_mask.view(1, n_pad))
         return {"output": None, "loss": loss, "output_rows": logits[:n], "rows": index}
 
-    def forward(self, x, labels=None, mask=None, rows=None):
+    def forward(self, x, labels=None, mask=None, rows=None, key_ranges=None):
+        """key_ranges ((N, 2), [k0, k1) per line): the keys the encoder layers attend to (backbone.encode_tokens); None: all, or with attend_valid_only
+        the hull of labels >= 0."""
+        key_ranges = self._ranges(x, labels, key_ranges)
         if self.head_rows == "masked" and self.training and labels is not None and mask is not None \
                 and getattr(self.loss, "unmasked_weight", None) is None:
-            result = self._forward_masked_rows(x, labels, mask, rows)
+            result = self._forward_masked_rows(x, labels, mask, rows, key_ranges)
             if result is not None:
                 return result
         elif self.head_rows not in ("all", "masked"):
@@ -249,7 +267,7 @@ class MaskedTransformerEncoder(torch.nn.Module):
             index = masked_row_list(mask, rows)
             if index is not None and index.numel() > 0:
                 n = x.shape[0]
-                tokens = self.backbone.encode_tokens(x, mask)
+                tokens = self.backbone.encode_tokens(x, mask, **ops.key_ranges_kw(key_ranges))
                 if not isinstance(mask, torch.Tensor):
                     mask = torch.from_numpy(np.asarray(mask))
                 if self.check_masked_rows:
@@ -257,7 +275,7 @@ class MaskedTransformerEncoder(torch.nn.Module):
                 logits, loss = _HeadCEFn.apply(tokens, self.head.linear.weight, self.head.linear.bias, torch.as_tensor(labels), mask,
                                                index.to(tokens.device, non_blocking=True), compute_dtype())
                 return {"output": logits.view(n, -1, logits.shape[-1]), "loss": loss}
-        output = self.encode(x, mask)
+        output = self.encode(x, mask, **ops.key_ranges_kw(key_ranges))
         if mask is not None and not isinstance(mask, torch.Tensor):
             mask = torch.from_numpy(mask).to(output.device)
         loss = None
@@ -265,9 +283,9 @@ class MaskedTransformerEncoder(torch.nn.Module):
             loss = self.loss(output, labels, mask)
         return {"output": output, "loss": loss}
 
-    def encode(self, images, mask=None):
+    def encode(self, images, mask=None, key_ranges=None):
         n = images.shape[0]
-        tokens = self.backbone.encode_tokens(images, mask)          # (N*S, d) row-major
+        tokens = self.backbone.encode_tokens(images, mask, **ops.key_ranges_kw(key_ranges))   # (N*S, d) row-major
         return self.head(tokens.view(n, -1, tokens.shape[-1]))     # == head(rearrange(backbone(x), 'n c w -> n w c'))
 
     def save(self, path):

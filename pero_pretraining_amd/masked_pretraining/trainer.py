@@ -107,7 +107,9 @@ class Trainer:
             # which layers keep their LayerNorm input rows (functional.ln_keep_rows) is baked into a captured graph: decided here, one graph each
             bb = self.model.backbone
             keep = F.ln_keep_rows(bb, torch.bfloat16 if self.bfloat16 else torch.float32)
-            key = tuple((tuple(t.shape), t.dtype) for t in tensors) + (self.model.training, keep)
+            # model.attend_valid_only works in a captured step: the key ranges are a device tensor computed INSIDE the graph from the static label
+            # buffer (ops.key_ranges_from_masks on a device tensor never synchronises); the attribute selects other kernels, so it is part of the key
+            key = tuple((tuple(t.shape), t.dtype) for t in tensors) + (self.model.training, keep, bool(getattr(self.model, "attend_valid_only", False)))
             bb.ln_keep_rows_pinned = keep
             try:
                 g = self._graphs.get(key)

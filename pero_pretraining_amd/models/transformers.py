@@ -62,12 +62,12 @@ class PositionalEncoding(torch.nn.Module):
 
 class _BackboneFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mod, x, mask, offsets, dtype, *params):
+    def forward(ctx, mod, x, mask, offsets, dtype, key_ranges, *params):
         save = any(ctx.needs_input_grad)
         if save:
             mod._grad_forwards = getattr(mod, "_grad_forwards", 0) + 1  # parallel.DataParallel overlaps only single-pass steps
         F.drop_row_grad_hint()   # (an announcement a failed or abandoned backward left behind must not meet this pass's gradient)
-        tokens, saved = F.backbone_fwd(mod, x, mask, offsets, dtype, save)
+        tokens, saved = F.backbone_fwd(mod, x, mask, offsets, dtype, save, key_ranges=key_ranges)
         ctx.mod, ctx.saved, ctx.dtype = mod, saved, dtype
         return tokens
 
@@ -79,7 +79,7 @@ class _BackboneFn(torch.autograd.Function):
         dt = dt.to(ctx.dtype).contiguous()
         F.backbone_bwd(ctx.mod, ctx.saved, dt, ctx.dtype, ctx.mod._on_layer_grads_ready, rows=rows)
         ctx.saved = None
-        return (None,) * (5 + len(ctx.mod._param_list))
+        return (None,) * (6 + len(ctx.mod._param_list))
 
 
 class TransformerEncoder(ABC, torch.nn.Module):
@@ -134,13 +134,26 @@ class TransformerEncoder(ABC, torch.nn.Module):
     def _param_list(self):
         return list(self.parameters())
 
-    def forward(self, x, mask=None):
-        tokens = self.encode_tokens(x, mask)
+    def forward(self, x, mask=None, key_ranges=None):
+        tokens = self.encode_tokens(x, mask, **ops.key_ranges_kw(key_ranges))
         n = x.shape[0]
         return tokens.view(n, -1, self.model_dim).permute(0, 2, 1)
 
-    def encode_tokens(self, x, mask=None):
-        """(N*S, model_dim) token rows (row-major, line-major)."""
+    def _key_ranges(self, key_ranges, n, device):
+        if key_ranges is None:
+            return None
+        kr = torch.as_tensor(key_ranges)
+        if kr.shape != (n, 2):
+            raise ValueError(f"key_ranges must have shape ({n}, 2), one [k0, k1) per line; got {tuple(kr.shape)}")
+        if not kr.is_cuda:   # known on the host: checked there (the kernels clamp what arrives on the device)
+            if bool((kr[:, 0] < 0).any() or (kr[:, 1] <= kr[:, 0]).any()):
+                raise ValueError("key_ranges: every line needs 0 <= k0 < k1")
+        return kr.to(device=device, dtype=torch.int32).contiguous()
+
+    def encode_tokens(self, x, mask=None, key_ranges=None):
+        """(N*S, model_dim) token rows (row-major, line-major).  key_ranges ((N, 2) integers, [k0, k1) per line; ops.key_ranges_from_masks): the layers'
+        attention takes these keys of a line only - torch's src_key_padding_mask for the padding of a collated batch; independent of `mask`, the
+        reference's masking of input columns.  Tokens at positions outside a line's range are still computed (from the line's valid keys)."""
         if not x.is_cuda:
             raise RuntimeError("pero_pretraining_amd backbones run on the GPU only (HIP kernels, no CPU fallback)")
         if x.dtype != torch.uint8 and mask is not None:
@@ -156,12 +169,13 @@ class TransformerEncoder(ABC, torch.nn.Module):
             mask = None
         w = x.shape[2] if x.dtype == torch.uint8 else x.shape[3]
         offsets = self.position_model.draw_offsets(x.shape[0], w // self.patch_size[1], x.device)
-        return _BackboneFn.apply(self, x, mask, offsets, compute_dtype(), *self._param_list)
+        return _BackboneFn.apply(self, x, mask, offsets, compute_dtype(), self._key_ranges(key_ranges, x.shape[0], x.device), *self._param_list)
 
-    def encode_tokens_views(self, views):
+    def encode_tokens_views(self, views, key_ranges=None):
         """Several equally shaped image batches (the two views of the joint-embedding step) through ONE pass of 2N lines:
         half the launches and twice the rows per product.  The positional offsets are drawn per view, in view order, with the
-        calls a sequence of separate encodes would make - the same device RNG stream as the reference's two encodes."""
+        calls a sequence of separate encodes would make - the same device RNG stream as the reference's two encodes.
+        key_ranges: one (N, 2) tensor per view (see encode_tokens), concatenated in view order."""
         if any(v.shape != views[0].shape or v.dtype != views[0].dtype for v in views):
             raise ValueError("encode_tokens_views: the views must have one shape and dtype")
         n, seq = views[0].shape[0], views[0].shape[-1 if views[0].dtype != torch.uint8 else 2] // self.patch_size[1]
@@ -171,7 +185,12 @@ class TransformerEncoder(ABC, torch.nn.Module):
         x = torch.empty((len(views) * n,) + tuple(views[0].shape[1:]), device=views[0].device, dtype=views[0].dtype)
         for k, v in enumerate(views):
             x[k * n:(k + 1) * n].copy_(v)
-        tokens = _BackboneFn.apply(self, x, None, offsets, compute_dtype(), *self._param_list)
+        kr = None
+        if key_ranges is not None:
+            if len(key_ranges) != len(views):
+                raise ValueError("encode_tokens_views: one key_ranges tensor per view")
+            kr = torch.cat([self._key_ranges(k, n, x.device) for k in key_ranges]).contiguous()
+        tokens = _BackboneFn.apply(self, x, None, offsets, compute_dtype(), kr, *self._param_list)
         return tokens  # (len(views) * N * S, model_dim): view v, line i at rows (v * N + i) * S ...
 
     def mask(self, x, mask):

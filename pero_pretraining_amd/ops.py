@@ -226,10 +226,17 @@ def bn_bwd(dy, x, y, weight, mean, rstd, dweight, dbias, relu):
     return dx
 
 
-def softmax_fwd(scores, scale, out_dtype):
+def softmax_fwd(scores, scale, out_dtype, key_ranges=None, rows_per_line=None):
+    """key_ranges (int32 (lines, 2), device): each row takes the keys [k0, k1) of its line (row // rows_per_line) only; p is exactly 0 outside."""
     rows, cols = scores.numel() // scores.shape[-1], scores.shape[-1]
     p = torch.empty(scores.shape, device=scores.device, dtype=out_dtype)
-    call("pero_softmax_fwd", ptr(scores), ptr(p), rows, cols, float(scale), dt(out_dtype), stream())
+    if key_ranges is None:
+        call("pero_softmax_fwd", ptr(scores), ptr(p), rows, cols, float(scale), dt(out_dtype), stream())
+    else:
+        if rows_per_line is None:
+            raise ValueError("softmax_fwd: key_ranges needs rows_per_line")
+        _check_key_ranges(key_ranges, rows // int(rows_per_line))
+        call("pero_softmax_fwd_keys", ptr(scores), ptr(key_ranges), ptr(p), rows, cols, int(rows_per_line), float(scale), dt(out_dtype), stream())
     return p
 
 
@@ -256,16 +263,66 @@ def attention_hd64_heads_per_block(n, s, h):
     return int(_lib.lib().pero_attention_hd64_heads_per_block(n, s, h))
 
 
-def attention_fwd_fused(qkv, n, s, h):
+def key_ranges_kw(key_ranges):
+    """The `key_ranges=` keyword of a call, or none at all without ranges: code that wraps or replaces the functions of this package with their signatures of
+    before (no such argument) keeps working as long as no ranges are in play."""
+    return {} if key_ranges is None else {"key_ranges": key_ranges}
+
+
+def _check_key_ranges(key_ranges, n):
+    if not (isinstance(key_ranges, torch.Tensor) and key_ranges.is_cuda and key_ranges.dtype == torch.int32 and key_ranges.shape == (n, 2) and
+            key_ranges.is_contiguous()):
+        raise ValueError(f"key_ranges must be a contiguous int32 device tensor of shape ({n}, 2) (ops.key_ranges_from_masks builds one)")
+
+
+def _hull_argmax(masks):
+    """[first, last + 1) of the positions equal to 1 per row of a 2-d tensor, by torch ops on the tensor's device (no host read)."""
+    v = (masks == 1).to(torch.uint8)
+    k0 = torch.argmax(v, dim=1)                      # argmax: the first of equal maxima
+    k1 = v.shape[1] - torch.argmax(v.flip(1), dim=1)
+    return torch.stack((k0, k1), dim=1).to(torch.int32).contiguous()
+
+
+def key_ranges_from_masks(masks, device=None):
+    """(N, S) mask, valid where it equals 1 (the collator's image_masks; `labels >= 0` of a masked-pretraining batch) -> int32 (N, 2) device tensor
+    [first valid position, last valid position + 1) per line: the `key_ranges` of the attention ops.  A device mask is reduced on the device without a
+    synchronisation (a line without a valid position comes out as [0, 1): the kernels' clamp of an empty range).  A mask known on the host (numpy array,
+    CPU tensor, list) is reduced there, and a line with no valid position or with a hole inside its hull raises ValueError; `device` says where it goes."""
+    if isinstance(masks, torch.Tensor) and masks.is_cuda:
+        if masks.dim() != 2:
+            raise ValueError("key_ranges_from_masks: the mask must be (N, S)")
+        return _hull_argmax(masks)
+    m = masks.numpy() if isinstance(masks, torch.Tensor) else np.asarray(masks)
+    if m.ndim != 2:
+        raise ValueError("key_ranges_from_masks: the mask must be (N, S)")
+    v = m == 1
+    cnt = v.sum(1)
+    if (cnt == 0).any():
+        raise ValueError(f"key_ranges_from_masks: line {int(np.argmax(cnt == 0))} has no valid position")
+    k0 = v.argmax(1)
+    k1 = m.shape[1] - v[:, ::-1].argmax(1)
+    if (k1 - k0 != cnt).any():
+        raise ValueError(f"key_ranges_from_masks: line {int(np.argmax(k1 - k0 != cnt))} has a hole inside its valid interval: only intervals are supported")
+    t = torch.from_numpy(np.stack((k0, k1), axis=1).astype(np.int32))
+    return t.to(device if device is not None else "cuda")
+
+
+def attention_fwd_fused(qkv, n, s, h, key_ranges=None):
+    """key_ranges (int32 (n, 2), device): line b attends to the keys [k0, k1) only (pero_attention_fwd_keys; clamped by the kernels)."""
     d = qkv.shape[1] // 3
     out = torch.empty((n * s, d), device=qkv.device, dtype=qkv.dtype)
     lse = torch.empty((n * h, s), device=qkv.device, dtype=torch.float32)
-    call("pero_attention_fwd", ptr(qkv), ptr(out), ptr(lse), n, s, h, d // h, dt(qkv), stream())
+    if key_ranges is None:
+        call("pero_attention_fwd", ptr(qkv), ptr(out), ptr(lse), n, s, h, d // h, dt(qkv), stream())
+    else:
+        _check_key_ranges(key_ranges, n)
+        call("pero_attention_fwd_keys", ptr(qkv), ptr(key_ranges), ptr(out), ptr(lse), n, s, h, d // h, dt(qkv), stream())
     return out, lse
 
 
-def attention_bwd_fused(qkv, out, dout, lse, n, s, h, dbias=None, dvec=None):
-    """dbias (f32 [3d], optional): in_proj's bias gradient (column sums of dqkv) is accumulated into it by the kernels.
+def attention_bwd_fused(qkv, out, dout, lse, n, s, h, dbias=None, dvec=None, key_ranges=None):
+    """key_ranges: those of the forward (pero_attention_bwd_keys: dK / dV rows outside a line's range are exact zeros).
+    dbias (f32 [3d], optional): in_proj's bias gradient (column sums of dqkv) is accumulated into it by the kernels.
     dvec (f32 [n*s][h], optional): D = per-head row sums of dout * out, already computed (then `out` is not read)."""
     d = qkv.shape[1] // 3
     dqkv = torch.empty_like(qkv)
@@ -274,8 +331,13 @@ def attention_bwd_fused(qkv, out, dout, lse, n, s, h, dbias=None, dvec=None):
     else:
         out = None
     work = torch.empty(3 * n * h * ((s + 127) // 128) * 128, device=qkv.device, dtype=torch.float32) if dbias is not None else None
-    call("pero_attention_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dvec), ptr(dqkv), ptr(dbias), ptr(work), n, s, h, d // h,
-         dt(qkv), stream())
+    if key_ranges is None:
+        call("pero_attention_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dvec), ptr(dqkv), ptr(dbias), ptr(work), n, s, h, d // h,
+             dt(qkv), stream())
+    else:
+        _check_key_ranges(key_ranges, n)
+        call("pero_attention_bwd_keys", ptr(qkv), ptr(key_ranges), ptr(out), ptr(dout), ptr(lse), ptr(dvec), ptr(dqkv), ptr(dbias), ptr(work), n, s, h,
+             d // h, dt(qkv), stream())
     return dqkv
 
 
