@@ -67,14 +67,13 @@ const char* pero_last_error(void);
 int pero_abi_version(void);
 /* tuning knobs for benchmarking and tests (defaults are the measured best; the one table: csrc/options.hpp): "gemm_policy" (0 = auto, 1 / 4 / 7 / 20 = force
  * one tile-kernel family, table in csrc/gemm.hip), "attn_bwd_pair" (1: the attention backward with D handed in runs as one launch, csrc/attention_bwd.hip),
- * "attn_pipe" (1: attention loops with software-pipelined inline-asm operand reads; 0: the compiler-scheduled loops - same bits), "attn_lh" (0; 1: S = 256
- * backward as one persistent workgroup per CU and (line, head) - same bits, not faster), "splitk_workspace" (1: the split-K
+ * "attn_order" (32: dispatch order of that launch's blocks; 0 = a unit's blocks side by side - same bits), "splitk_workspace" (1: the split-K
  * products of the eight-phase kernel leave partial tiles in the caller's `workspace`, summed in slice order by a second kernel - deterministic;
  * 0: f32 atomics even when a workspace is passed), "splitk_table" (1: unaligned slice counts hand their work items out XCD by XCD), "gemm_nw" (0; 1: stored
  * N = 512 products with a bias / residual epilogue run on the row-complete 128 x 512 tile that pero_gemm_resid_layernorm uses - same bits),
  * "gemm_e256_min" (192: stored products with at least that many 256x256 tiles take the eight-phase kernel; 0 = never), "gemm_e_splitk_min" (4),
  * "splitk_xcd" (1), "splitk_nearest" (0), "splitk_items" (512).  Process-wide; not meant to be changed while products are in flight.
- * "attn_pipe", "attn_bwd_pair", "attn_lh" and "attn_order" have no effect at head_dim 64: those kernels (csrc/attention_hd64.hip) have one form -
+ * "attn_bwd_pair" and "attn_order" have no effect at head_dim 64: those kernels (csrc/attention_hd64.hip) have one form -
  * compiler-scheduled loops, the dQ kernel then the dK / dV kernel whether D is computed or handed in. */
 int pero_set_option(const char* name, int value);
 
@@ -192,7 +191,7 @@ int pero_softmax_fwd_keys(const float* s, const int* key_ranges, void* p, int64_
  * out (N*S, nh*hd) = softmax(q k^T / sqrt(hd)) v per (line, head); lse (N*nh, S) f32 = base-2 log-sum-exp of the
  * scaled scores (kept for the backward kernels).  Scores never touch memory.  A line is cut into ceil(S/128) blocks of 128
  * rows; when S % 128 != 0 the last block is ragged: no address outside the line's S rows is read or written, and out,
- * lse, dvec and dqkv keep their unpadded shapes.  head_dim 128: csrc/attention_fwd.hip, attention_bwd.hip, attention_lh.hip; head_dim 64:
+ * lse, dvec and dqkv keep their unpadded shapes.  head_dim 128: csrc/attention_fwd.hip, attention_bwd.hip; head_dim 64:
  * csrc/attention_hd64.hip, same layouts.  Every other head_dim, and f32, is refused on the host before any launch (PERO_E_INVALID; the
  * message names the accepted widths): use the batched pero_gemm + pero_softmax_* path. */
 int pero_attention_fwd(const void* qkv, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads,
@@ -219,8 +218,8 @@ int pero_attention_bwd(const void* qkv, const void* out, const void* dout, const
  * the host, so the KERNELS clamp a bad range: k0 into [0, S - 1], then k1 into [k0 + 1, S] - an empty or inverted range means "the single
  * key k0".  Only intervals: no per-key masks, causal masks, biases or dropout.  The other arguments, the `out` / `dvec` conventions, the
  * dbias accumulation and the size of `work` are those of pero_attention_fwd / pero_attention_bwd.  A full range [0, S) on every line gives
- * the bits of the calls without ranges.  head_dim 128 always runs the pipelined ragged bodies (KEYS instantiations: csrc/attention_fwd.hip,
- * attention_bwd.hip), at every S and whatever "attn_pipe" / "attn_lh" say; key tiles without a live key are not visited. */
+ * the bits of the calls without ranges.  head_dim 128 runs the ragged bodies (KEYS instantiations: csrc/attention_fwd.hip,
+ * attention_bwd.hip) at every S; key tiles without a live key are not visited. */
 int pero_attention_fwd_keys(const void* qkv, const int* key_ranges, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads,
                             int64_t head_dim, int dtype, void* stream);
 int pero_attention_bwd_keys(const void* qkv, const int* key_ranges, const void* out, const void* dout, const float* lse, float* dvec,

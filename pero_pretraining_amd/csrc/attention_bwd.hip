@@ -1,15 +1,14 @@
-// Tiled backward of the fused attention (two workgroups of four waves per CU) and its launcher pero_attention_bwd, which also decides whether
-// the persistent kernel of attention_lh.hip runs instead.  Two bodies, each recomputing S^T / P from q, k and the saved base-2 log-sum-exp
-// (no S x S tensor is ever stored):
-//   attn_bwd_dq_body   : 128 queries of a (line, head), query on the lane, sweeps the keys in 32-key sub-tiles: S^T = K Q^T, dP^T = V dO^T,
-//                        dS^T = P^T (dP^T - D) scale, dQ^T += K^T dS^T.  Also writes D[q] = sum_d dO[q][d] O[q][d] for the other body
-//                        (unless D is handed in: `out` null).
-//   attn_bwd_dkv2_body : 128 keys, key on the lane, sweeps the queries in 32-query sub-tiles: S = Q K^T, P, dP = dO V^T, dS;
-//                        dV^T += dO^T P, dK^T += Q^T dS.
-// each compiler-scheduled and as `_p` with software-pipelined operand reads (attention_common.hpp; pero_set_option("attn_pipe"), same MFMAs
-// in the same order, same bits).  The `_p` bodies also have a RAGGED form for S % 128 != 0 (the three rules: attention_common.hpp), which the
-// launcher selects for every such S; the compiler-scheduled bodies and attn_bwd_lh_k take full tiles only.  Kernels: attn_bwd_dq_k<PIPE> then attn_bwd_dkv2_k<PIPE> (two launches: dq writes D), attn_bwd_pair_k<PIPE>
-// (both bodies in one launch when D is handed in), attn_bias_reduce_k.  No atomics in dqkv, deterministic; costs 7 MFMA products instead of
+// Tiled backward of the fused attention (two workgroups of four waves per CU) and its host side, attn_bwd_run behind pero_attention_bwd /
+// pero_attention_bwd_keys.  Two bodies, each recomputing S^T / P from q, k and the saved base-2 log-sum-exp (no S x S tensor is ever stored):
+//   attn_bwd_dq_body_p   : 128 queries of a (line, head), query on the lane, sweeps the keys in 32-key sub-tiles: S^T = K Q^T, dP^T = V dO^T,
+//                          dS^T = P^T (dP^T - D) scale, dQ^T += K^T dS^T.  Also writes D[q] = sum_d dO[q][d] O[q][d] for the other body
+//                          (unless D is handed in: `out` null).
+//   attn_bwd_dkv2_body_p : 128 keys, key on the lane, sweeps the queries in 32-query sub-tiles: S = Q K^T, P, dP = dO V^T, dS;
+//                          dV^T += dO^T P, dK^T += Q^T dS.
+// both with software-pipelined operand reads (attention_common.hpp), each instantiated for full tiles, RAGGED (S % 128 != 0, the three rules:
+// attention_common.hpp) and RAGGED with KEYS (per-line key ranges, at every S).  Kernels: attn_bwd_dq_k<RAGGED> then attn_bwd_dkv2_k<RAGGED> (two
+// launches: dq writes D), attn_bwd_pair_k<RAGGED> (both bodies in one launch when D is handed in), their three `_keys_k` forms, then
+// attn_bias_reduce_k<128> (attention_common.hpp).  No atomics in dqkv, deterministic; costs 7 MFMA products instead of
 // the minimal 5 (attention is ~8 % of the step's FLOPs).  All LDS tiles use the ONE dual-use image of attention_common.hpp.
 // Who waits for whom: every stage loop opens with vmcnt(0) + barrier (the stage has landed, every wave is done with the other buffer) and
 // issues the next stage's LDS-DMA right behind it, under the current stage's MFMAs; a global load issued in the loop goes out BEFORE the DMA
@@ -50,7 +49,7 @@ __device__ __forceinline__ void attn_store_tile(const f16v (&acc)[4], unsigned c
   }
   if (colsum) {
     // Column sums of the staged tile (this (line, head) block's share of in_proj's bias gradient) on the MATRIX pipe, which idles through
-    // the epilogue (as lh_store_matrix of attention_lh.hip does): wave w takes the 32 columns 32 w .., ones (32 x 16) times the 16 x 32 block of the
+    // the epilogue: wave w takes the 32 columns 32 w .., ones (32 x 16) times the 16 x 32 block of the
     // image read back TRANSPOSED (ds_read_b64_tr_b16: the row index becomes the MFMA's k - any order of the rows inside a k-step gives the
     // same sum), accumulated over the eight row blocks: every lane n then holds the sum of column 32 w + (n & 31), exact in f32, and writes
     // it - no cross-lane shuffles, no second pass through LDS, no barriers.  (As 128 vector adds + 16 shuffles per thread + an LDS
@@ -72,126 +71,13 @@ __device__ __forceinline__ void attn_store_tile(const f16v (&acc)[4], unsigned c
   }
 }
 
-// dbias[which * d + head * 128 + c] += sum over the workgroups (line, block) of partial[which][(lh, blk)][c], lh = line * nh + head.
-// Grid (heads, 3, slices of the workgroup list): one atomic per address and slice.  64 slices at >= 4096 workgroups per head (16 slices
-// were 192 blocks of two waves for 12.6 MB of partial rows: 37 us, latency-bound).
-__global__ __launch_bounds__(128) void attn_bias_reduce_k(const float* partial, float* dbias, int nlines, int nh, int nblk) {
-  const int c = threadIdx.x, head = blockIdx.x, which = blockIdx.y;
-  const long long nwg = (long long)nlines * nh * nblk;
-  const float* p = partial + (long long)which * nwg * 128;
-  const int per_head = nlines * nblk;  // workgroups of this head
-  const int chunk = (per_head + gridDim.z - 1) / gridDim.z;
-  const int i0 = blockIdx.z * chunk, i1 = i0 + chunk < per_head ? i0 + chunk : per_head;
-  // eight rows in flight per thread (two were 27 us for 25 MB of partial rows: one dependent load latency per pair)
-  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  auto at = [&](int i) -> float { return p[(((long long)(i / nblk) * nh + head) * nblk + i % nblk) * 128 + c]; };
-  int i = i0;
-  for (; i + 8 <= i1; i += 8) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) s[k] += at(i + k);
-  }
-  for (; i < i1; i++) s[0] += at(i);
-  if (i0 < i1) atomicAdd(dbias + (long long)which * nh * 128 + head * 128 + c, ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7])));
-}
-
-__device__ __forceinline__ void attn_bwd_dq_body(unsigned char* smem, int lh, int qb, const bf16raw* qkv, const bf16raw* out,
-                                                 const bf16raw* dout, const float* lse2, float* dvec, bf16raw* dqkv, float* dbias, int S,
-                                                 int nh, float c, float scale) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h5 = lane >> 5, r = lane & 31;
-  const int nqb = S >> 7;
-  const int line = lh / nh, head = lh % nh;
-  const long long d = (long long)nh * 128, ld = 3 * d;
-  const bf16raw* base = qkv + (long long)line * S * ld + head * 128;
-  const bf16raw* Kg = base + d;
-  const bf16raw* Vg = base + 2 * d;
-  const int q = qb * 128 + wave * 32 + r;
-
-  // K / V are staged in 64-key HALF tiles, double-buffered (2 x (16 + 16) KiB = the LDS of one 128-key tile pair before):
-  // the DMA of the next half runs under the current half's 48 MFMAs per wave.  With whole 128-key tiles and one buffer
-  // the DMA was issued after the tile's last read and waited for at the top of the next one - its whole latency exposed
-  // once per key tile, twice per workgroup at S = 256.
-  attn_glds_img<4>(Kg, ld, smem, wave, lane);
-  attn_glds_img<4>(Vg, ld, smem + AT_HALF_BYTES, wave, lane);
-
-  // D[q] = sum_d dO[q][d] O[q][d] (row sums of the output gradient times the output), layout dvec[(line*S + q)*nh + head]:
-  // either already there (out == nullptr: written by the epilogue of the product that produced dO, PERO_GEMM_ROWDOT) or
-  // computed here from the O rows and stored for the dK / dV kernel.
-  bf8v qf[8], gf[8];
-  float dsum = 0.f;
-  const long long dix = ((long long)line * S + q) * nh + head;
-  {
-    const bf16raw* qrow = base + (long long)q * ld + 8 * h5;
-    const bf16raw* grow = dout + ((long long)line * S + q) * d + head * 128 + 8 * h5;
-#pragma unroll
-    for (int ks = 0; ks < 8; ks++) {
-      qf[ks] = *(const bf8v*)(qrow + 16 * ks);
-      gf[ks] = *(const bf8v*)(grow + 16 * ks);
-    }
-    if (out) {
-      const bf16raw* orow = out + ((long long)line * S + q) * d + head * 128 + 8 * h5;
-#pragma unroll
-      for (int ks = 0; ks < 8; ks++) {
-        const bf8v of = *(const bf8v*)(orow + 16 * ks);
-#pragma unroll
-        for (int e = 0; e < 8; e++) dsum += (float)gf[ks][e] * (float)of[e];
-      }
-      dsum += __shfl_xor(dsum, 32, 64);
-      if (h5 == 0) dvec[dix] = dsum;
-    } else {
-      dsum = dvec[dix];
-    }
-  }
-  const float lq = lse2[(long long)lh * S + q];
-
-  f16v dq[4];
-#pragma unroll
-  for (int t = 0; t < 4; t++) dq[t] = (f16v){0};
-  const int nhalf = S >> 6;
-  for (int hk = 0; hk < nhalf; hk++) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // half hk landed; every wave is done with the other buffer
-    const unsigned char* kimg = smem + (hk & 1) * 2 * AT_HALF_BYTES;
-    const unsigned char* vimg = kimg + AT_HALF_BYTES;
-    if (hk + 1 < nhalf) {
-      unsigned char* nb = smem + ((hk + 1) & 1) * 2 * AT_HALF_BYTES;
-      attn_glds_img<4>(Kg + (long long)(hk + 1) * 64 * ld, ld, nb, wave, lane);
-      attn_glds_img<4>(Vg + (long long)(hk + 1) * 64 * ld, ld, nb + AT_HALF_BYTES, wave, lane);
-    }
-#pragma unroll
-    for (int t = 0; t < 2; t++) {  // 32-key sub-tile
-      f16v s = {0}, dp = {0};
-      AT_PRIO(1);
-#pragma unroll
-      for (int ks = 0; ks < 8; ks++) {
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_row_frag(kimg, t * 32 + r, ks, h5), qf[ks], s, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_row_frag(vimg, t * 32 + r, ks, h5), gf[ks], dp, 0, 0, 0);
-      }
-      AT_PRIO(0);
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const float p = __builtin_amdgcn_exp2f(fmaf(s[e], c, -lq));
-        s[e] = p * (dp[e] - dsum) * scale;  // dS^T
-      }
-      AT_PRIO(1);
-#pragma unroll
-      for (int sub = 0; sub < 2; sub++) {
-        const bf8v dsf = pack8(s, sub);
-#pragma unroll
-        for (int dt = 0; dt < 4; dt++)
-          dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_tr_frag(kimg, t * 32 + sub * 16, dt, lane), dsf, dq[dt], 0, 0, 0);
-      }
-      AT_PRIO(0);
-    }
-  }
-  // dbias: partial-sum workspace [3][workgroups][128] (q, k, v); this kernel fills plane 0
-  attn_store_tile(dq, smem, dqkv + ((long long)line * S + qb * 128) * ld + head * 128, ld,
-                  dbias ? dbias + ((long long)lh * nqb + qb) * 128 : nullptr, tid, wave, r, h5);
-}
-
-// ---- dQ body, pipelined reads.  Per 64-key half (one LDS stage pair): 48 fragments = 2 sub-tiles x (16 row fragments K0 V0 K1 V1 ... for
-// S^T / dP^T, then 8 transposed K fragments for dQ^T).  Fragment j is issued when fragment j - 7 has been consumed (pool of 8 registers
+// ---- dQ body.  K / V are staged in 64-key HALF tiles, double-buffered (2 x (16 + 16) KiB): the DMA of the next half runs under the current
+// half's 48 MFMAs per wave (whole 128-key tiles in one buffer exposed the DMA's latency once per key tile, twice per workgroup at S = 256).
+// Per 64-key half (one LDS stage pair): 48 fragments = 2 sub-tiles x (16 row fragments K0 V0 K1 V1 ... for S^T / dP^T, then 8 transposed K fragments for dQ^T).  Fragment j is issued when fragment j - 7 has been consumed (pool of 8 registers
 // sets), so at most 7 fragments (<= 14 LDS instructions) are in flight.
 #define DQ_DEPTH 7
+// LDS instructions of fragment j of a 64-key half (16 row fragments: one each, 8 transposed ones: two each)
+__device__ __forceinline__ constexpr int dq_ninstr(int j) { return (j % 24) < 16 ? 1 : 2; }
 __device__ __forceinline__ constexpr int dq_after(int j) {   // LDS instructions issued after fragment j's when it is consumed
   int n = 0;
   for (int k = j + 1; k <= j + DQ_DEPTH && k < 48; k++) n += dq_ninstr(k);
@@ -219,6 +105,9 @@ __device__ __forceinline__ void attn_bwd_dq_body_p(unsigned char* smem, int lh, 
   attn_glds_img<4, RAGGED>(Kg + (long long)h0 * 64 * ld, ld, smem, wave, lane, S - 1 - h0 * 64);
   attn_glds_img<4, RAGGED>(Vg + (long long)h0 * 64 * ld, ld, smem + AT_HALF_BYTES, wave, lane, S - 1 - h0 * 64);
 
+  // D[q] = sum_d dO[q][d] O[q][d] (row sums of the output gradient times the output), layout dvec[(line*S + q)*nh + head]:
+  // either already there (out == nullptr: written by the epilogue of the product that produced dO, PERO_GEMM_ROWDOT) or
+  // computed here from the O rows and stored for the dK / dV kernel.
   bf8v qf[8], gf[8];
   float dsum = 0.f;
   const long long dix = ((long long)line * S + qc) * nh + head;
@@ -345,16 +234,14 @@ __device__ __forceinline__ void attn_bwd_dq_body_p(unsigned char* smem, int lh, 
   attn_store_tile<RAGGED>(dq, smem, dqkv + ((long long)line * S + qb * 128) * ld + head * 128, ld,
                           dbias ? dbias + ((long long)lh * nqb + qb) * 128 : nullptr, tid, wave, r, h5, S - qb * 128);
 }
-// (RAGGED implies PIPE in all three kernels: the launcher sees to it)
-template <bool PIPE, bool RAGGED = false>
+template <bool RAGGED>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_k(const bf16raw* qkv, const bf16raw* out, const bf16raw* dout, const float* lse2,
                                                         float* dvec, bf16raw* dqkv, float* dbias, int S, int nh, float c, float scale) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int nqb = RAGGED ? (S + 127) >> 7 : S >> 7;
   int lh, qb;
   attn_block_map(blockIdx.x, nqb, gridDim.x / nqb, lh, qb);
-  if (PIPE) attn_bwd_dq_body_p<RAGGED>(smem, lh, qb, qkv, out, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
-  else attn_bwd_dq_body(smem, lh, qb, qkv, out, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
+  attn_bwd_dq_body_p<RAGGED>(smem, lh, qb, qkv, out, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
 }
 
 // dK and dV in ONE pass (4 products: S, dP, dV^T += dO^T P, dK^T += Q^T dS; key on the lane).  The two-launch form read
@@ -363,91 +250,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_k(const bf16raw* qkv, cons
 // was register-resident V next to register-resident K and two accumulator sets; here the workgroup's 128 x 128 V tile
 // lives in LDS (read as the B operand of dP) and Q / dO arrive in 32-query stages (8 + 8 KiB, double-buffered), so the
 // footprint stays at 64.5 KiB = two workgroups per CU.
-__device__ __forceinline__ void attn_bwd_dkv2_body(unsigned char* smem, int lh, int kb, long long nwg, const bf16raw* qkv, const bf16raw* dout,
-                                                   const float* lse2, const float* dvec, bf16raw* dqkv, float* dbias, int S, int nh, float c,
-                                                   float scale) {
-  unsigned char* vimg = smem + 4 * AT_SUB_BYTES;
-  float* lds_ld = (float*)(smem + 4 * AT_SUB_BYTES + AT_TILE_BYTES);  // [2 buffers][32 lse2 | 32 D]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h5 = lane >> 5, r = lane & 31;
-  const int nkb = S >> 7;
-  const int line = lh / nh, head = lh % nh;
-  const long long d = (long long)nh * 128, ld = 3 * d;
-  const bf16raw* base = qkv + (long long)line * S * ld + head * 128;
-  const bf16raw* Gg = dout + (long long)line * S * d + head * 128;
-  const int key = kb * 128 + wave * 32 + r;
-  // row statistics of a 32-query stage: threads 0-31 load lse2[lh][q], threads 32-63 load D[(line*S + q)*nh + head]
-  const float* stat = tid < 32 ? lse2 + (long long)lh * S + tid : dvec + ((long long)line * S + (tid & 31)) * nh + head;
-  const long long stat_step = tid < 32 ? 32 : 32LL * nh;
-
-  if (tid < 64) lds_ld[tid] = stat[0];
-  attn_glds_img<8>(base + 2 * d + (long long)kb * 128 * ld, ld, vimg, wave, lane);  // this workgroup's V tile, resident
-  attn_glds_img<2>(base, ld, smem, wave, lane);
-  attn_glds_img<2>(Gg, d, smem + AT_SUB_BYTES, wave, lane);
-
-  bf8v kf[8];
-  {
-    const bf16raw* krow = base + d + (long long)key * ld + 8 * h5;
-#pragma unroll
-    for (int ks = 0; ks < 8; ks++) kf[ks] = *(const bf8v*)(krow + 16 * ks);
-  }
-  f16v dv[4], dk[4];  // dV^T, dK^T: 32 d x 32 keys per tile, key on the lane
-#pragma unroll
-  for (int t = 0; t < 4; t++) { dv[t] = (f16v){0}; dk[t] = (f16v){0}; }
-  const int nsub = S >> 5;
-  for (int sq = 0; sq < nsub; sq++) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // stage sq (Q / dO rows + statistics) landed; every wave is done with the other buffers
-    const unsigned char* qimg = smem + (sq & 1) * 2 * AT_SUB_BYTES;
-    const unsigned char* gimg = qimg + AT_SUB_BYTES;
-    const float* lds_l = lds_ld + (sq & 1) * 64;
-    const float* lds_d = lds_l + 32;
-    float nstat = 0.f;
-    if (sq + 1 < nsub) {
-      if (tid < 64) nstat = stat[(sq + 1) * stat_step];  // before the DMA: vmcnt is in-order
-      unsigned char* nb = smem + ((sq + 1) & 1) * 2 * AT_SUB_BYTES;
-      attn_glds_img<2>(base + (long long)(sq + 1) * 32 * ld, ld, nb, wave, lane);
-      attn_glds_img<2>(Gg + (long long)(sq + 1) * 32 * d, d, nb + AT_SUB_BYTES, wave, lane);
-    }
-    // rows q = (e&3) + 8(e>>2) + 4*h5 of the 32-query stage on the registers, key on the lane
-    f16v s = {0}, dp = {0};
-    AT_PRIO(1);
-#pragma unroll
-    for (int ks = 0; ks < 8; ks++) {
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_row_frag(qimg, r, ks, h5), kf[ks], s, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_row_frag(gimg, r, ks, h5), img_row_frag(vimg, wave * 32 + r, ks, h5), dp, 0, 0, 0);
-    }
-    AT_PRIO(0);
-#pragma unroll
-    for (int g4 = 0; g4 < 4; g4++) {
-      const f4v l4 = *(const f4v*)(lds_l + 8 * g4 + 4 * h5);
-      const f4v d4 = *(const f4v*)(lds_d + 8 * g4 + 4 * h5);
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
-        const float p = __builtin_amdgcn_exp2f(fmaf(s[4 * g4 + e], c, -l4[e]));
-        s[4 * g4 + e] = p;                                         // P
-        dp[4 * g4 + e] = p * (dp[4 * g4 + e] - d4[e]) * scale;     // dS
-      }
-    }
-    AT_PRIO(1);
-#pragma unroll
-    for (int sub = 0; sub < 2; sub++) {
-      const bf8v pf = pack8(s, sub), dsf = pack8(dp, sub);
-#pragma unroll
-      for (int dt = 0; dt < 4; dt++) {
-        dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_tr_frag(gimg, sub * 16, dt, lane), pf, dv[dt], 0, 0, 0);   // dV^T += dO^T P
-        dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_tr_frag(qimg, sub * 16, dt, lane), dsf, dk[dt], 0, 0, 0);  // dK^T += Q^T dS
-      }
-    }
-    AT_PRIO(0);
-    if (sq + 1 < nsub && tid < 64) lds_ld[((sq + 1) & 1) * 64 + tid] = nstat;  // visible after the next barrier
-  }
-  bf16raw* tile_o = dqkv + ((long long)line * S + kb * 128) * ld + d + head * 128;  // dK tile; dV tile = + d columns
-  // planes 1 (dK) and 2 (dV) of the partial-sum workspace, nwg = (line, head) x key blocks entries each
-  attn_store_tile(dk, smem, tile_o, ld, dbias ? dbias + (nwg + (long long)lh * nkb + kb) * 128 : nullptr, tid, wave, r, h5);
-  attn_store_tile(dv, smem, tile_o + d, ld, dbias ? dbias + (2 * nwg + (long long)lh * nkb + kb) * 128 : nullptr, tid, wave, r, h5);
-}
-
-// ---- dK / dV body, pipelined reads.  Per 32-query stage: 24 row fragments (per ks: Q, dO, V) for S / dP, then the stage's row statistics
+// ---- dK / dV body.  Per 32-query stage: 24 row fragments (per ks: Q, dO, V) for S / dP, then the stage's row statistics
 // (compiler-visible LDS reads, issued while nothing else is in flight) and the exponentials, with the first transposed fragments of the
 // gradient products issued between the four groups of the arithmetic, then 16 transposed fragments (per (sub, dt): dO^T, Q^T).
 #ifndef DKV_POOL
@@ -625,15 +428,14 @@ __device__ __forceinline__ void attn_bwd_dkv2_body_p(unsigned char* smem, int lh
   attn_store_tile<RAGGED>(dk, smem, tile_o, ld, dbias ? dbias + (nwg + (long long)lh * nkb + kb) * 128 : nullptr, tid, wave, r, h5, S - kb * 128);
   attn_store_tile<RAGGED>(dv, smem, tile_o + d, ld, dbias ? dbias + (2 * nwg + (long long)lh * nkb + kb) * 128 : nullptr, tid, wave, r, h5, S - kb * 128);
 }
-template <bool PIPE, bool RAGGED = false>
+template <bool RAGGED>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv2_k(const bf16raw* qkv, const bf16raw* dout, const float* lse2, const float* dvec,
                                                           bf16raw* dqkv, float* dbias, int S, int nh, float c, float scale) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int nkb = RAGGED ? (S + 127) >> 7 : S >> 7;
   int lh, kb;
   attn_block_map(blockIdx.x, nkb, gridDim.x / nkb, lh, kb);
-  if (PIPE) attn_bwd_dkv2_body_p<RAGGED>(smem, lh, kb, gridDim.x, qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
-  else attn_bwd_dkv2_body(smem, lh, kb, gridDim.x, qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
+  attn_bwd_dkv2_body_p<RAGGED>(smem, lh, kb, gridDim.x, qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
 }
 // Both backward kernels as ONE launch (D already computed: `out` is not read, so no workgroup depends on another): the 2 x (S / 128)
 // workgroups of a (line, head) - its dQ blocks and its dK / dV blocks, which all read the same Q, K, V and dO rows - sit next to
@@ -663,20 +465,15 @@ __device__ __forceinline__ void attn_pair_map(int nb, int order, int& lh, int& b
     }
   }
 }
-template <bool PIPE, bool RAGGED = false>
+template <bool RAGGED>
 __global__ __launch_bounds__(256, 2) void attn_bwd_pair_k(const bf16raw* qkv, const bf16raw* dout, const float* lse2, float* dvec,
                                                           bf16raw* dqkv, float* dbias, int S, int nh, float c, float scale, int order) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int nb = RAGGED ? (S + 127) >> 7 : S >> 7;
   int lh, blk;
   attn_pair_map(nb, order, lh, blk);
-  if (blk < nb) {
-    if (PIPE) attn_bwd_dq_body_p<RAGGED>(smem, lh, blk, qkv, nullptr, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
-    else attn_bwd_dq_body(smem, lh, blk, qkv, nullptr, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
-  } else {
-    if (PIPE) attn_bwd_dkv2_body_p<RAGGED>(smem, lh, blk - nb, (long long)(gridDim.x >> 1), qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
-    else attn_bwd_dkv2_body(smem, lh, blk - nb, (long long)(gridDim.x >> 1), qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
-  }
+  if (blk < nb) attn_bwd_dq_body_p<RAGGED>(smem, lh, blk, qkv, nullptr, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
+  else attn_bwd_dkv2_body_p<RAGGED>(smem, lh, blk - nb, (long long)(gridDim.x >> 1), qkv, dout, lse2, dvec, dqkv, dbias, S, nh, c, scale);
 }
 // ---- the three launches with per-line key ranges: the KEYS instantiations of the pipelined ragged bodies
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_keys_k(const bf16raw* qkv, const int* kr, const bf16raw* out, const bf16raw* dout, const float* lse2,
@@ -706,97 +503,66 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pair_keys_k(const bf16raw* qk
 }
 
 constexpr int AT_PAIR_LDS = AT_DKV2_LDS > 2 * AT_TILE_BYTES ? AT_DKV2_LDS : 2 * AT_TILE_BYTES;   // a paired workgroup runs either body
-extern "C" int pero_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
-                                  float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim, int dtype,
-                                  void* stream) {
-  PERO_REQUIRE(qkv && dout && lse && dvec && dqkv, "pero_attention_bwd: null pointer");
-  PERO_REQUIRE(dtype == PERO_BF16 && (head_dim == 64 || head_dim == 128) && S > 0 && N > 0 && num_heads > 0,
-               "pero_attention_bwd: fused kernel needs bf16, head_dim 64 or 128, S > 0 (got hd=%lld S=%lld)", (long long)head_dim, (long long)S);
-  PERO_REQUIRE(aligned16(qkv) && (!out || aligned16(out)) && aligned16(dout) && aligned16(dqkv), "pero_attention_bwd: 16-byte alignment");
-  PERO_REQUIRE(!dbias || work, "pero_attention_bwd: dbias needs the partial-sum workspace");
-  if (head_dim == 64) {   // attention_hd64.hip: the same two kernels whether D is computed here or handed in
-    attn64_bwd_launch(qkv, out, dout, lse, dvec, dqkv, dbias, work, N, S, num_heads, (hipStream_t)stream);
-    PERO_CHECK_LAUNCH("pero_attention_bwd");
-    return PERO_OK;
-  }
-  static const bool lds_attrs_once = [] {
-    const struct { const void* kernel; int bytes; } attrs[] = {
-        {(const void*)attn_bwd_dq_k<false>, 2 * AT_TILE_BYTES}, {(const void*)attn_bwd_dq_k<true>, 2 * AT_TILE_BYTES},
-        {(const void*)attn_bwd_dkv2_k<false>, AT_DKV2_LDS},     {(const void*)attn_bwd_dkv2_k<true>, AT_DKV2_LDS},
-        {(const void*)attn_bwd_pair_k<false>, AT_PAIR_LDS},     {(const void*)attn_bwd_pair_k<true>, AT_PAIR_LDS},
-        {(const void*)attn_bwd_dq_k<true, true>, 2 * AT_TILE_BYTES}, {(const void*)attn_bwd_dkv2_k<true, true>, AT_DKV2_LDS},
-        {(const void*)attn_bwd_pair_k<true, true>, AT_PAIR_LDS}};
-    for (const auto& a : attrs) hipFuncSetAttribute(a.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, a.bytes);
-    return true;
-  }();
-  (void)lds_attrs_once;
-  const float scale = (float)(1.0 / sqrt((double)head_dim));
-  const float c = (float)(1.4426950408889634 / sqrt((double)head_dim));
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t nb = (S + 127) / 128;   // query blocks = key blocks of a line; the last one is ragged when S % 128 != 0
-  const bool ragged = S % 128 != 0;     // then the RAGGED instantiations of the pipelined bodies run, whatever "attn_pipe" says
-  dim3 grid((unsigned)(N * num_heads * nb)), block(256);
-  if (!out && g_opt.attn_bwd_pair && g_opt.attn_lh && S == 256 && dbias && N * num_heads < (1LL << 20) && num_heads <= 1024) {   // (32-bit byte offsets inside a unit and inside the partial-sum workspace)
-    // one persistent workgroup per CU, a (line, head) per pass (attn_bwd_lh_k); its bias partials: one row per unit
-    // ("attn_lh", off: same bits; measured 735-745 us against 725-735 us of the paired kernels at 1024 lines)
-    attn_bwd_lh_launch(qkv, dout, lse, dvec, dqkv, work, N, num_heads, c, scale, st);
-    hipLaunchKernelGGL(attn_bias_reduce_k, dim3((unsigned)num_heads, 3, N >= 4096 ? 128 : N >= 1024 ? 64 : 16), dim3(128), 0, st, work, dbias, (int)N, (int)num_heads, 1);
-    PERO_CHECK_LAUNCH("pero_attention_bwd");
-    return PERO_OK;
-  }
-  const bool pipe = g_opt.attn_pipe != 0;   // selects each kernel, once
-  const bf16raw *q_ = (const bf16raw*)qkv, *o_ = (const bf16raw*)out, *g_ = (const bf16raw*)dout;
-  bf16raw* dq_ = (bf16raw*)dqkv;
-  float* const part = dbias ? work : nullptr;   // the partial-sum workspace of the bias gradient
-  if (!out && g_opt.attn_bwd_pair) {
-    hipLaunchKernelGGL((ragged ? attn_bwd_pair_k<true, true> : pipe ? attn_bwd_pair_k<true> : attn_bwd_pair_k<false>), dim3(2 * grid.x), block, AT_PAIR_LDS, st, q_, g_, lse, dvec, dq_, part,
-                       (int)S, (int)num_heads, c, scale, g_opt.attn_order);
-  } else {
-    hipLaunchKernelGGL((ragged ? attn_bwd_dq_k<true, true> : pipe ? attn_bwd_dq_k<true> : attn_bwd_dq_k<false>), grid, block, 2 * AT_TILE_BYTES, st, q_, o_, g_, lse, dvec, dq_, part,
-                       (int)S, (int)num_heads, c, scale);
-    hipLaunchKernelGGL((ragged ? attn_bwd_dkv2_k<true, true> : pipe ? attn_bwd_dkv2_k<true> : attn_bwd_dkv2_k<false>), grid, block, AT_DKV2_LDS, st, q_, g_, lse, dvec, dq_, part,
-                       (int)S, (int)num_heads, c, scale);
-  }
-  if (dbias)
-    hipLaunchKernelGGL(attn_bias_reduce_k, dim3((unsigned)num_heads, 3, (N * nb >= 4096) ? 128 : (N * nb >= 1024) ? 64 : 16), dim3(128), 0, st, work, dbias, (int)N, (int)num_heads, (int)nb);
-  PERO_CHECK_LAUNCH("pero_attention_bwd");
-  return PERO_OK;
-}
 
-// The same with per-line key ranges (include/pero_hip.h): always the KEYS instantiations of the pipelined ragged bodies - two launches when D is computed
-// here, the paired launch when it is handed in - at every S and whatever "attn_pipe", "attn_lh" say; "attn_order" only orders the paired dispatch.
-extern "C" int pero_attention_bwd_keys(const void* qkv, const int* key_ranges, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
-                                       float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim, int dtype, void* stream) {
-  PERO_REQUIRE(qkv && key_ranges && dout && lse && dvec && dqkv, "pero_attention_bwd_keys: null pointer");
+// One host path for both entry points (`who` prefixes the error texts; key_ranges null: none): validate, dispatch on head_dim, launch - two
+// launches when D is computed here (`out` given) or "attn_bwd_pair" is 0, the paired launch otherwise ("attn_order" orders its dispatch) -, reduce
+// the bias gradient, check.  Key ranges run the KEYS instantiations (ragged bodies) at every S.
+static int attn_bwd_run(const char* who, const void* qkv, const int* key_ranges /* null: none */, const void* out, const void* dout, const float* lse,
+                        float* dvec, void* dqkv, float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim, int dtype,
+                        hipStream_t st) {
+  PERO_REQUIRE(qkv && dout && lse && dvec && dqkv, "%s: null pointer", who);
   PERO_REQUIRE(dtype == PERO_BF16 && (head_dim == 64 || head_dim == 128) && S > 0 && N > 0 && num_heads > 0,
-               "pero_attention_bwd_keys: fused kernel needs bf16, head_dim 64 or 128, S > 0 (got hd=%lld S=%lld)", (long long)head_dim, (long long)S);
-  PERO_REQUIRE(aligned16(qkv) && (!out || aligned16(out)) && aligned16(dout) && aligned16(dqkv), "pero_attention_bwd_keys: 16-byte alignment");
-  PERO_REQUIRE(!dbias || work, "pero_attention_bwd_keys: dbias needs the partial-sum workspace");
-  hipStream_t st = (hipStream_t)stream;
-  if (head_dim == 64) {   // attention_hd64.hip
-    attn64_bwd_keys_launch(qkv, key_ranges, out, dout, lse, dvec, dqkv, dbias, work, N, S, num_heads, st);
-    PERO_CHECK_LAUNCH("pero_attention_bwd_keys");
+               "%s: fused kernel needs bf16, head_dim 64 or 128, S > 0 (got hd=%lld S=%lld)", who, (long long)head_dim, (long long)S);
+  PERO_REQUIRE(aligned16(qkv) && (!out || aligned16(out)) && aligned16(dout) && aligned16(dqkv), "%s: 16-byte alignment", who);
+  PERO_REQUIRE(!dbias || work, "%s: dbias needs the partial-sum workspace", who);
+  if (head_dim == 64) {   // attention_hd64.hip: the same two kernels whether D is computed here or handed in
+    attn64_bwd_launch(qkv, key_ranges, out, dout, lse, dvec, dqkv, dbias, work, N, S, num_heads, st);
+    PERO_CHECK_LAUNCH(who);
     return PERO_OK;
   }
+  PERO_LDS_ATTR(attn_bwd_dq_k<false>, 2 * AT_TILE_BYTES);
+  PERO_LDS_ATTR(attn_bwd_dq_k<true>, 2 * AT_TILE_BYTES);
   PERO_LDS_ATTR(attn_bwd_dq_keys_k, 2 * AT_TILE_BYTES);
+  PERO_LDS_ATTR(attn_bwd_dkv2_k<false>, AT_DKV2_LDS);
+  PERO_LDS_ATTR(attn_bwd_dkv2_k<true>, AT_DKV2_LDS);
   PERO_LDS_ATTR(attn_bwd_dkv2_keys_k, AT_DKV2_LDS);
+  PERO_LDS_ATTR(attn_bwd_pair_k<false>, AT_PAIR_LDS);
+  PERO_LDS_ATTR(attn_bwd_pair_k<true>, AT_PAIR_LDS);
   PERO_LDS_ATTR(attn_bwd_pair_keys_k, AT_PAIR_LDS);
   const float scale = (float)(1.0 / sqrt((double)head_dim));
   const float c = (float)(1.4426950408889634 / sqrt((double)head_dim));
-  const int64_t nb = (S + 127) / 128;
-  dim3 grid((unsigned)(N * num_heads * nb)), block(256);
+  const int64_t nb = (S + 127) / 128;   // query blocks = key blocks of a line; the last one is ragged when S % 128 != 0
+  const bool ragged = S % 128 != 0;
+  const dim3 grid((unsigned)(N * num_heads * nb)), block(256);
   const bf16raw *q_ = (const bf16raw*)qkv, *o_ = (const bf16raw*)out, *g_ = (const bf16raw*)dout;
   bf16raw* dq_ = (bf16raw*)dqkv;
-  float* const part = dbias ? work : nullptr;
+  float* const part = dbias ? work : nullptr;   // the partial-sum workspace of the bias gradient
+  const int s_ = (int)S, nh_ = (int)num_heads;
   if (!out && g_opt.attn_bwd_pair) {
-    hipLaunchKernelGGL(attn_bwd_pair_keys_k, dim3(2 * grid.x), block, AT_PAIR_LDS, st, q_, key_ranges, g_, lse, dvec, dq_, part, (int)S, (int)num_heads, c, scale,
-                       g_opt.attn_order);
+    const dim3 grid2(2 * grid.x);
+    if (key_ranges) hipLaunchKernelGGL(attn_bwd_pair_keys_k, grid2, block, AT_PAIR_LDS, st, q_, key_ranges, g_, lse, dvec, dq_, part, s_, nh_, c, scale, g_opt.attn_order);
+    else hipLaunchKernelGGL((ragged ? attn_bwd_pair_k<true> : attn_bwd_pair_k<false>), grid2, block, AT_PAIR_LDS, st, q_, g_, lse, dvec, dq_, part, s_, nh_, c, scale, g_opt.attn_order);
+  } else if (key_ranges) {
+    hipLaunchKernelGGL(attn_bwd_dq_keys_k, grid, block, 2 * AT_TILE_BYTES, st, q_, key_ranges, o_, g_, lse, dvec, dq_, part, s_, nh_, c, scale);
+    hipLaunchKernelGGL(attn_bwd_dkv2_keys_k, grid, block, AT_DKV2_LDS, st, q_, key_ranges, g_, lse, dvec, dq_, part, s_, nh_, c, scale);
   } else {
-    hipLaunchKernelGGL(attn_bwd_dq_keys_k, grid, block, 2 * AT_TILE_BYTES, st, q_, key_ranges, o_, g_, lse, dvec, dq_, part, (int)S, (int)num_heads, c, scale);
-    hipLaunchKernelGGL(attn_bwd_dkv2_keys_k, grid, block, AT_DKV2_LDS, st, q_, key_ranges, g_, lse, dvec, dq_, part, (int)S, (int)num_heads, c, scale);
+    hipLaunchKernelGGL((ragged ? attn_bwd_dq_k<true> : attn_bwd_dq_k<false>), grid, block, 2 * AT_TILE_BYTES, st, q_, o_, g_, lse, dvec, dq_, part, s_, nh_, c, scale);
+    hipLaunchKernelGGL((ragged ? attn_bwd_dkv2_k<true> : attn_bwd_dkv2_k<false>), grid, block, AT_DKV2_LDS, st, q_, g_, lse, dvec, dq_, part, s_, nh_, c, scale);
   }
-  if (dbias)
-    hipLaunchKernelGGL(attn_bias_reduce_k, dim3((unsigned)num_heads, 3, (N * nb >= 4096) ? 128 : (N * nb >= 1024) ? 64 : 16), dim3(128), 0, st, work, dbias, (int)N, (int)num_heads, (int)nb);
-  PERO_CHECK_LAUNCH("pero_attention_bwd_keys");
+  if (dbias) attn_bias_reduce_launch<128>(work, dbias, N, num_heads, nb, st);
+  PERO_CHECK_LAUNCH(who);
   return PERO_OK;
+}
+
+extern "C" int pero_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
+                                  float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim, int dtype,
+                                  void* stream) {
+  return attn_bwd_run("pero_attention_bwd", qkv, nullptr, out, dout, lse, dvec, dqkv, dbias, work, N, S, num_heads, head_dim, dtype, (hipStream_t)stream);
+}
+
+// The same with per-line key ranges (include/pero_hip.h)
+extern "C" int pero_attention_bwd_keys(const void* qkv, const int* key_ranges, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
+                                       float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, int64_t head_dim, int dtype, void* stream) {
+  PERO_REQUIRE(key_ranges, "pero_attention_bwd_keys: null pointer");
+  return attn_bwd_run("pero_attention_bwd_keys", qkv, key_ranges, out, dout, lse, dvec, dqkv, dbias, work, N, S, num_heads, head_dim, dtype, (hipStream_t)stream);
 }

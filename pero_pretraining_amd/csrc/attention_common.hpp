@@ -1,17 +1,18 @@
-// What the three attention kernel families share: the forward (attention_fwd.hip), the tiled backward (attention_bwd.hip) and the persistent
-// (line, head) backward (attention_lh.hip).  Fused multi-head attention for the encoder layers (torch SDPA inside
+// What the attention kernel families share: the forward (attention_fwd.hip) and the tiled backward (attention_bwd.hip) at head_dim 128; the
+// head_dim-64 kernels (attention_hd64.hip) take the key ranges, the block map and the bias reduction from here.  Fused multi-head attention for the encoder layers (torch SDPA inside
 // TransformerEncoderLayer._sa_block, reference models/transformers.py:36-43,86): softmax(q k^T / sqrt(hd)) v over all S keys of a line - or,
 // opt-in, over one interval of keys per line (KEYS: "Per-line key ranges" below); bf16, head_dim 128, any S >= 1, operating directly on the packed qkv (N*S, 3d) tensor.
+// Each kernel has ONE body (attn_fwd_p_body, attn_bwd_dq_body_p, attn_bwd_dkv2_body_p: software-pipelined operand reads, below) in up to three
+// instantiations: full tiles, RAGGED, and RAGGED with KEYS.
 // Ragged S (S % 128 != 0): a line has nb = ceil(S / 128) query blocks and key tiles, the last one with S - 128 (nb - 1) rows.  The launchers then
-// start the RAGGED = true instantiations of the PIPELINED bodies (attn_fwd_p_k, attn_bwd_dq_body_p, attn_bwd_dkv2_body_p) whatever "attn_pipe"
-// says - the compiler-scheduled bodies have no ragged form - under three rules: (1) every row index that feeds a global address is clamped to
+// start the RAGGED = true instantiations under three rules: (1) every row index that feeds a global address is clamped to
 // the line's last row (the LDS-DMA source rows here, the Q / dO / O / lse / D reads in the bodies), so a tail row holds a copy of a real row and
 // every MFMA operand is finite; (2) P is SELECTED to 0 wherever the key >= S or the query >= S; (3) every row store is guarded by row < S.
-// S % 128 == 0 starts RAGGED = false: the code of before, bit for bit.
+// S % 128 == 0 starts RAGGED = false: no clamp, no select, no guard.
 // In this header: the AT_* sizes; the LDS-DMA tile loaders and the fragment reads of the forward's K and V images and of the backward's
 // dual-use image (img_f); the workgroup -> ((line, head), block) map; the software-pipelining helpers (at_*: operand reads by inline asm, each
-// MFMA tied to a counted lgkmcnt); those asm wrappers of the persistent backward (lh_*) that the pipelined forward uses too; the declaration of
-// attention_lh.hip's launcher, which pero_attention_bwd (attention_bwd.hip) calls.
+// MFMA tied to a counted lgkmcnt; the forward's asm vector-memory and LDS wrappers); the reduction of the bias gradient's partial rows; the
+// declarations of attention_hd64.hip's launchers.
 #pragma once
 #include "common.hpp"
 #include "options.hpp"
@@ -134,15 +135,16 @@ __device__ __forceinline__ void attn_block_map(int bid, int nblk, int nlh, int& 
   }
 }
 
-// ---- Software-pipelined operand reads.  hipcc compiles the plain loops (attn_fwd_k, attn_bwd_dq_body, attn_bwd_dkv2_body) to  read -> s_waitcnt
+// ---- Software-pipelined operand reads.  hipcc compiles the same loops written with plain LDS reads (the head_dim-64 kernels still are; the
+// head_dim-128 forms of that kind were retired) to  read -> s_waitcnt
 // lgkmcnt(0) -> MFMA  pairs - one LDS round trip exposed per one or two 32-cycle MFMAs - and, worse, puts an `s_waitcnt vmcnt(0)` in front of
 // the first LDS read that follows an LDS-DMA (it cannot tell the DMA's destination from the tile being read), which makes the "prefetch" of
-// the next tile a wait in the middle of the current one (an ablation build: the loop's DMA cost 24 % of the backward).  The pipelined bodies
-// (attn_fwd_p_k, attn_bwd_dq_body_p, attn_bwd_dkv2_body_p, attn_bwd_lh_k) issue every fragment read by inline asm the compiler neither waits
+// the next tile a wait in the middle of the current one (an ablation build: the loop's DMA cost 24 % of the backward).  The bodies
+// (attn_fwd_p_body, attn_bwd_dq_body_p, attn_bwd_dkv2_body_p) issue every fragment read by inline asm the compiler neither waits
 // for nor orders, up to SEVEN fragments ahead of the MFMA that consumes them, each MFMA tied to a counted `s_waitcnt lgkmcnt(n)` through its
 // fragment register (LDS operations retire in order, so n = the LDS instructions issued after the fragment's own).  One sequence of reads runs
 // through a whole LDS stage: the transposed fragments of the gradient products are in flight while the exponentials run, the next sub-tile's
-// row fragments while the gradient products run.  Same MFMAs in the same order: results are bit-identical to the plain bodies.
+// row fragments while the gradient products run.  Same MFMAs in the same order as the plain loops.
 template <int I, int N, typename F>
 __device__ __forceinline__ void at_static_for(F&& f) {
   if constexpr (I < N) {
@@ -211,59 +213,77 @@ __device__ __forceinline__ void at_wait_lgkm2(T& f, T& g) {
   static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
   asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(f), "+v"(g) : "i"(N) : "memory");
 }
-// LDS instructions of fragment j of a 64-key half of the dQ sequence (48 fragments = 2 sub-tiles x (16 row fragments, 8 transposed ones)):
-// attn_bwd_dq_body_p and phase Q of attn_bwd_lh_k count their waits with it
-__device__ __forceinline__ constexpr int dq_ninstr(int j) { return (j % 24) < 16 ? 1 : 2; }
 
-// ---- asm vector-memory and LDS wrappers that both the pipelined forward and attn_bwd_lh_k use (the rest of the lh_* family: attention_lh.hip)
+// ---- asm vector-memory and LDS wrappers of the forward: loads and stores the compiler neither waits for nor orders.
 // Every asm vector-memory instruction that takes an SGPR base opens with wait states: a v_readlane_b32 / v_readfirstlane_b32 that has
 // just (re)written the SGPR - a restored spill - needs five of them before a vector-memory instruction reads it, and the compiler pads that
 // hazard for its own instructions only (gemm_e_common.hpp's E_BSTORE16 once took stale row offsets that way; tools/check_async_loads.py
 // checks the ISA of these kernels too: tests/test_cabi_and_host.py).
 template <int IMM, typename T>
-__device__ __forceinline__ void lh_gload16(T& d, const void* sbase, unsigned voff) {
+__device__ __forceinline__ void at_gload16(T& d, const void* sbase, unsigned voff) {
   static_assert(sizeof(T) == 16 && IMM >= 0 && IMM < 4096, "global_load_dwordx4");
   asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(d) : "v"(voff), "s"(sbase), "i"(IMM) : "memory");
 }
 // (the trailing wait states: the data registers are rewritten right behind the store - see E_BSTORE16 in gemm_e_common.hpp)
 template <int IMM, typename T>
-__device__ __forceinline__ void lh_gstore16(const T& v, void* sbase, unsigned voff) {
+__device__ __forceinline__ void at_gstore16(const T& v, void* sbase, unsigned voff) {
   static_assert(sizeof(T) == 16 && IMM >= 0 && IMM < 4096, "global_store_dwordx4");
   asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 2" :: "v"(voff), "v"(v), "s"(sbase), "i"(IMM) : "memory");
 }
-__device__ __forceinline__ void lh_gstore4(float v, void* sbase, unsigned voff) {
+__device__ __forceinline__ void at_gstore4(float v, void* sbase, unsigned voff) {
   asm volatile("s_nop 4\n\tglobal_store_dword %0, %1, %2\n\ts_nop 2" :: "v"(voff), "v"(v), "s"(sbase) : "memory");
 }
-__device__ __forceinline__ void lh_barrier() {
+__device__ __forceinline__ void at_barrier() {
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("s_barrier" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
 }
 template <typename T>
-__device__ __forceinline__ void lh_ds_write8(unsigned addr, const T& v) {
+__device__ __forceinline__ void at_ds_write8(unsigned addr, const T& v) {
   static_assert(sizeof(T) == 8, "ds_write_b64");
   asm volatile("ds_write_b64 %0, %1" :: "v"(addr), "v"(v) : "memory");
 }
 template <typename T>
-__device__ __forceinline__ void lh_ds_read16(T& d, unsigned addr) {
+__device__ __forceinline__ void at_ds_read16(T& d, unsigned addr) {
   static_assert(sizeof(T) == 16, "ds_read_b128");
   asm volatile("ds_read_b128 %0, %1" : "=v"(d) : "v"(addr) : "memory");
 }
 template <int N>
-__device__ __forceinline__ void lh_wait_lgkm_plain() {
+__device__ __forceinline__ void at_wait_lgkm_plain() {
   asm volatile("s_waitcnt lgkmcnt(%0)" :: "i"(N) : "memory");
 }
 
-// attention_lh.hip: sets the LDS attribute of attn_bwd_lh_k, sizes its grid (one persistent workgroup per CU, at most one per (line, head))
-// and launches it; the caller checks the launch
-__attribute__((visibility("hidden"))) void attn_bwd_lh_launch(const void* qkv, const void* dout, const float* lse, const float* dvec, void* dqkv,
-                                                              float* work, int64_t N, int64_t num_heads, float c, float scale, hipStream_t st);
+// ---- Bias gradient.  The backward kernels leave partial[which][(lh, blk)][HD] (which = q, k, v; lh = line * nh + head): the column sums of each workgroup's
+// output tile.  dbias[which * d + head * HD + c] += their sum over the workgroups (line, block) of a head.
+// Grid (heads, 3, slices of the workgroup list): one atomic per address and slice.  64 slices at >= 4096 workgroups per head (16 slices
+// were 192 blocks of two waves for 12.6 MB of partial rows: 37 us, latency-bound).
+template <int HD>
+__global__ __launch_bounds__(HD) void attn_bias_reduce_k(const float* partial, float* dbias, int nlines, int nh, int nblk) {
+  const int c = threadIdx.x, head = blockIdx.x, which = blockIdx.y;
+  const long long nwg = (long long)nlines * nh * nblk;
+  const float* p = partial + (long long)which * nwg * HD;
+  const int per_head = nlines * nblk;  // workgroups of this head
+  const int chunk = (per_head + gridDim.z - 1) / gridDim.z;
+  const int i0 = blockIdx.z * chunk, i1 = i0 + chunk < per_head ? i0 + chunk : per_head;
+  // eight rows in flight per thread (two were 27 us for 25 MB of partial rows: one dependent load latency per pair)
+  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  auto at = [&](int i) -> float { return p[(((long long)(i / nblk) * nh + head) * nblk + i % nblk) * HD + c]; };
+  int i = i0;
+  for (; i + 8 <= i1; i += 8) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) s[k] += at(i + k);
+  }
+  for (; i < i1; i++) s[0] += at(i);
+  if (i0 < i1) atomicAdd(dbias + (long long)which * nh * HD + head * HD + c, ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7])));
+}
+template <int HD>
+static inline void attn_bias_reduce_launch(const float* partial, float* dbias, int64_t N, int64_t num_heads, int64_t nb, hipStream_t st) {
+  const unsigned slices = (N * nb >= 4096) ? 128 : (N * nb >= 1024) ? 64 : 16;
+  hipLaunchKernelGGL(attn_bias_reduce_k<HD>, dim3((unsigned)num_heads, 3, slices), dim3(HD), 0, st, partial, dbias, (int)N, (int)num_heads, (int)nb);
+}
 
-// attention_hd64.hip: the head_dim-64 kernels (compiler-scheduled, any S >= 1, one head per workgroup).  pero_attention_fwd / pero_attention_bwd
-// validate the arguments, dispatch on head_dim and check the launch.
-__attribute__((visibility("hidden"))) void attn64_fwd_launch(const void* qkv, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads, hipStream_t st);
-__attribute__((visibility("hidden"))) void attn64_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
+// attention_hd64.hip: the head_dim-64 kernels (compiler-scheduled, any S >= 1); kr null: no key ranges.  attn_fwd_run / attn_bwd_run
+// (attention_fwd.hip, attention_bwd.hip) validate the arguments, dispatch on head_dim and check the launch.
+__attribute__((visibility("hidden"))) void attn64_fwd_launch(const void* qkv, const int* kr, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads, hipStream_t st);
+__attribute__((visibility("hidden"))) void attn64_bwd_launch(const void* qkv, const int* kr, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
                                                              float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, hipStream_t st);
-__attribute__((visibility("hidden"))) void attn64_fwd_keys_launch(const void* qkv, const int* kr, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads, hipStream_t st);
-__attribute__((visibility("hidden"))) void attn64_bwd_keys_launch(const void* qkv, const int* kr, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv,
-                                                                  float* dbias, float* work, int64_t N, int64_t S, int64_t num_heads, hipStream_t st);

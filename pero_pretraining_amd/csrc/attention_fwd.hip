@@ -1,7 +1,7 @@
-// Forward of the fused attention: attn_fwd_k (compiler-scheduled loop), attn_fwd_p_k (the same loop with software-pipelined operand reads,
-// the default: pero_set_option("attn_pipe")) and their launcher pero_attention_fwd.  One workgroup = 128 queries of one (line, head); 4 waves x
-// 32 queries.  Keys are processed in tiles of 128 (online softmax across tiles).  S % 128 != 0 always runs attn_fwd_p_k<RAGGED = true> (the
-// ragged last tile: attention_common.hpp); attn_fwd_k takes S % 128 == 0 only; attn_fwd_keys_k = the pipelined ragged body with per-line key ranges.  Everything is computed TRANSPOSED so that a query lives
+// Forward of the fused attention: attn_fwd_p_k (one body, software-pipelined operand reads), attn_fwd_keys_k (the same body with per-line key
+// ranges) and their host side, attn_fwd_run behind pero_attention_fwd / pero_attention_fwd_keys.  One workgroup = 128 queries of one (line, head); 4 waves x
+// 32 queries.  Keys are processed in tiles of 128 (online softmax across tiles).  S % 128 != 0 runs attn_fwd_p_k<RAGGED = true> (the
+// ragged last tile: attention_common.hpp), S % 128 == 0 attn_fwd_p_k<false>.  Everything is computed TRANSPOSED so that a query lives
 // on a LANE and keys / head-dim live on registers (guide section 3 "an accumulator tile as the next MFMA's operand"):
 //   S^T tile (32 keys x 32 q)  = mfma_32x32x16(A = K rows from LDS, B = Q^T from registers)
 //   row max / sum of a query    = in-lane reduction over its 64 score registers + ONE lane^32 exchange
@@ -15,163 +15,18 @@
 //   scores S^T = K Q^T | vmcnt(0): own part of V(u) | barrier: every wave is done with the K image, V(u) landed | DMA of K(u + 1)
 //   online softmax | O^T += V^T P^T | (a head's last tile: barrier, O through the V image, barrier, row stores, the next head's Q rows)
 //   barrier: every wave is done with the V image | DMA of V(u + 1)
+// V(u) is waited for one phase after K(u) because vmcnt retires in order: a full wait at the loop top exposed V's whole latency at every unit.
 #include "attention_common.hpp"
 
 // hpb = heads per workgroup: the (head, key tile) pairs of `hpb` heads of one line are walked as ONE stream, so the
 // LDS-DMA of the next head's first K / V tile and the global loads of its Q rows run under the current head's last
 // tile.  At S = 256 a (line, head, 128 queries) unit is only two key tiles: measured 439 TFLOP/s against 855 at S = 2048
 // with identical inner loops - the difference was the per-workgroup prologue / epilogue.
-__global__ __launch_bounds__(256, 2) void attn_fwd_k(const bf16raw* qkv, bf16raw* out, float* lse2, int S, int nh, int hpb, float c) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* kimg = smem;
-  unsigned char* vimg = smem + AT_TILE_BYTES;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h5 = lane >> 5, r = lane & 31;
-  const int nqb = S >> 7, ngrp = nh / hpb;
-  int lg, qb;
-  attn_block_map(blockIdx.x, nqb, gridDim.x / nqb, lg, qb);
-  const int line = lg / ngrp, head0 = (lg % ngrp) * hpb;
-  const long long d = (long long)nh * 128, ld = 3 * d;
-  const bf16raw* lbase = qkv + (long long)line * S * ld;  // + head * 128 : q ; + d : k ; + 2d : v
-  const int q = qb * 128 + wave * 32 + r;  // this lane's query (both lane halves hold the same query)
-  const int nkt = S >> 7, units = hpb * nkt;
-
-  attn_glds_tile<false>(lbase + head0 * 128 + d, ld, kimg, wave, lane);
-  attn_glds_tile<true>(lbase + head0 * 128 + 2 * d, ld, vimg, wave, lane);
-
-  bf8v qf[8];
-  {
-    const bf16raw* qrow = lbase + head0 * 128 + (long long)q * ld + 8 * h5;
-#pragma unroll
-    for (int ks = 0; ks < 8; ks++) qf[ks] = *(const bf8v*)(qrow + 16 * ks);
-  }
-  f16v o[4];
-#pragma unroll
-  for (int t = 0; t < 4; t++) o[t] = (f16v){0};
-  float m = -INFINITY, l = 0.f;
-
-  for (int u = 0; u < units; u++) {
-    const int head = head0 + u / nkt, kt = u % nkt;
-    // K(u) (and the head's Q rows) must have landed; V(u) - the NEWEST eight DMA instructions, issued at the end of the
-    // previous unit - may still fly: it is waited for after the scores, one phase later (in-order vmcnt: a full wait here
-    // exposed V's whole latency at every unit)
-    if (u > 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // K(u) landed
-    f16v s[4];
-    AT_PRIO(1);   // this wave's MFMA cluster goes ahead of the other wave's softmax instructions on the same SIMD
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-      s[t] = (f16v){0};
-#pragma unroll
-      for (int ks = 0; ks < 8; ks++)
-        s[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(attn_k_frag(kimg, t * 32 + r, ks, h5), qf[ks], s[t], 0, 0, 0);
-    }
-    AT_PRIO(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own part of V(u)
-    __syncthreads();  // every wave is done with the K image; V(u) landed
-    if (u + 1 < units) {
-      const int nhd = head0 + (u + 1) / nkt, nkt_i = (u + 1) % nkt;
-      attn_glds_tile<false>(lbase + nhd * 128 + d + (long long)nkt_i * 128 * ld, ld, kimg, wave, lane);
-    }
-
-    // ---- online softmax, all lane-local except one lane^32 exchange per reduction
-    float mx = s[0][0];
-#pragma unroll
-    for (int t = 0; t < 4; t++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) mx = fmaxf(mx, s[t][e]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float mn = fmaxf(m, mx);
-    const float alpha = __builtin_amdgcn_exp2f((m - mn) * c);  // exp2(-inf) = 0 on a head's first tile
-    const float mc = mn * c;
-    float ps = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; t++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const float p = __builtin_amdgcn_exp2f(fmaf(s[t][e], c, -mc));
-        s[t][e] = p;
-        ps += p;
-      }
-    ps += __shfl_xor(ps, 32, 64);
-    l = l * alpha + ps;
-    m = mn;
-    if (kt != 0) {  // (a head's first tile: O is still zero)
-#pragma unroll
-      for (int t = 0; t < 4; t++)
-#pragma unroll
-        for (int e = 0; e < 16; e++) o[t][e] *= alpha;
-    }
-
-    // ---- O^T += V^T P^T
-    AT_PRIO(1);
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-#pragma unroll
-      for (int sub = 0; sub < 2; sub++) {
-        const bf8v pf = pack8(s[t], sub);
-#pragma unroll
-        for (int dt = 0; dt < 4; dt++)
-          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(attn_vT_frag(vimg, t * 32 + sub * 16, dt, lane), pf, o[dt], 0, 0, 0);
-      }
-    }
-    AT_PRIO(0);
-    if (kt == nkt - 1) {
-      // ---- head finished: O[q][d] = o[dt][reg] / l, staged through the (now free) V image so that HBM sees whole
-      // 256-byte rows in 16-byte lanes: the direct form (16 scattered 8-byte stores per lane) cost 23 % of the kernel
-      // at S = 256 - and vmcnt makes the next tile's DMA wait for them.  Image: 128 rows x 256 B, 8-byte granule index
-      // XORed with (row & 31): conflict-free ds_write_b64 (lanes = rows) and ds_read_b128 (lanes = chunks of a row).
-      __syncthreads();  // every wave is done with the V image
-      const float inv = 1.0f / l;
-      int qrow_l = wave * 32 + r, tid_l = tid;
-      asm volatile("" : "+v"(qrow_l), "+v"(tid_l));  // keep the 24 staging addresses out of the unit loop's live set
-#pragma unroll
-      for (int dt = 0; dt < 4; dt++)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; g4++) {
-          uint2 w;
-          w.x = pack2bf(o[dt][4 * g4 + 0] * inv, o[dt][4 * g4 + 1] * inv);
-          w.y = pack2bf(o[dt][4 * g4 + 2] * inv, o[dt][4 * g4 + 3] * inv);
-          const int g = dt * 8 + 2 * g4 + h5;  // granule of d = dt*32 + 8*g4 + 4*h5
-          *(uint2*)(vimg + qrow_l * 256 + ((g ^ (qrow_l & 31)) << 3)) = w;
-        }
-      if (h5 == 0) lse2[((long long)line * nh + head) * S + q] = m * c + __builtin_amdgcn_logf(l);  // base-2 LSE of c*scores
-      __syncthreads();
-      {
-        const int ch = tid_l & 15;
-#pragma unroll 2
-        for (int i = 0; i < 8; i++) {
-          const int row = (tid_l >> 4) + 16 * i;
-          const int x = row & 31;
-          uint4 v = *(const uint4*)(vimg + row * 256 + ((ch ^ (x >> 1)) << 4));
-          if (x & 1) { const unsigned t0 = v.x, t1 = v.y; v.x = v.z; v.y = v.w; v.z = t0; v.w = t1; }
-          *(uint4*)(out + ((long long)line * S + qb * 128 + row) * d + head * 128 + ch * 8) = v;
-        }
-      }
-      if (u + 1 < units) {  // next head: fresh statistics, its Q rows (the loads complete under the loop-top wait)
-#pragma unroll
-        for (int t = 0; t < 4; t++) o[t] = (f16v){0};
-        m = -INFINITY;
-        l = 0.f;
-        const bf16raw* qrow = lbase + (head + 1) * 128 + (long long)q * ld + 8 * h5;
-#pragma unroll
-        for (int ks = 0; ks < 8; ks++) qf[ks] = *(const bf8v*)(qrow + 16 * ks);
-      }
-    }
-    if (u + 1 < units) {
-      __syncthreads();  // every wave is done with the V image (and with the O staging reads)
-      const int nhd = head0 + (u + 1) / nkt, nkt_i = (u + 1) % nkt;
-      attn_glds_tile<true>(lbase + nhd * 128 + 2 * d + (long long)nkt_i * 128 * ld, ld, vimg, wave, lane);
-    }
-  }
-}
-
-// ---- forward, pipelined operand reads (see the software-pipelining note in attention_common.hpp).  hipcc's schedule of attn_fwd_k
-// puts an `s_waitcnt vmcnt(0)` right behind the counted vmcnt(8) at the loop top and another one in front of the V reads - the
-// K(u+1) tile issued after the scores is waited for before P V, the V(u) wait cannot be deferred - and serialises read -> wait -> MFMA.
-// Here every LDS access of the loop (fragments, the O staging of a head's last tile) is inline asm: 32 K row fragments for the scores
-// (six in flight), the first seven transposed V fragments in flight while the exponentials run, then rolling.  Same MFMAs in the
-// same order: out and lse are bit-identical to attn_fwd_k.
+// Pipelined operand reads (see the software-pipelining note in attention_common.hpp): left to hipcc, the loop gets an `s_waitcnt vmcnt(0)`
+// right behind the counted vmcnt(8) at the loop top and another one in front of the V reads - the K(u+1) tile issued after the scores is
+// waited for before P V, the V(u) wait cannot be deferred - and read -> wait -> MFMA is serialised.  So every LDS access of the loop
+// (fragments, the O staging of a head's last tile) is inline asm: 32 K row fragments for the scores (six in flight), the first seven
+// transposed V fragments in flight while the exponentials run, then rolling.
 #define FW_POOL 8
 // KEYS (pero_attention_fwd_keys, with RAGGED): line b attends to the keys [k0, k1) of `kr` only (at_key_range: clamped).  The stream of a head walks
 // the key tiles kt0 .. kt_last that intersect the range - a tile without a live key is never visited: its scores would all be -inf and the
@@ -206,7 +61,7 @@ __device__ __forceinline__ void attn_fwd_p_body(const bf16raw* qkv, const int* k
   const unsigned qoff = (unsigned)((long long)qc * ld * 2 + 16 * h5);
   auto load_q = [&](int head) {
     const bf16raw* qb_ = lbase + head * 128;
-    at_static_for<0, 8>([&](auto kc) __attribute__((always_inline)) { constexpr int ks = decltype(kc)::value; lh_gload16<32 * ks>(qf[ks], qb_, qoff); });
+    at_static_for<0, 8>([&](auto kc) __attribute__((always_inline)) { constexpr int ks = decltype(kc)::value; at_gload16<32 * ks>(qf[ks], qb_, qoff); });
   };
   load_q(head0);
   // fragment addresses: K row fragment (key 32 t + r, k-step ks) = ka0 ^ (32 ks) + 8192 t;  V^T fragment (keys 32 t + 16 sub + .., head-dim
@@ -229,7 +84,7 @@ __device__ __forceinline__ void attn_fwd_p_body(const bf16raw* qkv, const int* k
     if (u > 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // K(u) (and the head's Q rows); V(u), the newest eight, may still fly
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]), "+v"(qf[4]), "+v"(qf[5]), "+v"(qf[6]), "+v"(qf[7]) :: "memory");   // (older than V(u): landed)
-    lh_barrier();  // K(u) landed
+    at_barrier();  // K(u) landed
     bf8v fr[FW_POOL];
     f16v s[4];
     // ---- S^T = K Q^T: 32 row fragments (t, ks), six in flight
@@ -251,7 +106,7 @@ __device__ __forceinline__ void attn_fwd_p_body(const bf16raw* qkv, const int* k
     });
     AT_PRIO(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own part of V(u)
-    lh_barrier();  // every wave is done with the K image; V(u) landed
+    at_barrier();  // every wave is done with the K image; V(u) landed
     if (u + 1 < units) {
       const int nhd = head0 + (u + 1) / nkt, nkt_i = kt0 + (u + 1) % nkt;
       attn_glds_tile<false, RAGGED>(lbase + nhd * 128 + d + (long long)nkt_i * 128 * ld, ld, kimg, wave, lane, S - 1 - nkt_i * 128);
@@ -335,7 +190,7 @@ __device__ __forceinline__ void attn_fwd_p_body(const bf16raw* qkv, const int* k
     if (kt == kt_last) {
       // ---- head finished: O[q][d] = o[dt][reg] / l, staged through the (now free) V image so that HBM sees whole 256-byte rows in
       // 16-byte lanes.  Image: 128 rows x 256 B, 8-byte granule index XORed with (row & 31).  (LDS accesses by asm: see the note in front of the kernel)
-      lh_barrier();  // every wave is done with the V image
+      at_barrier();  // every wave is done with the V image
       const float inv = 1.0f / l;
       int qrow_l = wave * 32 + r, tid_l = tid;
       asm volatile("" : "+v"(qrow_l), "+v"(tid_l));  // keep the staging addresses out of the unit loop's live set
@@ -345,19 +200,19 @@ __device__ __forceinline__ void attn_fwd_p_body(const bf16raw* qkv, const int* k
         for (int g4 = 0; g4 < 4; g4++) {
           const at_u2v w = {pack2bf(o[dt][4 * g4 + 0] * inv, o[dt][4 * g4 + 1] * inv), pack2bf(o[dt][4 * g4 + 2] * inv, o[dt][4 * g4 + 3] * inv)};
           const int g = dt * 8 + 2 * g4 + h5;  // granule of d = dt*32 + 8*g4 + 4*h5
-          lh_ds_write8(vbase + qrow_l * 256 + ((g ^ (qrow_l & 31)) << 3), w);
+          at_ds_write8(vbase + qrow_l * 256 + ((g ^ (qrow_l & 31)) << 3), w);
         }
       // base-2 LSE of c*scores (both lane halves hold it and store it: same value, same address)
-      if (!RAGGED || q < S) lh_gstore4(m * c + __builtin_amdgcn_logf(l), lse2 + ((long long)line * nh + head) * S, (unsigned)q * 4u);
-      lh_wait_lgkm_plain<0>();
-      lh_barrier();
+      if (!RAGGED || q < S) at_gstore4(m * c + __builtin_amdgcn_logf(l), lse2 + ((long long)line * nh + head) * S, (unsigned)q * 4u);
+      at_wait_lgkm_plain<0>();
+      at_barrier();
       {
         const int ch = tid_l & 15;
         at_u4v v[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) {
           const int row = (tid_l >> 4) + 16 * i;
-          lh_ds_read16(v[i], vbase + row * 256 + ((ch ^ ((row & 31) >> 1)) << 4));
+          at_ds_read16(v[i], vbase + row * 256 + ((ch ^ ((row & 31) >> 1)) << 4));
         }
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]) :: "memory");
 #pragma unroll
@@ -365,7 +220,7 @@ __device__ __forceinline__ void attn_fwd_p_body(const bf16raw* qkv, const int* k
           const int row = (tid_l >> 4) + 16 * i;
           at_u4v x = v[i];
           if (row & 1) x = (at_u4v){v[i][2], v[i][3], v[i][0], v[i][1]};
-          if (!RAGGED || qb * 128 + row < S) lh_gstore16<0>(x, out + ((long long)line * S + qb * 128) * d + head * 128, (unsigned)(row * (int)d * 2 + ch * 16));
+          if (!RAGGED || qb * 128 + row < S) at_gstore16<0>(x, out + ((long long)line * S + qb * 128) * d + head * 128, (unsigned)(row * (int)d * 2 + ch * 16));
         }
       }
       if (u + 1 < units) {  // next head: fresh statistics, its Q rows (the loads complete under the loop-top wait)
@@ -377,7 +232,7 @@ __device__ __forceinline__ void attn_fwd_p_body(const bf16raw* qkv, const int* k
       }
     }
     if (u + 1 < units) {
-      lh_barrier();  // every wave is done with the V image (and with the O staging reads)
+      at_barrier();  // every wave is done with the V image (and with the O staging reads)
       const int nhd = head0 + (u + 1) / nkt, nkt_i = kt0 + (u + 1) % nkt;
       attn_glds_tile<true, RAGGED>(lbase + nhd * 128 + 2 * d + (long long)nkt_i * 128 * ld, ld, vimg, wave, lane, S - 1 - nkt_i * 128);
     }
@@ -401,47 +256,41 @@ static int attn_heads_per_block(long long N, long long S, long long nh) {
   return hpb;
 }
 
-extern "C" int pero_attention_fwd(const void* qkv, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads,
-                                  int64_t head_dim, int dtype, void* stream) {
-  PERO_REQUIRE(qkv && out && lse, "pero_attention_fwd: null pointer");
+// One host path for both entry points (`who` prefixes the error texts; key_ranges null: none): validate, dispatch on head_dim, launch, check.
+static int attn_fwd_run(const char* who, const void* qkv, const int* key_ranges /* null: none */, void* out, float* lse, int64_t N, int64_t S,
+                        int64_t num_heads, int64_t head_dim, int dtype, hipStream_t st) {
+  PERO_REQUIRE(qkv && out && lse, "%s: null pointer", who);
   PERO_REQUIRE(dtype == PERO_BF16 && (head_dim == 64 || head_dim == 128) && S > 0 && N > 0 && num_heads > 0,
-               "pero_attention_fwd: fused kernel needs bf16, head_dim 64 or 128, S > 0 (got hd=%lld S=%lld)", (long long)head_dim, (long long)S);
-  PERO_REQUIRE(aligned16(qkv) && aligned16(out), "pero_attention_fwd: 16-byte alignment");
-  if (head_dim == 64) {   // attention_hd64.hip
-    attn64_fwd_launch(qkv, out, lse, N, S, num_heads, (hipStream_t)stream);
-    PERO_CHECK_LAUNCH("pero_attention_fwd");
-    return PERO_OK;
+               "%s: fused kernel needs bf16, head_dim 64 or 128, S > 0 (got hd=%lld S=%lld)", who, (long long)head_dim, (long long)S);
+  PERO_REQUIRE(aligned16(qkv) && aligned16(out), "%s: 16-byte alignment", who);
+  if (head_dim == 64) {
+    attn64_fwd_launch(qkv, key_ranges, out, lse, N, S, num_heads, st);   // attention_hd64.hip
+  } else {
+    PERO_LDS_ATTR(attn_fwd_p_k<false>, 2 * AT_TILE_BYTES);
+    PERO_LDS_ATTR(attn_fwd_p_k<true>, 2 * AT_TILE_BYTES);
+    PERO_LDS_ATTR(attn_fwd_keys_k, 2 * AT_TILE_BYTES);
+    const float c = (float)(1.4426950408889634 / sqrt((double)head_dim));
+    const int hpb = attn_heads_per_block(N, S, num_heads);
+    const dim3 grid((unsigned)(N * (num_heads / hpb) * ((S + 127) / 128))), block(256);
+    const bf16raw* q_ = (const bf16raw*)qkv;
+    bf16raw* o_ = (bf16raw*)out;
+    if (key_ranges)   // the ragged body at every S
+      hipLaunchKernelGGL(attn_fwd_keys_k, grid, block, 2 * AT_TILE_BYTES, st, q_, key_ranges, o_, lse, (int)S, (int)num_heads, hpb, c);
+    else
+      hipLaunchKernelGGL((S % 128 ? attn_fwd_p_k<true> : attn_fwd_p_k<false>), grid, block, 2 * AT_TILE_BYTES, st, q_, o_, lse, (int)S, (int)num_heads, hpb, c);
   }
-  PERO_LDS_ATTR(attn_fwd_k, 2 * AT_TILE_BYTES);
-  PERO_LDS_ATTR(attn_fwd_p_k<false>, 2 * AT_TILE_BYTES);
-  PERO_LDS_ATTR(attn_fwd_p_k<true>, 2 * AT_TILE_BYTES);
-  const float c = (float)(1.4426950408889634 / sqrt((double)head_dim));
-  const int hpb = attn_heads_per_block(N, S, num_heads);
-  // a ragged S runs the pipelined kernel whatever "attn_pipe" says: the compiler-scheduled one has no ragged form
-  const auto kernel = S % 128 ? attn_fwd_p_k<true> : g_opt.attn_pipe ? attn_fwd_p_k<false> : attn_fwd_k;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(N * (num_heads / hpb) * ((S + 127) / 128))), dim3(256), 2 * AT_TILE_BYTES,
-                     (hipStream_t)stream, (const bf16raw*)qkv, (bf16raw*)out, lse, (int)S, (int)num_heads, hpb, c);
-  PERO_CHECK_LAUNCH("pero_attention_fwd");
+  PERO_CHECK_LAUNCH(who);
   return PERO_OK;
 }
 
-// The same with per-line key ranges (include/pero_hip.h): always the pipelined ragged body, at every S and whatever "attn_pipe" says.
+extern "C" int pero_attention_fwd(const void* qkv, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads,
+                                  int64_t head_dim, int dtype, void* stream) {
+  return attn_fwd_run("pero_attention_fwd", qkv, nullptr, out, lse, N, S, num_heads, head_dim, dtype, (hipStream_t)stream);
+}
+
+// The same with per-line key ranges (include/pero_hip.h)
 extern "C" int pero_attention_fwd_keys(const void* qkv, const int* key_ranges, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads,
                                        int64_t head_dim, int dtype, void* stream) {
-  PERO_REQUIRE(qkv && key_ranges && out && lse, "pero_attention_fwd_keys: null pointer");
-  PERO_REQUIRE(dtype == PERO_BF16 && (head_dim == 64 || head_dim == 128) && S > 0 && N > 0 && num_heads > 0,
-               "pero_attention_fwd_keys: fused kernel needs bf16, head_dim 64 or 128, S > 0 (got hd=%lld S=%lld)", (long long)head_dim, (long long)S);
-  PERO_REQUIRE(aligned16(qkv) && aligned16(out), "pero_attention_fwd_keys: 16-byte alignment");
-  if (head_dim == 64) {   // attention_hd64.hip
-    attn64_fwd_keys_launch(qkv, key_ranges, out, lse, N, S, num_heads, (hipStream_t)stream);
-    PERO_CHECK_LAUNCH("pero_attention_fwd_keys");
-    return PERO_OK;
-  }
-  PERO_LDS_ATTR(attn_fwd_keys_k, 2 * AT_TILE_BYTES);
-  const float c = (float)(1.4426950408889634 / sqrt((double)head_dim));
-  const int hpb = attn_heads_per_block(N, S, num_heads);
-  hipLaunchKernelGGL(attn_fwd_keys_k, dim3((unsigned)(N * (num_heads / hpb) * ((S + 127) / 128))), dim3(256), 2 * AT_TILE_BYTES,
-                     (hipStream_t)stream, (const bf16raw*)qkv, key_ranges, (bf16raw*)out, lse, (int)S, (int)num_heads, hpb, c);
-  PERO_CHECK_LAUNCH("pero_attention_fwd_keys");
-  return PERO_OK;
+  PERO_REQUIRE(key_ranges, "pero_attention_fwd_keys: null pointer");
+  return attn_fwd_run("pero_attention_fwd_keys", qkv, key_ranges, out, lse, N, S, num_heads, head_dim, dtype, (hipStream_t)stream);
 }

@@ -1,9 +1,10 @@
-// Fused attention at head_dim 64 (bf16, any S >= 1): forward attn64_fwd_k, backward attn64_bwd_dq_k then attn64_bwd_dkv_k, the bias
-// reduction attn64_bias_reduce_k and the two launchers that pero_attention_fwd / pero_attention_bwd dispatch to.  The scheme is the one of
+// Fused attention at head_dim 64 (bf16, any S >= 1): forward attn64_fwd_k, backward attn64_bwd_dq_k then attn64_bwd_dkv_k, their `_keys_k`
+// forms with per-line key ranges, and the two launchers that attn_fwd_run / attn_bwd_run (attention_fwd.hip, attention_bwd.hip) dispatch to; the bias
+// reduction is attn_bias_reduce_k<64> of attention_common.hpp.  The scheme is the one of
 // attention_fwd.hip and attention_bwd.hip - everything computed TRANSPOSED (a query, or a key, lives on a lane), P never leaves registers, K / V
 // / Q / dO tiles arrive by LDS-DMA, the backward recomputes P from the base-2 lse, no atomics go into dqkv - re-derived for rows of 128 bytes
 // (64 bf16): S^T of 32 keys x 32 queries takes 4 k-steps of mfma_f32_32x32x16_bf16, O^T / dQ^T / dK^T / dV^T take 2 head-dim tiles.  The loops
-// are compiler-scheduled; "attn_pipe", "attn_bwd_pair", "attn_lh" and "attn_order" have no effect here.
+// are compiler-scheduled; "attn_bwd_pair" and "attn_order" have no effect here.
 //
 // ONE LDS image serves every tile (K and V of the forward, K / V halves of dQ, the Q / dO stages and the V tile of dK / dV).  Rows of 128 B
 // in pieces of 1 KiB: piece p = rows 8p .. 8p+7, filled by ONE global_load_lds of 16 bytes per lane, lane -> (row 8p + (lane >> 3), 16-byte
@@ -114,7 +115,7 @@ __device__ __forceinline__ void a64_store_tile(const f16v (&acc)[2], unsigned ch
 // vmcnt(0): own part of V(kt) | barrier: every wave is done with the K image | DMA of K(kt + 1) | softmax | O^T += V^T P^T | barrier | DMA of
 // V(kt + 1).  As compiled: hipcc cannot tell an LDS-DMA's destination from the image being read and puts an `s_waitcnt vmcnt(0)` in front of the
 // first LDS read behind every DMA, here the first V fragment of the P V cluster - so K(kt + 1) is waited for in the middle of tile kt, under
-// the softmax only, not under the P V MFMAs (the plain bodies' behaviour described in attention_common.hpp, "Software-pipelined operand
+// the softmax only, not under the P V MFMAs (the behaviour of plain loops described in attention_common.hpp, "Software-pipelined operand
 // reads").  Correct either way; it is part of the 12-23 % by which these loops trail the inline-asm head_dim-128 ones.
 // KEYS (pero_attention_fwd_keys): line b attends to the keys [k0, k1) of `kr` only (at_key_range, attention_common.hpp: clamped).  A head's stream walks the key
 // tiles kt0 .. kt_last that intersect the range - a tile without a live key would leave the running maximum at -inf - and the -inf select covers the dead keys
@@ -522,26 +523,6 @@ __global__ __launch_bounds__(256, 2) void attn64_bwd_dkv_keys_k(const bf16raw* q
   attn64_bwd_dkv_body<true>(smem, qkv, kr, dout, lse2, dvec, dqkv, part, S, nh, c, scale);
 }
 
-// dbias[which * d + head * 64 + c] += sum over the workgroups (line, block) of partial[which][(lh, blk)][c], lh = line * nh + head: the
-// 64-column sibling of attn_bias_reduce_k.  Grid (heads, 3, slices of the workgroup list): one atomic per address and slice.
-__global__ __launch_bounds__(64) void attn64_bias_reduce_k(const float* partial, float* dbias, int nlines, int nh, int nblk) {
-  const int c = threadIdx.x, head = blockIdx.x, which = blockIdx.y;
-  const long long nwg = (long long)nlines * nh * nblk;
-  const float* p = partial + (long long)which * nwg * 64;
-  const int per_head = nlines * nblk;  // workgroups of this head
-  const int chunk = (per_head + gridDim.z - 1) / gridDim.z;
-  const int i0 = blockIdx.z * chunk, i1 = i0 + chunk < per_head ? i0 + chunk : per_head;
-  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // eight rows in flight per thread
-  auto at = [&](int i) -> float { return p[(((long long)(i / nblk) * nh + head) * nblk + i % nblk) * 64 + c]; };
-  int i = i0;
-  for (; i + 8 <= i1; i += 8) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) s[k] += at(i + k);
-  }
-  for (; i < i1; i++) s[0] += at(i);
-  if (i0 < i1) atomicAdd(dbias + (long long)which * nh * 64 + head * 64 + c, ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7])));
-}
-
 // Heads per forward workgroup: the largest divisor of num_heads that keeps >= 4 workgroups per CU - two rounds of the two resident ones.  Measured
 // (forward, d = 512, 8 heads, us, 1 / 2 / 4 / 8 heads per workgroup): N = 2048: S = 256 640 / 596 / 581 / 574, S = 260 1094 / 1034 / 1008 / 1012,
 // S = 36 160 / 146 / 139 / 138; N = 256: S = 256 77 / 74 / 72 / 72, S = 260 132 / 128 / 129 / 146 - the last one is 768 workgroups, one and a
@@ -561,50 +542,32 @@ extern "C" int pero_attention_hd64_heads_per_block(int64_t N, int64_t S, int64_t
   return a64_heads_per_block(N, S, num_heads);
 }
 
-// ---- launchers (declared in attention_common.hpp): the callers have validated the arguments and check the launch
-void attn64_fwd_launch(const void* qkv, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads, hipStream_t st) {
+// ---- launchers (declared in attention_common.hpp): the callers have validated the arguments and check the launch.  kr null: the plain kernels;
+// else the `_keys_k` ones - same grids, same heads per workgroup.
+void attn64_fwd_launch(const void* qkv, const int* kr, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads, hipStream_t st) {
   const float c = (float)(1.4426950408889634 / sqrt(64.0));
   const int64_t nb = (S + 127) / 128;
   const int hpb = a64_heads_per_block(N, S, num_heads);
-  hipLaunchKernelGGL(attn64_fwd_k, dim3((unsigned)(N * (num_heads / hpb) * nb)), dim3(256), A64_FWD_LDS, st, (const bf16raw*)qkv, (bf16raw*)out, lse,
-                     (int)S, (int)num_heads, hpb, c);
+  const dim3 grid((unsigned)(N * (num_heads / hpb) * nb)), block(256);
+  if (kr) hipLaunchKernelGGL(attn64_fwd_keys_k, grid, block, A64_FWD_LDS, st, (const bf16raw*)qkv, kr, (bf16raw*)out, lse, (int)S, (int)num_heads, hpb, c);
+  else hipLaunchKernelGGL(attn64_fwd_k, grid, block, A64_FWD_LDS, st, (const bf16raw*)qkv, (bf16raw*)out, lse, (int)S, (int)num_heads, hpb, c);
 }
 // The same two kernels whether D is computed (`out` given) or handed in (`out` null): dqkv is bit-identical between the two forms.
-void attn64_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv, float* dbias, float* work,
+void attn64_bwd_launch(const void* qkv, const int* kr, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv, float* dbias, float* work,
                        int64_t N, int64_t S, int64_t num_heads, hipStream_t st) {
   const float scale = (float)(1.0 / sqrt(64.0));
   const float c = (float)(1.4426950408889634 / sqrt(64.0));
   const int64_t nb = (S + 127) / 128;   // query blocks = key blocks of a line
   const dim3 grid((unsigned)(N * num_heads * nb)), block(256);
+  const bf16raw *q_ = (const bf16raw*)qkv, *o_ = (const bf16raw*)out, *g_ = (const bf16raw*)dout;
+  bf16raw* dq_ = (bf16raw*)dqkv;
   float* const part = dbias ? work : nullptr;   // 3 * N * num_heads * nb * 64 floats: half of what ops.attention_bwd_fused allocates
-  hipLaunchKernelGGL(attn64_bwd_dq_k, grid, block, A64_DQ_LDS, st, (const bf16raw*)qkv, (const bf16raw*)out, (const bf16raw*)dout, lse, dvec,
-                     (bf16raw*)dqkv, part, (int)S, (int)num_heads, c, scale);
-  hipLaunchKernelGGL(attn64_bwd_dkv_k, grid, block, A64_DKV_LDS, st, (const bf16raw*)qkv, (const bf16raw*)dout, lse, dvec, (bf16raw*)dqkv, part,
-                     (int)S, (int)num_heads, c, scale);
-  if (dbias)
-    hipLaunchKernelGGL(attn64_bias_reduce_k, dim3((unsigned)num_heads, 3, (N * nb >= 4096) ? 128 : (N * nb >= 1024) ? 64 : 16), dim3(64), 0, st,
-                       work, dbias, (int)N, (int)num_heads, (int)nb);
-}
-// ---- the same with per-line key ranges (pero_attention_fwd_keys / pero_attention_bwd_keys): same grids, same heads per workgroup
-void attn64_fwd_keys_launch(const void* qkv, const int* kr, void* out, float* lse, int64_t N, int64_t S, int64_t num_heads, hipStream_t st) {
-  const float c = (float)(1.4426950408889634 / sqrt(64.0));
-  const int64_t nb = (S + 127) / 128;
-  const int hpb = a64_heads_per_block(N, S, num_heads);
-  hipLaunchKernelGGL(attn64_fwd_keys_k, dim3((unsigned)(N * (num_heads / hpb) * nb)), dim3(256), A64_FWD_LDS, st, (const bf16raw*)qkv, kr, (bf16raw*)out, lse,
-                     (int)S, (int)num_heads, hpb, c);
-}
-void attn64_bwd_keys_launch(const void* qkv, const int* kr, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv, float* dbias, float* work,
-                            int64_t N, int64_t S, int64_t num_heads, hipStream_t st) {
-  const float scale = (float)(1.0 / sqrt(64.0));
-  const float c = (float)(1.4426950408889634 / sqrt(64.0));
-  const int64_t nb = (S + 127) / 128;
-  const dim3 grid((unsigned)(N * num_heads * nb)), block(256);
-  float* const part = dbias ? work : nullptr;
-  hipLaunchKernelGGL(attn64_bwd_dq_keys_k, grid, block, A64_DQ_LDS, st, (const bf16raw*)qkv, kr, (const bf16raw*)out, (const bf16raw*)dout, lse, dvec,
-                     (bf16raw*)dqkv, part, (int)S, (int)num_heads, c, scale);
-  hipLaunchKernelGGL(attn64_bwd_dkv_keys_k, grid, block, A64_DKV_LDS, st, (const bf16raw*)qkv, kr, (const bf16raw*)dout, lse, dvec, (bf16raw*)dqkv, part,
-                     (int)S, (int)num_heads, c, scale);
-  if (dbias)
-    hipLaunchKernelGGL(attn64_bias_reduce_k, dim3((unsigned)num_heads, 3, (N * nb >= 4096) ? 128 : (N * nb >= 1024) ? 64 : 16), dim3(64), 0, st,
-                       work, dbias, (int)N, (int)num_heads, (int)nb);
+  if (kr) {
+    hipLaunchKernelGGL(attn64_bwd_dq_keys_k, grid, block, A64_DQ_LDS, st, q_, kr, o_, g_, lse, dvec, dq_, part, (int)S, (int)num_heads, c, scale);
+    hipLaunchKernelGGL(attn64_bwd_dkv_keys_k, grid, block, A64_DKV_LDS, st, q_, kr, g_, lse, dvec, dq_, part, (int)S, (int)num_heads, c, scale);
+  } else {
+    hipLaunchKernelGGL(attn64_bwd_dq_k, grid, block, A64_DQ_LDS, st, q_, o_, g_, lse, dvec, dq_, part, (int)S, (int)num_heads, c, scale);
+    hipLaunchKernelGGL(attn64_bwd_dkv_k, grid, block, A64_DKV_LDS, st, q_, g_, lse, dvec, dq_, part, (int)S, (int)num_heads, c, scale);
+  }
+  if (dbias) attn_bias_reduce_launch<64>(work, dbias, N, num_heads, nb, st);
 }

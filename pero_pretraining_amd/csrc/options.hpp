@@ -6,9 +6,7 @@
 #define PERO_OPTIONS(X)                                                                                                                  \
   X(gemm_policy, 0, "tile-kernel family (table in gemm.hip): 0 = auto, 1 = 128x128x64 persistent, 4 = gemm_bf16_o128, 7 = gemm_bf16_r256, 20 = gemm_bf16_e256") \
   X(attn_bwd_pair, 1, "the attention backward with D handed in runs as one launch")                                                      \
-  X(attn_pipe, 1, "attention bodies with software-pipelined operand reads; 0: the compiler-scheduled ones (same bits)")                  \
   X(attn_order, 32, "dispatch order of the paired backward's blocks (attn_bwd_pair_k); 0 = a unit's four blocks side by side")           \
-  X(attn_lh, 0, "1: S = 256 backward with D handed in and a bias gradient wanted -> the persistent (line, head) kernel (same bits)")     \
   X(splitk_workspace, 1, "split-K of gemm_bf16_e256 leaves partial tiles in the caller's workspace; 0: f32 atomics")                     \
   X(splitk_table, 1, "unaligned slice counts hand their work items out XCD by XCD; 0: plain item order")                                 \
   X(gemm_nw, 0, "1: N = 512 stored products with the plain / residual epilogue on the row-complete tile gemm_bf16_n512")                 \

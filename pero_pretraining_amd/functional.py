@@ -4,7 +4,7 @@ Token layout: every activation is a row-major (N*S, d) matrix of token rows (lin
 what the reference reaches after its `n d s -> s n d` / `s n d -> n d s` transposes
 (models/transformers.py:82-89) - those are pure layout and vanish here.
 
-Attention: bf16 with head_dim 128 runs the fused flash-style kernels of csrc/attention_fwd.hip / attention_bwd.hip / attention_lh.hip, bf16 with
+Attention: bf16 with head_dim 128 runs the fused flash-style kernels of csrc/attention_fwd.hip / attention_bwd.hip, bf16 with
 head_dim 64 those of csrc/attention_hd64.hip, on the
 packed qkv tensor at every line length S (128-row tiles, the last one ragged when S % 128 != 0; scores never stored; one f32 log-sum-exp
 per query saved for the backward); f32 parity mode and other

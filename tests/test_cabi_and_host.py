@@ -127,16 +127,19 @@ def test_argument_validation_without_gpu():
 def test_set_option_takes_the_tested_knobs_and_no_diagnostic_variant():
     """Every option of the library's table (csrc/options.hpp) is accepted (each set to its default here, so the process state does not change); the option
     that selected the eight-phase kernel's diagnostic builds, some of which gave wrong results by design, is gone and is rejected like any
-    unknown name."""
+    unknown name, and so are the two that selected the retired attention variants."""
     from pero_pretraining_amd import _lib
     h = _lib.lib()
-    defaults = {"gemm_policy": 0, "attn_bwd_pair": 1, "attn_pipe": 1, "attn_order": 32, "attn_lh": 0, "splitk_workspace": 1, "splitk_table": 1,
+    defaults = {"gemm_policy": 0, "attn_bwd_pair": 1, "attn_order": 32, "splitk_workspace": 1, "splitk_table": 1,
                 "gemm_nw": 0, "gemm_d128": 0, "gemm_e_walk": 1, "gemm_e256_min": 192, "gemm_e_splitk_min": 4, "splitk_xcd": 1, "splitk_nearest": 0,
                 "splitk_items": 512}
     for name, value in defaults.items():
         assert h.pero_set_option(name.encode(), value) == 0, name
     assert h.pero_set_option(b"gemm_e_var", 1) == -1
     assert b"unknown option gemm_e_var" in h.pero_last_error()
+    for name in (b"attn_pipe", b"attn_lh"):
+        assert h.pero_set_option(name, 1) == -1
+        assert b"unknown option " + name in h.pero_last_error()
 
 
 def test_no_cpu_fallback():
@@ -290,7 +293,7 @@ def test_inline_asm_vector_memory_of_the_tile_gemm_passes_the_isa_lint(tmp_path)
 
 
 def test_inline_asm_vector_memory_of_the_attention_kernels_passes_the_sgpr_lint(tmp_path):
-    """The same SGPR hazard check on the three attention files csrc/attention_fwd.hip, attention_bwd.hip, attention_lh.hip and their header
+    """The same SGPR hazard check on the two attention files csrc/attention_fwd.hip, attention_bwd.hip and their header
     attention_common.hpp: their asm global_load_dword* / global_store_dword* / global_load_lds
     statements take an SGPR base, the kernels hold 20-38 v_readlane / v_readfirstlane each, and nothing but the `s_nop`s inside the asm strings
     keeps a restored SGPR five wait states away from the vector-memory instruction that reads it.  (Only the SGPR check: the in-flight-register
@@ -304,7 +307,7 @@ def test_inline_asm_vector_memory_of_the_attention_kernels_passes_the_sgpr_lint(
         pytest.skip("no hipcc")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "pero_pretraining_amd", "csrc")
-    files = ("attention_fwd", "attention_bwd", "attention_lh")
+    files = ("attention_fwd", "attention_bwd")
     compiles = {name: subprocess.Popen([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-ffp-contract=off",
                                         "-Wno-unused-value", "-S", "--cuda-device-only", os.path.join(csrc, name + ".hip"), "-o", str(tmp_path / (name + ".s"))],
                                        stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL) for name in files}   # side by side
@@ -315,9 +318,9 @@ def test_inline_asm_vector_memory_of_the_attention_kernels_passes_the_sgpr_lint(
                            capture_output=True, text=True)
         assert r.returncode == 0, (name, r.stdout[-2000:])
         linted += r.stdout
-    assert "attn_fwd_p_k" in linted and "attn_bwd_pair_k" in linted and "attn_bwd_lh_k" in linted
+    assert "attn_fwd_p_k" in linted and "attn_bwd_pair_k" in linted
     src = "".join(open(os.path.join(csrc, name)).read() for name in [f + ".hip" for f in files] + ["attention_common.hpp"])
     statements = re.findall(r'asm volatile\("([^"]*(?:global_load_dword|global_store_dword)[^"]*)"', src)
-    assert len(statements) >= 4, statements          # lh_gload16, lh_gload4, lh_gstore16, lh_gstore4: as many as the one-file source had
+    assert len(statements) == 3, statements          # at_gload16, at_gstore16, at_gstore4 (attention_common.hpp); the two .hip files hold none of their own
     for text in statements:
         assert text.startswith("s_nop 4"), "asm vector-memory statement without leading wait states: " + text[:60]

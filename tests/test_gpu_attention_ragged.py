@@ -170,24 +170,6 @@ def test_ragged_paired_launch_equals_the_two_launch_form(n, s, h):
     assert float((db_pair - want).abs().max()) <= 1e-3 * max(1.0, float(want.abs().max()))
 
 
-@pytest.mark.parametrize("n,s,h", [(2, 4, 4), (2, 132, 4), (3, 260, 4)])
-def test_ragged_attn_pipe_off_equals_on(n, s, h):
-    """A ragged S runs the pipelined bodies whatever attn_pipe says (the compiler-scheduled ones have no ragged form): same bits."""
-    from pero_pretraining_amd._lib import call
-    c = case(n, s, h)
-    call("pero_set_option", b"attn_pipe", 0)
-    try:
-        out, lse = fwd(c["qkv"], n, s, h)
-        dqkv, _ = bwd(c["qkv"], out, c["dout"], lse, n, s, h)
-        dvec = Guarded(n * s, h, torch.float32, data=c["dvec"].t)
-        pair, _ = bwd(c["qkv"], None, c["dout"], lse, n, s, h, dvec=dvec)
-    finally:
-        call("pero_set_option", b"attn_pipe", 1)
-    assert torch.equal(out.t, c["out"].t) and torch.equal(lse.t, c["lse"].t)
-    assert torch.equal(dqkv.t, c["dqkv"].t) and torch.equal(pair.t, c["dqkv"].t)
-    assert out.intact() and lse.intact() and dqkv.intact() and pair.intact()
-
-
 def test_ragged_lines_are_independent():
     """S = 100, three lines (one head per workgroup at this size): the call on all lines equals the calls on each line alone, bit for bit."""
     n, s, h = 3, 100, 4

@@ -280,10 +280,10 @@ def test_fused_attention_fwd_bwd(ops, n, s, h):
 
 
 @pytest.mark.parametrize("n", [1, 3, 70])
-def test_attention_backward_variants_give_the_same_bits(ops, n):
-    """S = 256, D handed in, bias gradient wanted: the paired kernels with software-pipelined operand reads (default), their
-    compiler-scheduled form (attn_pipe 0) and the persistent one-(line, head)-per-pass kernel (attn_lh 1; 70 lines x 4 heads = more
-    units than CUs: the workgroups loop) must agree bit for bit in dqkv; the bias gradient up to the order of its f32 sums."""
+def test_attention_backward_paired_two_launch_and_dispatch_orders_give_the_same_bits(ops, n):
+    """S = 256, D handed in, bias gradient wanted: the paired launch in its default dispatch order (attn_order 32), the two-launch form
+    (attn_bwd_pair 0) and the paired launch with a unit's blocks side by side (attn_order 0; 70 lines x 4 heads = 280 units: the XCD block
+    map) must agree bit for bit in dqkv; the bias gradient up to the order of its f32 sums.  A repeated forward gives the same bits."""
     from pero_pretraining_amd._lib import call
     s, h, hd = 256, 4, 128
     d = h * hd
@@ -294,19 +294,19 @@ def test_attention_backward_variants_give_the_same_bits(ops, n):
     dvec = (out.float() * dout.float()).reshape(n * s, h, hd).sum(-1).contiguous()
     res = {}
     try:
-        for name, pipe, lh in (("pipelined", 1, 0), ("compiler", 0, 0), ("line_head", 1, 1)):
-            call("pero_set_option", b"attn_pipe", pipe)
-            call("pero_set_option", b"attn_lh", lh)
+        for name, pair, order in (("paired", 1, 32), ("two_launches", 0, 32), ("side_by_side", 1, 0)):
+            call("pero_set_option", b"attn_bwd_pair", pair)
+            call("pero_set_option", b"attn_order", order)
             db = torch.zeros(3 * d, device="cuda")
             res[name] = (ops.attention_bwd_fused(qkv, None, dout, lse, n, s, h, dbias=db, dvec=dvec), db)
             o2, l2 = ops.attention_fwd_fused(qkv, n, s, h)
             assert torch.equal(o2, out) and torch.equal(l2, lse)
     finally:
-        call("pero_set_option", b"attn_pipe", 1)
-        call("pero_set_option", b"attn_lh", 0)
-    ref, dbr = res["pipelined"]
+        call("pero_set_option", b"attn_bwd_pair", 1)
+        call("pero_set_option", b"attn_order", 32)
+    ref, dbr = res["paired"]
     assert bool(torch.isfinite(ref.float()).all())
-    for name in ("compiler", "line_head"):
+    for name in ("two_launches", "side_by_side"):
         got, db = res[name]
         assert torch.equal(got, ref), name
         assert float((db - dbr).abs().max()) <= 1e-5 * max(1.0, float(dbr.abs().max())), name

@@ -6,7 +6,7 @@ asm load before the wait it cannot see (it did, under register pressure, in the 
 were copied and the arriving data later overwrote live registers).  Straight-line approximation: branches are ignored.
 usage: python tools/check_async_loads.py <file.s> [kernel-name-substring] [--sgpr-only]
 --sgpr-only: only the second check (vector-memory instruction reading an SGPR fewer than five wait states after a vector-ALU write of it): the
-first one models straight-line code and gives false positives on compiler-scheduled kernels with loops (attention_fwd.hip, attention_bwd.hip, attention_lh.hip)."""
+first one models straight-line code and gives false positives on compiler-scheduled kernels with loops (attention_fwd.hip, attention_bwd.hip)."""
 import re, sys
 
 def regs(tok):
