@@ -462,6 +462,40 @@ int pero_line_masks(const int32_t* widths1, const int32_t* widths2, const int32_
                     const int32_t* crop_shifts, uint8_t* image_masks1, uint8_t* image_masks2, uint8_t* shift_masks1,
                     uint8_t* shift_masks2, int32_t* shifts, int64_t B, int64_t S, int64_t subsampling, void* stream);
 
+/* ---- CTC (fine-tuning a recogniser on a pre-trained backbone; csrc/ctc.hip, DESIGN.md "CTC") -------------------------
+ * logits (N*S, C) row-major in `dtype` - the head's own output rows, line n at rows [n S, (n + 1) S); all arithmetic f32.
+ * The log-softmax is fused: logp_t(c) = x[n][t][c] - row_lse[n S + t], row_lse = log sum_c exp(x) per row; no (N*S, C) f32
+ * log-probability tensor exists.  targets (N, Lmax) int64, padded (entries behind target_lengths[n] are never read);
+ * input_lengths, target_lengths (N) int64; every index / length is a DEVICE pointer, nothing synchronises.  Lengths are
+ * clamped to [0, S] and [0, Lmax].  blank: any class in [0, C).  Line n with T = input_lengths[n] frames and L =
+ * target_lengths[n] labels l_0 .. l_{L-1} has the L' = 2 L + 1 extended states l' = (blank, l_0, blank, l_1, .., blank).
+ * A label outside [0, C) emits with probability 0 (the line is infeasible); a label equal to blank counts as blank.
+ *
+ * pero_ctc_fwd: row_lse (N*S) f32 for every row; alpha (N, S, 2 Lmax + 1) f32, entries [n][t][s] with t < T, s < L' written:
+ *   alpha_0(s) = logp_0(l'_s) for s < 2, -inf else;
+ *   alpha_t(s) = logp_t(l'_s) + log(exp alpha_{t-1}(s) + exp alpha_{t-1}(s-1) + [l'_s != l'_{s-2}] exp alpha_{t-1}(s-2));
+ *   nll[n] = -log(exp alpha_{T-1}(L'-1) + exp alpha_{T-1}(L'-2)), +inf for an infeasible line (T < L + repeats; -inf states
+ *   propagate, no NaN).  T = 0: nll = 0 for L = 0, +inf otherwise.
+ * pero_ctc_bwd: beta (N, S, 2 Lmax + 1) f32, a caller buffer written here, INCLUDES the emission at t:
+ *   beta_{T-1}(s) = logp_{T-1}(l'_s) for s >= L' - 2, -inf else;
+ *   beta_t(s) = logp_t(l'_s) + log(exp beta_{t+1}(s) + exp beta_{t+1}(s+1) + [l'_{s+2} != l'_s] exp beta_{t+1}(s+2));
+ *   dlogits[n][t][c] = g[n] (exp(logp_t(c)) - sum_{s: l'_s = c} exp(alpha_t(s) + beta_t(s) + nll[n] - logp_t(c)))   in `dtype`,
+ *   exact zeros for t >= T, and with zero_infinity != 0 for every row of a line whose nll is not finite (without the flag such
+ *   a line's rows are unspecified).  g (N) f32: the upstream scale per line, on the device.  The states of one class are summed in a
+ *   fixed order without atomics: two calls give the same bits.  chain: (N, Lmax) int32 scratch written here.
+ * pero_ctc_greedy: per row the first maximal class (numpy.argmax; NaN-free input), per line over t < T repeats collapsed, then blanks
+ *   dropped: out (N, S) int64 padded with -1, out_lengths (N) int64.
+ * Workspaces (caller-owned): row_lse 4 N S bytes; alpha, beta 4 N S (2 Lmax + 1) bytes each; chain 4 N Lmax bytes; nll 4 N.
+ * Supported: 2 <= C <= 8192, 1 <= S <= 512, 0 <= Lmax <= 512 (PERO_E_UNSUPPORTED above; Lmax may exceed S, a line with L > T is
+ * infeasible), N S < 2^31. */
+int pero_ctc_fwd(const void* logits, const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths, float* row_lse,
+                 float* alpha, float* nll, int64_t N, int64_t S, int64_t C, int64_t Lmax, int64_t blank, int dtype, void* stream);
+int pero_ctc_bwd(const void* logits, const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths,
+                 const float* row_lse, const float* alpha, const float* nll, const float* g, float* beta, int32_t* chain, void* dlogits,
+                 int64_t N, int64_t S, int64_t C, int64_t Lmax, int64_t blank, int zero_infinity, int dtype, void* stream);
+int pero_ctc_greedy(const void* logits, const int64_t* input_lengths, int64_t* out, int64_t* out_lengths, int64_t N, int64_t S, int64_t C,
+                    int64_t blank, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

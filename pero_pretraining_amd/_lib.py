@@ -93,6 +93,9 @@ SIGNATURES = {
     "pero_kmeans_sqnorm": [_vp, _vp, _i64, _i64, _vp],
     "pero_kmeans_pp_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp],
     "pero_kmeans_converge": [_vp, _vp, _vp, _i64, _i64, _f64, _i64, _vp],
+    "pero_ctc_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp],
+    "pero_ctc_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp],
+    "pero_ctc_greedy": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
 }
 
 

@@ -839,3 +839,52 @@ def line_masks(widths1, left1, S, subsampling, widths2=None, left2=None, crop_sh
     call("pero_line_masks", ptr(widths1), ptr(widths2), ptr(left1), ptr(left2), ptr(crop_shifts), ptr(im1), ptr(im2), ptr(sm1),
          ptr(sm2), ptr(shifts), B, S, subsampling, stream())
     return im1, im2, sm1, sm2, shifts
+
+
+def _ctc_args(logits, targets, input_lengths, target_lengths):
+    _req_cuda(logits, targets, input_lengths, target_lengths)
+    n = input_lengths.numel()
+    rows, C = logits.shape
+    if not logits.is_contiguous() or rows % n or targets.dim() != 2 or targets.shape[0] != n or target_lengths.numel() != n:
+        raise ValueError("ctc: logits must be contiguous (N*S, C), targets (N, Lmax), input_lengths and target_lengths (N)")
+    for t in (targets, input_lengths, target_lengths):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise ValueError("ctc: targets and lengths must be contiguous int64 device tensors")
+    return n, rows // n, C, targets.shape[1]
+
+
+def ctc_fwd(logits, targets, input_lengths, target_lengths, blank=0):
+    """logits (N*S, C) f32 / bf16; targets (N, Lmax), input_lengths, target_lengths (N) int64, all on the device.
+    Returns (nll (N) f32, row_lse (N*S) f32, alpha (N, S, 2 Lmax + 1) f32); the last two go to ctc_bwd."""
+    n, S, C, Lmax = _ctc_args(logits, targets, input_lengths, target_lengths)
+    nll = torch.empty(n, device=logits.device, dtype=torch.float32)
+    row_lse = torch.empty(n * S, device=logits.device, dtype=torch.float32)
+    alpha = torch.empty((n, S, 2 * Lmax + 1), device=logits.device, dtype=torch.float32)
+    call("pero_ctc_fwd", ptr(logits), ptr(targets), ptr(input_lengths), ptr(target_lengths), ptr(row_lse), ptr(alpha), ptr(nll),
+         n, S, C, Lmax, blank, dt(logits), stream())
+    return nll, row_lse, alpha
+
+
+def ctc_bwd(logits, targets, input_lengths, target_lengths, row_lse, alpha, nll, g, blank=0, zero_infinity=False):
+    """dlogits (N*S, C) in the logits' dtype = g[n] * d nll[n] / d logits (g: (N) f32 device tensor); the same bits on every call."""
+    n, S, C, Lmax = _ctc_args(logits, targets, input_lengths, target_lengths)
+    beta = torch.empty((n, S, 2 * Lmax + 1), device=logits.device, dtype=torch.float32)
+    chain = torch.empty((n, Lmax), device=logits.device, dtype=torch.int32)
+    dlogits = torch.empty_like(logits)
+    call("pero_ctc_bwd", ptr(logits), ptr(targets), ptr(input_lengths), ptr(target_lengths), ptr(row_lse), ptr(alpha), ptr(nll), ptr(g),
+         ptr(beta), ptr(chain), ptr(dlogits), n, S, C, Lmax, blank, int(bool(zero_infinity)), dt(logits), stream())
+    return dlogits
+
+
+def ctc_greedy(logits, input_lengths, blank=0):
+    """Greedy CTC decoding of (N*S, C) logits: (labels (N, S) int64 padded with -1, lengths (N) int64), on the device."""
+    _req_cuda(logits, input_lengths)
+    n = input_lengths.numel()
+    rows, C = logits.shape
+    if not logits.is_contiguous() or rows % n or input_lengths.dtype != torch.int64 or not input_lengths.is_contiguous():
+        raise ValueError("ctc_greedy: logits must be contiguous (N*S, C), input_lengths contiguous int64 (N)")
+    S = rows // n
+    out = torch.empty((n, S), device=logits.device, dtype=torch.int64)
+    out_lengths = torch.empty(n, device=logits.device, dtype=torch.int64)
+    call("pero_ctc_greedy", ptr(logits), ptr(input_lengths), ptr(out), ptr(out_lengths), n, S, C, blank, dt(logits), stream())
+    return out, out_lengths

@@ -1,0 +1,135 @@
+"""CTC fine-tuning of a pre-trained backbone: CTCLoss over the HIP kernels of csrc/ctc.hip and TransformerRecognizer,
+the backbone + a character head.  (The reference has no recogniser: an extension, like FusedAdamW.)"""
+import torch
+
+from .. import ops
+from ..masked_pretraining.model import LinearHead, init_backbone, init_head
+
+
+class _CTCFn(torch.autograd.Function):
+    """nll (N) f32 of (N, S, C) logits; the backward hands the kernels the upstream (N) gradient as the per-line scale."""
+
+    @staticmethod
+    def forward(ctx, output, targets, input_lengths, target_lengths, blank, zero_infinity):
+        lg = output.detach().reshape(-1, output.shape[-1])
+        if not lg.is_contiguous():
+            lg = lg.contiguous()
+        tg, il, tl = (torch.as_tensor(t).to(device=lg.device, dtype=torch.int64).contiguous() for t in (targets, input_lengths, target_lengths))
+        nll, row_lse, alpha = ops.ctc_fwd(lg, tg, il, tl, blank)
+        ctx.save_for_backward(lg, tg, il, tl, row_lse, alpha, nll)
+        ctx.shape, ctx.blank, ctx.zero_infinity = output.shape, blank, zero_infinity
+        return nll.clone()   # the saved vector stays what the kernels wrote
+
+    @staticmethod
+    def backward(ctx, dnll):
+        lg, tg, il, tl, row_lse, alpha, nll = ctx.saved_tensors
+        g = dnll.detach().to(torch.float32).contiguous()   # stays on the device: no host sync
+        dlogits = ops.ctc_bwd(lg, tg, il, tl, row_lse, alpha, nll, g, ctx.blank, ctx.zero_infinity)
+        return dlogits.view(ctx.shape), None, None, None, None, None
+
+
+class CTCLoss(torch.nn.Module):
+    """torch.nn.CTCLoss's reductions on (N, S, C) LOGITS (the log-softmax is inside the kernels): "none" -> (N); "sum"; "mean" -> the batch
+    mean of nll / clamp(target_length, 1).  zero_infinity: an infeasible line counts 0 and its gradient rows are zeros."""
+
+    def __init__(self, blank=0, reduction="mean", zero_infinity=False):
+        super().__init__()
+        if reduction not in ("none", "sum", "mean"):
+            raise ValueError(f"Unknown reduction: {reduction}")
+        self.blank = blank
+        self.reduction = reduction
+        self.zero_infinity = zero_infinity
+
+    def forward(self, output, targets, input_lengths, target_lengths):
+        if output.dim() != 3:
+            raise ValueError("CTCLoss: output must be (N, S, C)")
+        if not 0 <= self.blank < output.shape[-1]:
+            raise ValueError(f"CTCLoss: blank {self.blank} outside [0, {output.shape[-1]})")
+        nll = _CTCFn.apply(output, targets, input_lengths, target_lengths, self.blank, self.zero_infinity)
+        if self.zero_infinity:
+            nll = torch.where(torch.isinf(nll), torch.zeros_like(nll), nll)
+        if self.reduction == "none":
+            return nll
+        if self.reduction == "sum":
+            return nll.sum()
+        tl = torch.as_tensor(target_lengths).to(device=nll.device).clamp_min(1).to(nll.dtype)
+        return (nll / tl).mean()
+
+
+class TransformerRecognizer(torch.nn.Module):
+    # True: with input_lengths the encoder layers attend to the keys [0, input_length) of each line only (the padding of a batch of
+    # lines of different widths stays out of every valid token); explicit key_ranges of forward() / decode() win.
+    attend_valid_only = False
+
+    def __init__(self, backbone, head, loss=None):
+        super().__init__()
+        self.backbone = backbone
+        self.head = head
+        self.loss = CTCLoss() if loss is None else loss
+
+    def _ranges(self, input_lengths, key_ranges):
+        if key_ranges is not None or not self.attend_valid_only or input_lengths is None:
+            return key_ranges
+        il = torch.as_tensor(input_lengths).to(torch.int64)
+        return torch.stack((torch.zeros_like(il), il.clamp_min(1)), dim=1)   # an empty line attends to its first position (the kernels' clamp)
+
+    def encode(self, images, key_ranges=None):
+        n = images.shape[0]
+        tokens = self.backbone.encode_tokens(images, None, **ops.key_ranges_kw(key_ranges))   # (N*S, d) row-major
+        return self.head(tokens.view(n, -1, tokens.shape[-1]))
+
+    def forward(self, images, targets=None, target_lengths=None, input_lengths=None, key_ranges=None):
+        output = self.encode(images, **ops.key_ranges_kw(self._ranges(input_lengths, key_ranges)))
+        loss = None
+        if targets is not None and target_lengths is not None:
+            if input_lengths is None:
+                input_lengths = torch.full((output.shape[0],), output.shape[1], dtype=torch.int64, device=output.device)
+            loss = self.loss(output, targets, input_lengths, target_lengths)
+        return {"output": output, "loss": loss}
+
+    def decode(self, images, input_lengths=None, key_ranges=None):
+        """Greedy labels (N, S) int64 padded with -1 and their lengths (N), on the device."""
+        with torch.no_grad():
+            output = self.encode(images, **ops.key_ranges_kw(self._ranges(input_lengths, key_ranges)))
+        return greedy_decode(output, input_lengths, getattr(self.loss, "blank", 0))
+
+    def save(self, path):
+        torch.save(self.state_dict(), path)
+
+    def load(self, path):
+        device = next(self.parameters()).device
+        self.load_state_dict(torch.load(path, map_location=device, weights_only=True))
+
+    def load_pretrained_backbone(self, path):
+        """The `backbone.*` entries of a plain state_dict written by MaskedTransformerEncoder.save or the joint model's save, strictly
+        (every backbone tensor must be there, with its shape); the pre-training head's entries are ignored, this model's head is untouched."""
+        device = next(self.parameters()).device
+        sd = torch.load(path, map_location=device, weights_only=True)
+        self.backbone.load_state_dict({k[len("backbone."):]: v for k, v in sd.items() if k.startswith("backbone.")}, strict=True)
+
+
+def greedy_decode(output, input_lengths=None, blank=0):
+    n, S, C = output.shape
+    lg = output.detach().reshape(-1, C)
+    if not lg.is_contiguous():
+        lg = lg.contiguous()
+    if input_lengths is None:
+        il = torch.full((n,), S, dtype=torch.int64, device=lg.device)
+    else:
+        il = torch.as_tensor(input_lengths).to(device=lg.device, dtype=torch.int64).contiguous()
+    return ops.ctc_greedy(lg, il, blank)
+
+
+def init_model(device, backbone_definition, head_definition, path=None, pretrained_path=None, blank=0, reduction="mean", zero_infinity=False):
+    """The masked train.py helper for a recogniser.  path: a recogniser checkpoint; pretrained_path: a pre-training checkpoint whose backbone is taken."""
+    model = TransformerRecognizer(init_backbone(backbone_definition), init_head(head_definition),
+                                  loss=CTCLoss(blank=blank, reduction=reduction, zero_infinity=zero_infinity))
+    model.to(device)
+    if pretrained_path is not None:
+        model.load_pretrained_backbone(pretrained_path)
+    if path is not None:
+        model.load(path)
+    return model
+
+
+__all__ = ["CTCLoss", "TransformerRecognizer", "LinearHead", "greedy_decode", "init_backbone", "init_head", "init_model"]
