@@ -114,6 +114,26 @@ int pero_gemm(const void* A, const void* B, void* C, const float* bias, const vo
 /* bytes of `workspace` with which pero_gemm runs the product of this shape / flags / k_split deterministically (0: it needs none).
  * Depends on the arguments and the pero_set_option knobs only (no device query). */
 int64_t pero_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t batch, int flags, int k_split, int in_dtype, int out_dtype);
+/* What pero_gemm would do with these arguments, without doing it: returns the kernel family that takes the product (PERO_GEMM_KERNEL_*), or the
+ * negative status (and pero_last_error() text) with which pero_gemm refuses the call.  *k_split_out (may be null): the k-slices the kernel runs
+ * with (1: a stored product); *extra_pass_out (may be null): 0, or the PERO_GEMM_PASS_* that pero_gemm runs over C afterwards because the chosen
+ * kernel has no fused PERO_GEMM_COLSUM / PERO_GEMM_ROWDOT epilogue.  Launches nothing, needs no GPU and reads no operand (only the pointers'
+ * alignment counts); depends on the arguments and the pero_set_option knobs only. */
+#define PERO_GEMM_KERNEL_GENERIC 1      /* gemm_generic: exact f32, any shape */
+#define PERO_GEMM_KERNEL_T128 2         /* gemm_bf16_t128: persistent 128x128x64 */
+#define PERO_GEMM_KERNEL_O128 3         /* gemm_bf16_o128: 128x128x64, one tile per workgroup */
+#define PERO_GEMM_KERNEL_R256 4         /* gemm_bf16_r256: 256x128x32 */
+#define PERO_GEMM_KERNEL_E256 5         /* gemm_bf16_e256, stored product */
+#define PERO_GEMM_KERNEL_E256_SPLITK 6  /* gemm_bf16_e256, split-K */
+#define PERO_GEMM_KERNEL_N512 7         /* gemm_bf16_n512: row-complete 128x512 ("gemm_nw") */
+#define PERO_GEMM_PASS_COLSUM 1
+#define PERO_GEMM_PASS_ROWDOT 2
+int pero_gemm_plan(const void* A, const void* B, void* C, const float* bias, const void* residual, const void* gate,
+                   int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int64_t ldg,
+                   int64_t batch, int64_t batch_inner,
+                   int64_t sAo, int64_t sAi, int64_t sBo, int64_t sBi, int64_t sCo, int64_t sCi,
+                   float alpha, int flags, int k_split, int in_dtype, int out_dtype, void* workspace, int64_t workspace_bytes,
+                   void* stream, int* k_split_out, int* extra_pass_out);
 
 /* Linear + residual + LayerNorm in ONE launch (bf16; N = 512, M % 128 == 0, K % 64 == 0, K >= 192): Y = A W^T + bias + R stored (the backward
  * reads it), T = LayerNorm(Y) * gamma + beta computed from the rounded rows of Y exactly as pero_layernorm_fwd does, mean / rstd f32 per row.

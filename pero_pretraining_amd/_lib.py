@@ -19,6 +19,9 @@ GEMM_MASK_TILED = 16384
 GEMM_COLSUM = 1024  # `bias` is an OUTPUT: column sums of the stored result (bias gradient of the upstream Linear)
 GEMM_TILE_V = 512  # prefer the 256x256x64 kernel: products that have the GPU to themselves (forward pass)
 GEMM_TILE128, GEMM_TILE256 = 64, 128
+# pero_gemm_plan: the kernel family that takes a product, and the pass pero_gemm runs over C where that kernel has no fused side output
+GEMM_KERNELS = {1: "generic", 2: "t128", 3: "o128", 4: "r256", 5: "e256", 6: "e256_splitk", 7: "n512"}
+GEMM_PASSES = {0: None, 1: "colsum", 2: "rowdot"}
 
 _vp, _i64, _i32, _f32, _f64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_double
 
@@ -97,6 +100,8 @@ SIGNATURES = {
     "pero_ctc_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp],
     "pero_ctc_greedy": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
 }
+# pero_gemm's arguments + int* k_split, int* extra_pass (each may be null); returns the kernel family (> 0: a key of GEMM_KERNELS), so not for call()
+SIGNATURES["pero_gemm_plan"] = SIGNATURES["pero_gemm"] + [_vp, _vp]
 
 
 class PeroHipError(RuntimeError):

@@ -355,7 +355,10 @@ __global__ __launch_bounds__(256) void gemm_generic(GemmP p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Tile-kernel policy ("gemm_policy"; measurements: DESIGN.md section 8):
+// The plan of one product: which kernel family runs it and with what.  gemm_plan is the one place that decides; it is PURE - no HIP call, no device
+// query, no operand pointer dereferenced (only their alignment is looked at) - so pero_gemm_plan can show the decision to tests without a GPU.
+//
+// Tile-kernel policy ("gemm_policy"; measurements: DESIGN.md section 8; the options and their defaults: options.hpp):
 //   0 = auto:
 //         * stored bf16 products with >= "gemm_e256_min" (192) tiles of 256x256 - and those flagged PERO_GEMM_TILE256 -> the
 //           eight-phase persistent 256x256x64 kernel gemm_bf16_e256 (gemm_e.hip) with its fused epilogues;
@@ -364,22 +367,134 @@ __global__ __launch_bounds__(256) void gemm_generic(GemmP p) {
 //           k-slice per XCD), k-slices aimed at "splitk_items" (512) workgroups;
 //         * other stored products -> gemm_bf16_r256 (256x128x32, two workgroups per CU: small batches) when M is a multiple
 //           of 256, else the persistent 128x128x64 kernel of this file (also: batched products, PERO_GEMM_TILE128);
+//         * "gemm_nw" = 1: N = 512 stored products with the plain / residual epilogue -> the row-complete tile gemm_bf16_n512 first;
 //   forcing one family for A/B runs and tests: 1 = 128x128x64 persistent, 4 = o128, 7 = r256, 20 = e256 (any tile count).
-// (the options and their defaults: options.hpp)
-static int gemm_dispatch(const void* A, const void* B, void* C, const float* bias, const void* residual, const void* gate,
-                         int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int64_t ldg,
-                         int64_t batch, int64_t batch_inner,
-                         int64_t sAo, int64_t sAi, int64_t sBo, int64_t sBi, int64_t sCo, int64_t sCi,
-                         float alpha, int flags, int k_split, int in_dtype, int out_dtype, void* workspace, int64_t workspace_bytes,
-                         void* stream, bool* colsum_fused);
-
-// does a split-K product of this shape take the eight-phase kernel (whose partial tiles can go to a caller-owned workspace)?
-static bool splitk_takes_e256(int64_t M, int64_t N, int64_t K, int flags) {
-  const bool can256 = M % 256 == 0 && N % 256 == 0 && !(flags & PERO_GEMM_TILE128) && g_opt.gemm_policy != 1;
-  const long long t256 = can256 ? (M / 256) * (N / 256) : 0;
-  return can256 && K % 64 == 0 && K >= 128 &&
-         (g_opt.gemm_policy == 20 || (g_opt.gemm_policy == 0 && ((flags & PERO_GEMM_TILE256) || (g_opt.gemm_e256_min > 0 && K >= 32768 && t256 >= g_opt.gemm_e_splitk_min))));
+//   What a family's kernel cannot do (its `_takes` predicate) falls through to the next one in the order below; f32 operands, ragged shapes,
+//   misaligned rows and PERO_GEMM_FORCE_GENERIC take the exact-f32 generic kernel.
+struct GemmPlan {
+  int kernel;      // PERO_GEMM_KERNEL_*
+  int k_split;     // k-slices the kernel really runs with (1: a stored product)
+  int extra_pass;  // 0, or PERO_GEMM_PASS_*: the kernel has no fused side output and pero_gemm runs pero_colsum / pero_rowdot_blocks over C afterwards
+  GemmP p;         // the parameter block as that kernel receives it
+};
+static int gemm_plan(GemmPlan& pl, const void* A, const void* B, void* C, const float* bias, const void* residual, const void* gate,
+                     int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int64_t ldg,
+                     int64_t batch, int64_t batch_inner,
+                     int64_t sAo, int64_t sAi, int64_t sBo, int64_t sBi, int64_t sCo, int64_t sCi,
+                     float alpha, int flags, int k_split, int in_dtype, int out_dtype, void* workspace, int64_t workspace_bytes) {
+  PERO_REQUIRE(workspace_bytes >= 0 && (workspace || workspace_bytes == 0), "pero_gemm: workspace_bytes without a workspace");
+  if (flags & PERO_GEMM_COLSUM)
+    PERO_REQUIRE(bias && batch == 1 && !(flags & (PERO_GEMM_ATOMIC | PERO_GEMM_ACCUM | PERO_GEMM_ROWDOT)),
+                 "pero_gemm: PERO_GEMM_COLSUM needs the output pointer in `bias`, one problem, a stored result");
+  if (flags & PERO_GEMM_ROWDOT)
+    PERO_REQUIRE(bias && gate && batch == 1 && out_dtype == PERO_BF16 && N % 128 == 0 && !(flags & (PERO_GEMM_ATOMIC | PERO_GEMM_ACCUM)),
+                 "pero_gemm: PERO_GEMM_ROWDOT needs the output pointer in `bias`, the second matrix in `gate`, bf16 C, N %% 128 == 0");
+  PERO_REQUIRE(A && B && C, "pero_gemm: null operand");
+  PERO_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0 && batch_inner > 0, "pero_gemm: bad sizes M=%lld N=%lld K=%lld batch=%lld",
+               (long long)M, (long long)N, (long long)K, (long long)batch);
+  PERO_REQUIRE((in_dtype == PERO_F32 || in_dtype == PERO_BF16) && (out_dtype == PERO_F32 || out_dtype == PERO_BF16), "pero_gemm: bad dtype");
+  PERO_REQUIRE(!((flags & (PERO_GEMM_ATOMIC | PERO_GEMM_ACCUM)) && out_dtype != PERO_F32), "pero_gemm: ATOMIC/ACCUM need f32 C");
+  PERO_REQUIRE(k_split >= 0 && (k_split == 1 || (flags & PERO_GEMM_ATOMIC)), "pero_gemm: k_split != 1 needs PERO_GEMM_ATOMIC");
+  PERO_REQUIRE(batch < 65536, "pero_gemm: batch too large");
+  GemmP& p = pl.p;
+  p.A = A; p.B = B; p.C = C; p.bias = bias; p.resid = residual; p.gate = gate;
+  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = ldr; p.ldg = ldg;
+  p.sAo = sAo; p.sAi = sAi; p.sBo = sBo; p.sBi = sBi; p.sCo = sCo; p.sCi = sCi;
+  p.binner = (int)batch_inner; p.alpha = alpha; p.flags = flags; p.kchunk = K;
+  pl.k_split = 1; pl.extra_pass = 0;
+  const int policy = g_opt.gemm_policy;
+  const bool of = out_dtype == PERO_F32, atomic = flags & PERO_GEMM_ATOMIC, bits = flags & PERO_GEMM_RELU_BITS;
+  const bool side = flags & (PERO_GEMM_COLSUM | PERO_GEMM_ROWDOT);
+  const int esz_o = of ? 4 : 2;
+  const bool fast = in_dtype == PERO_BF16 && !(flags & PERO_GEMM_FORCE_GENERIC) && M % T_BM == 0 && N % T_BN == 0 && K % T_BK == 0 &&
+                    lda % 8 == 0 && ldb % 8 == 0 && (ldc * esz_o) % 16 == 0 && aligned16(A) && aligned16(B) && aligned16(C) &&
+                    (sAo % 8 == 0) && (sAi % 8 == 0) && (sBo % 8 == 0) && (sBi % 8 == 0) && ((sCo * esz_o) % 16 == 0) &&
+                    ((sCi * esz_o) % 16 == 0) && (!residual || (ldr % 8 == 0 && aligned16(residual))) &&
+                    (!gate || bits || (ldg % 8 == 0 && aligned16(gate)));
+  if (fast && policy == 1) p.flags |= PERO_GEMM_TILE128;
+  const bool force128 = p.flags & PERO_GEMM_TILE128, force256 = flags & PERO_GEMM_TILE256;
+  PERO_REQUIRE(!(flags & PERO_GEMM_MASK_TILED) || (bits && N % 256 == 0), "pero_gemm: PERO_GEMM_MASK_TILED needs PERO_GEMM_RELU_BITS and N %% 256 == 0");
+  if (bits) {
+    // bit-mask ReLU gate: only the e256 / r256 epilogues read or write it
+    PERO_REQUIRE(fast && gate && batch == 1 && out_dtype == PERO_BF16 && !(flags & PERO_GEMM_TRANS_A) && !atomic && !force128 && M % 256 == 0 &&
+                 N % 128 == 0 && K % 32 == 0 && (policy == 0 || policy == 7 || policy == 20),
+                 "pero_gemm: PERO_GEMM_RELU_BITS needs a bf16 product for the 256-row tile kernels (M %% 256, N %% 128, K %% 32, batch 1)");
+  }
+  // PERO_GEMM_COLSUM / PERO_GEMM_ROWDOT: only the e256 / r256 epilogues fuse the side output; every other kernel gets the block without the flag and
+  // without the (output) bias pointer - for the row dots without the second matrix in `gate` as well - and pero_gemm runs the pass over C afterwards
+  auto take = [&](int kernel) { pl.kernel = kernel; return PERO_OK; };
+  auto unfused = [&](int kernel) {
+    if (side) {
+      pl.extra_pass = (flags & PERO_GEMM_ROWDOT) ? PERO_GEMM_PASS_ROWDOT : PERO_GEMM_PASS_COLSUM;
+      p.flags &= ~(PERO_GEMM_COLSUM | PERO_GEMM_ROWDOT);
+      p.bias = nullptr;
+      if (flags & PERO_GEMM_ROWDOT) p.gate = nullptr;
+    }
+    return take(kernel);
+  };
+  if (!fast) {
+    PERO_REQUIRE((M + 63) / 64 < 2147483647LL && (N + 63) / 64 < 65536, "pero_gemm: N too large for the generic kernel");
+    return unfused(PERO_GEMM_KERNEL_GENERIC);
+  }
+  // the row-complete 128 x 512 tile (opt-in)
+  if (!atomic && !side && !of && pero_gemm_n512_takes(p, batch, of)) return take(PERO_GEMM_KERNEL_N512);
+  // the eight-phase persistent 256x256x64 kernel: split-K weight gradients on long reductions, and stored bf16 products with every fused epilogue
+  const bool can256 = M % 256 == 0 && N % 256 == 0 && !force128;
+  const long long t256 = can256 ? (M / 256) * (N / 256) * batch : 0;
+  const bool many = atomic ? K >= 32768 && t256 >= g_opt.gemm_e_splitk_min : t256 >= g_opt.gemm_e256_min;
+  if (can256 && (policy == 20 || (policy == 0 && (force256 || (g_opt.gemm_e256_min > 0 && many)))) && pero_gemm_e256_takes(p, batch, k_split, of, &pl.k_split))
+    return take(atomic ? PERO_GEMM_KERNEL_E256_SPLITK : PERO_GEMM_KERNEL_E256);
+  // k-slices of the two 128x128x64 kernels
+  int ks = 1;
+  if (atomic && k_split == 0) {
+    const long long t128 = (M / T_BM) * (N / T_BN) * batch;
+    long long n = (g_opt.splitk_items + t128 - 1) / t128;
+    if (n > K / 512) n = K / 512;
+    if (n < 1) n = 1;
+    // powers of two (<= 8) or multiples of 8: lets the kernel place one k-slice per XCD
+    if (n >= 8) n = ((n + (g_opt.splitk_nearest ? 4 : 7)) / 8) * 8;
+    else if (n > 4) n = 8;
+    else if (n == 3) n = 4;
+    if (n > K / 64) n = 1;
+    ks = (int)n;
+  } else if (k_split > 1) {
+    ks = k_split;
+  }
+  // split-K atomics: one 128x128x64 tile per workgroup (policy 4: stored products too)
+  if (!force128 && pero_gemm_o128_takes(p) && (atomic ? policy != 7 : policy == 4 && !side && !bits)) {
+    p.kchunk = pero_k_chunk(K, PERO_BK128, &ks);
+    pl.k_split = ks;
+    return take(PERO_GEMM_KERNEL_O128);
+  }
+  // 256x128x32 tiles, two workgroups per CU: stored products of small batches; carries the column-sum / row-dot / bit-mask epilogues
+  if (!force128 && !atomic && policy != 4 && pero_gemm_r256_takes(p)) return take(PERO_GEMM_KERNEL_R256);
+  PERO_REQUIRE(!bits, "pero_gemm: no kernel took the PERO_GEMM_RELU_BITS product (internal)");
+  p.kchunk = pero_k_chunk(K, PERO_BK128, &ks);
+  pl.k_split = ks;
+  return unfused(PERO_GEMM_KERNEL_T128);
 }
+
+static void gemm_t128_launch(const GemmP& p, long long batch, int k_split, bool out_f32, hipStream_t st) {
+  const long long nwork = (p.M / T_BM) * (p.N / T_BN) * batch * k_split;
+  const long long resident = 2LL * pero_num_cus();  // 2 workgroups per CU (LDS-limited)
+  dim3 grid((unsigned)(nwork < resident ? nwork : resident)), block(256);
+  const int nbatch = (int)batch;
+#define LAUNCH_FAST(TA_, TB_, OF_)                                                                                        \
+  do {                                                                                                                    \
+    PERO_LDS_ATTR((gemm_bf16_t128<TA_, TB_, OF_>), T_LDS_BYTES);                                                          \
+    hipLaunchKernelGGL((gemm_bf16_t128<TA_, TB_, OF_>), grid, block, T_LDS_BYTES, st, p, nbatch, nwork);                  \
+  } while (0)
+  PERO_LAYOUT_LADDER(LAUNCH_FAST, p.flags & PERO_GEMM_TRANS_A, p.flags & PERO_GEMM_TRANS_B, out_f32);
+#undef LAUNCH_FAST
+}
+static void gemm_generic_launch(const GemmP& p, long long batch, int in_dtype, int out_dtype, hipStream_t st) {
+  dim3 grid((unsigned)((p.M + 63) / 64), (unsigned)((p.N + 63) / 64), (unsigned)batch), block(256);
+  if (in_dtype == PERO_F32 && out_dtype == PERO_F32) hipLaunchKernelGGL((gemm_generic<float, float>), grid, block, 0, st, p);
+  else if (in_dtype == PERO_BF16 && out_dtype == PERO_BF16) hipLaunchKernelGGL((gemm_generic<bf16raw, bf16raw>), grid, block, 0, st, p);
+  else if (in_dtype == PERO_BF16 && out_dtype == PERO_F32) hipLaunchKernelGGL((gemm_generic<bf16raw, float>), grid, block, 0, st, p);
+  else hipLaunchKernelGGL((gemm_generic<float, bf16raw>), grid, block, 0, st, p);
+}
+
 // Linear + residual + LayerNorm in one launch (the row-complete 128 x 512 tile of gemm_n.hip): Y = A W^T + bias + R (bf16, stored: the backward
 // needs it), T = (Y - mean) * rstd * gamma + beta over the ROUNDED rows of Y (layernorm_fwd4_k's arithmetic), mean / rstd (f32 per row).
 extern "C" int pero_gemm_resid_layernorm(const void* A, const void* W, const float* bias, const void* R, const float* gamma, const float* beta,
@@ -417,12 +532,31 @@ extern "C" int pero_gemm_resid_layernorm_bwd(const void* A, const void* Wt, cons
   PERO_CHECK_LAUNCH("pero_gemm_resid_layernorm_bwd");
   return PERO_OK;
 }
+extern "C" int pero_gemm_plan(const void* A, const void* B, void* C, const float* bias, const void* residual, const void* gate,
+                              int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int64_t ldg,
+                              int64_t batch, int64_t batch_inner,
+                              int64_t sAo, int64_t sAi, int64_t sBo, int64_t sBi, int64_t sCo, int64_t sCi,
+                              float alpha, int flags, int k_split, int in_dtype, int out_dtype, void* workspace, int64_t workspace_bytes,
+                              void* /*stream*/, int* k_split_out, int* extra_pass_out) {
+  GemmPlan pl;
+  const int rc = gemm_plan(pl, A, B, C, bias, residual, gate, M, N, K, lda, ldb, ldc, ldr, ldg, batch, batch_inner, sAo, sAi, sBo, sBi, sCo, sCi, alpha,
+                           flags, k_split, in_dtype, out_dtype, workspace, workspace_bytes);
+  if (rc != PERO_OK) return rc;
+  if (k_split_out) *k_split_out = pl.k_split;
+  if (extra_pass_out) *extra_pass_out = pl.extra_pass;
+  return pl.kernel;
+}
+// (the plan of the same product with made-up, aligned operands and rows as long as the matrices are wide)
 extern "C" int64_t pero_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t batch, int flags, int k_split, int in_dtype,
                                              int out_dtype) {
-  if (!(flags & PERO_GEMM_ATOMIC) || batch != 1 || in_dtype != PERO_BF16 || out_dtype != PERO_F32 || (flags & PERO_GEMM_FORCE_GENERIC) || M <= 0 ||
-      N <= 0 || K <= 0 || !splitk_takes_e256(M, N, K, flags))
+  if (!(flags & PERO_GEMM_ATOMIC)) return 0;
+  void* const any = (void*)(uintptr_t)4096;
+  GemmPlan pl;
+  if (gemm_plan(pl, any, any, any, nullptr, nullptr, nullptr, M, N, K, (flags & PERO_GEMM_TRANS_A) ? M : K, (flags & PERO_GEMM_TRANS_B) ? N : K, N, 0, 0,
+                batch, 1, 0, 0, 0, 0, 0, 0, 1.0f, flags, k_split, in_dtype, out_dtype, nullptr, 0) != PERO_OK ||
+      pl.kernel != PERO_GEMM_KERNEL_E256_SPLITK)
     return 0;
-  return pero_gemm_e256_splitk_ws_bytes(M, N, K, k_split);
+  return pero_gemm_e256_splitk_ws_bytes(M, N, pl.k_split);
 }
 
 extern "C" int pero_gemm(const void* A, const void* B, void* C, const float* bias, const void* residual, const void* gate,
@@ -431,159 +565,25 @@ extern "C" int pero_gemm(const void* A, const void* B, void* C, const float* bia
                          int64_t sAo, int64_t sAi, int64_t sBo, int64_t sBi, int64_t sCo, int64_t sCi,
                          float alpha, int flags, int k_split, int in_dtype, int out_dtype, void* workspace, int64_t workspace_bytes,
                          void* stream) {
-  bool fused = false;
-  PERO_REQUIRE(workspace_bytes >= 0 && (workspace || workspace_bytes == 0), "pero_gemm: workspace_bytes without a workspace");
-  if (flags & PERO_GEMM_COLSUM)
-    PERO_REQUIRE(bias && batch == 1 && !(flags & (PERO_GEMM_ATOMIC | PERO_GEMM_ACCUM | PERO_GEMM_ROWDOT)),
-                 "pero_gemm: PERO_GEMM_COLSUM needs the output pointer in `bias`, one problem, a stored result");
-  if (flags & PERO_GEMM_ROWDOT)
-    PERO_REQUIRE(bias && gate && batch == 1 && out_dtype == PERO_BF16 && N % 128 == 0 && !(flags & (PERO_GEMM_ATOMIC | PERO_GEMM_ACCUM)),
-                 "pero_gemm: PERO_GEMM_ROWDOT needs the output pointer in `bias`, the second matrix in `gate`, bf16 C, N %% 128 == 0");
-  const int rc = gemm_dispatch(A, B, C, bias, residual, gate, M, N, K, lda, ldb, ldc, ldr, ldg, batch, batch_inner, sAo, sAi, sBo, sBi,
-                               sCo, sCi, alpha, flags, k_split, in_dtype, out_dtype, workspace, workspace_bytes, stream, &fused);
-  if (rc != PERO_OK || !(flags & (PERO_GEMM_COLSUM | PERO_GEMM_ROWDOT)) || fused) return rc;
-  // kernels without the fused epilogue: a pass over C
-  if (flags & PERO_GEMM_ROWDOT) return pero_rowdot_blocks(C, gate, (float*)bias, M, N, ldc, ldg, stream);
-  return pero_colsum(C, (float*)bias, M, N, ldc, out_dtype, stream);
-}
-
-static int gemm_dispatch(const void* A, const void* B, void* C, const float* bias, const void* residual, const void* gate,
-                         int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int64_t ldg,
-                         int64_t batch, int64_t batch_inner,
-                         int64_t sAo, int64_t sAi, int64_t sBo, int64_t sBi, int64_t sCo, int64_t sCi,
-                         float alpha, int flags, int k_split, int in_dtype, int out_dtype, void* workspace, int64_t workspace_bytes,
-                         void* stream, bool* colsum_fused) {
-  PERO_REQUIRE(A && B && C, "pero_gemm: null operand");
-  PERO_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0 && batch_inner > 0, "pero_gemm: bad sizes M=%lld N=%lld K=%lld batch=%lld",
-               (long long)M, (long long)N, (long long)K, (long long)batch);
-  PERO_REQUIRE((in_dtype == PERO_F32 || in_dtype == PERO_BF16) && (out_dtype == PERO_F32 || out_dtype == PERO_BF16), "pero_gemm: bad dtype");
-  PERO_REQUIRE(!((flags & (PERO_GEMM_ATOMIC | PERO_GEMM_ACCUM)) && out_dtype != PERO_F32), "pero_gemm: ATOMIC/ACCUM need f32 C");
-  PERO_REQUIRE(k_split >= 0 && (k_split == 1 || (flags & PERO_GEMM_ATOMIC)), "pero_gemm: k_split != 1 needs PERO_GEMM_ATOMIC");
-  PERO_REQUIRE(batch < 65536, "pero_gemm: batch too large");
-  const bool ta = flags & PERO_GEMM_TRANS_A, tb = flags & PERO_GEMM_TRANS_B;
-  GemmP p;
-  p.A = A; p.B = B; p.C = C; p.bias = bias; p.resid = residual; p.gate = gate;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = ldr; p.ldg = ldg;
-  p.sAo = sAo; p.sAi = sAi; p.sBo = sBo; p.sBi = sBi; p.sCo = sCo; p.sCi = sCi;
-  p.binner = (int)batch_inner; p.alpha = alpha; p.flags = flags; p.kchunk = K;
+  GemmPlan pl;
+  const int rc = gemm_plan(pl, A, B, C, bias, residual, gate, M, N, K, lda, ldb, ldc, ldr, ldg, batch, batch_inner, sAo, sAi, sBo, sBi, sCo, sCi, alpha,
+                           flags, k_split, in_dtype, out_dtype, workspace, workspace_bytes);
+  if (rc != PERO_OK) return rc;
+  const GemmP& p = pl.p;
+  const bool of = out_dtype == PERO_F32;
   hipStream_t st = (hipStream_t)stream;
-  // PERO_GEMM_COLSUM: only the r256 / v256 epilogues accumulate the column sums (`pc`); every other kernel gets `p`
-  // without the flag and without the (output) bias pointer, and pero_gemm runs pero_colsum over C afterwards.
-  // PERO_GEMM_ROWDOT is handled the same way (r256 only): `pc` keeps flag, gate and output pointer, `p` loses all three.
-  const bool want_cs = flags & (PERO_GEMM_COLSUM | PERO_GEMM_ROWDOT);
-  const bool want_rd = flags & PERO_GEMM_ROWDOT;
-  const int cs_bits = flags & (PERO_GEMM_COLSUM | PERO_GEMM_ROWDOT);
-  GemmP pc = p;
-  if (want_cs) { flags &= ~(PERO_GEMM_COLSUM | PERO_GEMM_ROWDOT); p.flags = flags; p.bias = nullptr; if (want_rd) p.gate = nullptr; }
-
-  const int esz_o = out_dtype == PERO_F32 ? 4 : 2;
-  bool fast = in_dtype == PERO_BF16 && !(flags & 32) && M % T_BM == 0 && N % T_BN == 0 && K % T_BK == 0 &&
-              lda % 8 == 0 && ldb % 8 == 0 && (ldc * esz_o) % 16 == 0 && aligned16(A) && aligned16(B) && aligned16(C) &&
-              (sAo % 8 == 0) && (sAi % 8 == 0) && (sBo % 8 == 0) && (sBi % 8 == 0) && ((sCo * esz_o) % 16 == 0) &&
-              ((sCi * esz_o) % 16 == 0) && (!residual || (ldr % 8 == 0 && aligned16(residual))) &&
-              (!gate || (flags & PERO_GEMM_RELU_BITS) || (ldg % 8 == 0 && aligned16(gate))) && (!(residual || gate) || out_dtype == PERO_BF16 || true);
-  if (fast && g_opt.gemm_policy == 1) { flags |= PERO_GEMM_TILE128; p.flags = flags; pc.flags = flags | cs_bits; }
-  const bool force128 = flags & PERO_GEMM_TILE128, force256 = flags & PERO_GEMM_TILE256;
-  PERO_REQUIRE(!(flags & PERO_GEMM_MASK_TILED) || ((flags & PERO_GEMM_RELU_BITS) && N % 256 == 0), "pero_gemm: PERO_GEMM_MASK_TILED needs PERO_GEMM_RELU_BITS and N %% 256 == 0");
-  if (flags & PERO_GEMM_RELU_BITS) {
-    // bit-mask ReLU gate: only the e256 / r256 epilogues read or write it
-    PERO_REQUIRE(fast && gate && batch == 1 && out_dtype == PERO_BF16 && !ta && !(flags & PERO_GEMM_ATOMIC) && !force128 && M % 256 == 0 &&
-                 N % 128 == 0 && K % 32 == 0 && !(flags & PERO_GEMM_ROWDOT) && (g_opt.gemm_policy == 0 || g_opt.gemm_policy == 7 || g_opt.gemm_policy == 20),
-                 "pero_gemm: PERO_GEMM_RELU_BITS needs a bf16 product for the 256-row tile kernels (M %% 256, N %% 128, K %% 32, batch 1)");
+  switch (pl.kernel) {
+    case PERO_GEMM_KERNEL_E256:
+    case PERO_GEMM_KERNEL_E256_SPLITK: pero_gemm_e256_launch(p, pl.k_split, st, workspace, workspace_bytes); break;
+    case PERO_GEMM_KERNEL_N512: pero_gemm_n512_launch(p, st); break;
+    case PERO_GEMM_KERNEL_O128: pero_gemm_o128_launch(p, batch, pl.k_split, of, st); break;
+    case PERO_GEMM_KERNEL_R256: pero_gemm_r256_launch(p, batch, pl.k_split, of, st); break;
+    case PERO_GEMM_KERNEL_T128: gemm_t128_launch(p, batch, pl.k_split, of, st); break;
+    default: gemm_generic_launch(p, batch, in_dtype, out_dtype, st); break;
   }
-  if (fast) {
-    const bool atomic = flags & PERO_GEMM_ATOMIC;
-    const bool can256 = M % 256 == 0 && N % 256 == 0 && !force128;
-    const long long t256 = can256 ? (M / 256) * (N / 256) * batch : 0;
-    const long long t128 = (M / T_BM) * (N / T_BN) * batch;
-    const int k_split_req = k_split;
-    const bool auto_or = g_opt.gemm_policy == 0;
-    // the eight-phase persistent 256x256x64 kernel (gemm_e.hip): split-K weight gradients on long reductions ...
-    if (atomic && out_dtype == PERO_F32 && batch == 1 && splitk_takes_e256(M, N, K, flags) &&
-        pero_launch_gemm_e256(p, batch, k_split_req, ta, tb, true, st, workspace, workspace_bytes)) {
-      PERO_CHECK_LAUNCH("pero_gemm(e256 split-K)");
-      return PERO_OK;
-    }
-    // the row-complete 128 x 512 tile (opt-in): N = 512 stored products with the plain / residual epilogue
-    if (!atomic && g_opt.gemm_nw && !want_cs && out_dtype == PERO_BF16 && pero_launch_gemm_n512(p, batch, ta, tb, false, st)) {
-      PERO_CHECK_LAUNCH("pero_gemm(n512)");
-      return PERO_OK;
-    }
-    // two workgroups per CU on 256 x 128 tiles (opt-in): stored products with few K-tiles per tile, plain / ReLU / bit-mask epilogues
-    if (!atomic && g_opt.gemm_d128 && out_dtype == PERO_BF16 && !want_rd && K <= g_opt.gemm_d128 * 64LL && (auto_or || g_opt.gemm_policy == 20) &&
-        pero_launch_gemm_d128(pc, batch, ta, tb, false, st)) {
-      *colsum_fused = want_cs;
-      PERO_CHECK_LAUNCH("pero_gemm(d128)");
-      return PERO_OK;
-    }
-    // ... and stored bf16 products with every fused epilogue
-    if (!atomic && can256 && (g_opt.gemm_policy == 20 || (auto_or && (force256 || (g_opt.gemm_e256_min > 0 && t256 >= g_opt.gemm_e256_min)))) &&
-        pero_launch_gemm_e256(pc, batch, k_split, ta, tb, out_dtype == PERO_F32, st)) {
-      *colsum_fused = want_cs;
-      PERO_CHECK_LAUNCH("pero_gemm(e256)");
-      return PERO_OK;
-    }
-    if (atomic && k_split == 0) {
-      long long ks = (g_opt.splitk_items + t128 - 1) / t128;
-      if (ks > K / 512) ks = K / 512;
-      if (ks < 1) ks = 1;
-      // powers of two (<= 8) or multiples of 8: lets the kernel place one k-slice per XCD
-      if (ks >= 8) ks = ((ks + (g_opt.splitk_nearest ? 4 : 7)) / 8) * 8;
-      else if (ks > 4) ks = 8;
-      else if (ks == 3) ks = 4;
-      if (ks > K / 64) ks = 1;
-      k_split = (int)ks;
-    } else if (k_split < 1) {
-      k_split = 1;
-    }
-    // split-K atomics: one 128x128x64 tile per workgroup
-    if (!force128 && atomic && g_opt.gemm_policy != 7 && pero_launch_gemm_o128(p, batch, k_split, ta, tb, out_dtype == PERO_F32, st)) {
-      PERO_CHECK_LAUNCH("pero_gemm(bf16 o128)");
-      return PERO_OK;
-    }
-    if (!force128 && !atomic && g_opt.gemm_policy == 4 && !want_cs && !(flags & PERO_GEMM_RELU_BITS) &&
-        pero_launch_gemm_o128(p, batch, k_split, ta, tb, out_dtype == PERO_F32, st)) {
-      PERO_CHECK_LAUNCH("pero_gemm(bf16 o128)");
-      return PERO_OK;
-    }
-    // 256x128x32 tiles, two workgroups per CU: stored products of small batches; carries the column-sum / row-dot / bit-mask epilogues
-    if (!force128 && !atomic && g_opt.gemm_policy != 4 && pero_launch_gemm_r256(want_cs ? pc : p, batch, k_split, ta, tb, out_dtype == PERO_F32, st)) {
-      *colsum_fused = want_cs;
-      PERO_CHECK_LAUNCH("pero_gemm(bf16 r256)");
-      return PERO_OK;
-    }
-    PERO_REQUIRE(!(flags & PERO_GEMM_RELU_BITS), "pero_gemm: no kernel took the PERO_GEMM_RELU_BITS product (internal)");
-    if (k_split > 1) {
-
-      long long steps = K / T_BK;
-      long long per = (steps + k_split - 1) / k_split;
-      p.kchunk = per * T_BK;
-      k_split = (int)((steps + per - 1) / per);
-    }
-    const long long nwork = (M / T_BM) * (N / T_BN) * batch * k_split;
-    const int num_cus = pero_num_cus();
-    const long long resident = 2LL * num_cus;  // 2 workgroups per CU (LDS-limited)
-    dim3 grid((unsigned)(nwork < resident ? nwork : resident)), block(256);
-    const int nbatch = (int)batch;
-#define LAUNCH_FAST(TA_, TB_, OF_)                                                                                        \
-  do {                                                                                                                    \
-    PERO_LDS_ATTR((gemm_bf16_t128<TA_, TB_, OF_>), T_LDS_BYTES);                                                          \
-    hipLaunchKernelGGL((gemm_bf16_t128<TA_, TB_, OF_>), grid, block, T_LDS_BYTES, st, p, nbatch, nwork);                                 \
-  } while (0)
-    const bool of = out_dtype == PERO_F32;
-    if (!ta && !tb) { if (of) LAUNCH_FAST(false, false, true); else LAUNCH_FAST(false, false, false); }
-    else if (!ta && tb) { if (of) LAUNCH_FAST(false, true, true); else LAUNCH_FAST(false, true, false); }
-    else if (ta && tb) { if (of) LAUNCH_FAST(true, true, true); else LAUNCH_FAST(true, true, false); }
-    else { if (of) LAUNCH_FAST(true, false, true); else LAUNCH_FAST(true, false, false); }
-    PERO_CHECK_LAUNCH("pero_gemm(bf16 fast)");
-    return PERO_OK;
-  }
-  PERO_REQUIRE((M + 63) / 64 < 2147483647LL && (N + 63) / 64 < 65536, "pero_gemm: N too large for the generic kernel");
-  dim3 grid((unsigned)((M + 63) / 64), (unsigned)((N + 63) / 64), (unsigned)batch), block(256);
-  if (in_dtype == PERO_F32 && out_dtype == PERO_F32) hipLaunchKernelGGL((gemm_generic<float, float>), grid, block, 0, st, p);
-  else if (in_dtype == PERO_BF16 && out_dtype == PERO_BF16) hipLaunchKernelGGL((gemm_generic<bf16raw, bf16raw>), grid, block, 0, st, p);
-  else if (in_dtype == PERO_BF16 && out_dtype == PERO_F32) hipLaunchKernelGGL((gemm_generic<bf16raw, float>), grid, block, 0, st, p);
-  else hipLaunchKernelGGL((gemm_generic<float, bf16raw>), grid, block, 0, st, p);
-  PERO_CHECK_LAUNCH("pero_gemm(generic)");
+  PERO_CHECK_LAUNCH("pero_gemm");
+  // kernels without the fused epilogue: a pass over C
+  if (pl.extra_pass == PERO_GEMM_PASS_ROWDOT) return pero_rowdot_blocks(C, gate, (float*)bias, M, N, ldc, ldg, stream);
+  if (pl.extra_pass == PERO_GEMM_PASS_COLSUM) return pero_colsum(C, (float*)bias, M, N, ldc, out_dtype, stream);
   return PERO_OK;
 }

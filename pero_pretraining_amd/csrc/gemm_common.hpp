@@ -1,4 +1,4 @@
-// Shared by the bf16 tile GEMM kernels (gemm.hip, gemm_o.hip, gemm_r.hip and, through gemm_e_common.hpp, gemm_e.hip, gemm_d.hip, gemm_n.hip).
+// Shared by the bf16 tile GEMM kernels (gemm.hip, gemm_o.hip, gemm_r.hip and, through gemm_e_common.hpp, gemm_e.hip, gemm_n.hip).
 #pragma once
 #include "common.hpp"
 #include <initializer_list>
@@ -27,26 +27,50 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");  // keep later LDS accesses below the barrier
 }
 
-// host entry of the one-tile-per-workgroup 128x128x64 kernel (gemm_o.hip): split-K weight gradients of short reductions
-bool pero_launch_gemm_o128(const GemmP& p, long long batch, int k_split, bool ta, bool tb, bool out_f32, hipStream_t st);
-// host entry of the 256x128x32 eight-wave kernel (gemm_r.hip): stored products of small batches
-bool pero_launch_gemm_r256(const GemmP& p, long long batch, int k_split, bool ta, bool tb, bool out_f32, hipStream_t st);
-// host entry of the eight-phase ping-pong persistent 256x256x64 kernel (gemm_e.hip)
-// ws / ws_bytes: the caller's workspace for split-K partial tiles (pero_gemm's `workspace`); null: f32 atomics
-bool pero_launch_gemm_e256(const GemmP& p, long long batch, int k_split, bool ta, bool tb, bool out_f32, hipStream_t st, void* ws = nullptr,
-                           long long ws_bytes = 0);
-long long pero_gemm_e256_splitk_ws_bytes(long long M, long long N, long long K, int k_split);
-// host entry of the row-complete 128 x 512 tile (gemm_n.hip, opt-in "gemm_nw"): N = 512 stored products with the plain / residual epilogue
-bool pero_launch_gemm_n512(const GemmP& p, long long batch, bool ta, bool tb, bool out_f32, hipStream_t st);
-// host entry of the 256 x 128 tile with two workgroups per CU (gemm_d.hip, opt-in "gemm_d128" = the largest K / 64 that takes it)
-bool pero_launch_gemm_d128(const GemmP& p, long long batch, bool ta, bool tb, bool out_f32, hipStream_t st);
+// ---- host entries of the tile kernels.  Each family has a pure predicate `_takes` (the shape / epilogue restrictions of its kernel; no HIP call, no
+// pointer dereferenced) and a `_launch` that cannot refuse: gemm_plan (gemm.hip) asks the predicates, pero_gemm launches what the plan names.
+// ta / tb are p.flags' PERO_GEMM_TRANS_A / _B; `k_split` of a launch is the slice count the plan settled on (p.kchunk set to match).
+// one-tile-per-workgroup 128x128x64 kernel (gemm_o.hip): split-K weight gradients of short reductions
+bool pero_gemm_o128_takes(const GemmP& p);
+void pero_gemm_o128_launch(const GemmP& p, long long batch, int k_split, bool out_f32, hipStream_t st);
+// 256x128x32 eight-wave kernel (gemm_r.hip): stored products of small batches
+bool pero_gemm_r256_takes(const GemmP& p);
+void pero_gemm_r256_launch(const GemmP& p, long long batch, int k_split, bool out_f32, hipStream_t st);
+// eight-phase ping-pong persistent 256x256x64 kernel (gemm_e.hip); k_split: as the caller asked (<= 0: the library chooses), *slices: the slice count
+// the kernel runs with (1: a stored product).  ws / ws_bytes: the caller's workspace for split-K partial tiles (pero_gemm's `workspace`); null: f32 atomics
+bool pero_gemm_e256_takes(const GemmP& p, long long batch, int k_split, bool out_f32, int* slices);
+void pero_gemm_e256_launch(const GemmP& p, int k_split, hipStream_t st, void* ws, long long ws_bytes);
+long long pero_gemm_e256_splitk_ws_bytes(long long M, long long N, int slices);
+// row-complete 128 x 512 tile (gemm_n.hip, opt-in "gemm_nw"): N = 512 stored products with the plain / residual epilogue
+bool pero_gemm_n512_takes(const GemmP& p, long long batch, bool out_f32);
+void pero_gemm_n512_launch(const GemmP& p, hipStream_t st);
+// ... and its fused LayerNorm forms, which have no other kernel to fall back to (false: the shape is not theirs, nothing was launched)
 bool pero_launch_gemm_n512_ln(const GemmP& p, void* t, long long ldt, float* mean, float* rstd, const float* gamma, const float* beta, float eps,
                               hipStream_t st);
 bool pero_launch_gemm_n512_lnb(const GemmP& p, const void* t, long long ldt, const float* rstd, const float* gamma, const float* beta, float* work,
                                int* grid_out, hipStream_t st);
-// EP_* epilogue mode (gemm_e_common.hpp) of a stored bf16 product on the eight-phase tiles, from its flags and pointers; -1: that combination (or a
-// side input whose stride does not fit 32-bit byte offsets) is another kernel's.  Defined in gemm_e.hip; a launcher adds the restrictions of its own.
-int pero_stored_epilogue(const GemmP& p);
+
+// ---- host arithmetic shared by the split-K launchers
+constexpr int PERO_BK128 = 64;   // K-step of both 128x128 kernels (T_BK, O_BK): gemm_plan chunks K for either
+// `*k_split` slices of whole bk-wide K-steps: returns the chunk length and leaves in *k_split the slice count those chunks really make (<= 1: one slice, K)
+static inline long long pero_k_chunk(long long K, int bk, int* k_split) {
+  if (*k_split <= 1) { *k_split = 1; return K; }
+  const long long steps = K / bk, per = (steps + *k_split - 1) / *k_split;
+  *k_split = (int)((steps + per - 1) / per);
+  return per * bk;
+}
+// can `tiles` x `ks` work items be dealt so that every XCD (workgroup index % 8) keeps the same few k-slices?
+static inline bool pero_xcd_slices(long long tiles, int ks) {
+  return (ks == 1 || ks == 2 || ks == 4 || ks % 8 == 0) && (tiles * ks) % 8 == 0 && (ks >= 8 || tiles % (8 / ks) == 0);
+}
+// LAUNCH_(TA, TB, OUTF32) with the three template arguments as constants
+#define PERO_LAYOUT_LADDER(LAUNCH_, ta_, tb_, of_)                                                                  \
+  do {                                                                                                              \
+    if (!(ta_) && !(tb_)) { if (of_) LAUNCH_(false, false, true); else LAUNCH_(false, false, false); }              \
+    else if (!(ta_) && (tb_)) { if (of_) LAUNCH_(false, true, true); else LAUNCH_(false, true, false); }            \
+    else if ((ta_) && (tb_)) { if (of_) LAUNCH_(true, true, true); else LAUNCH_(true, true, false); }               \
+    else { if (of_) LAUNCH_(true, false, true); else LAUNCH_(true, false, false); }                                 \
+  } while (0)
 
 // ---- host helpers of the persistent launchers
 // CU count rounded down to a multiple of 8 (a grid is dealt to the 8 XCDs in turn), at least 8

@@ -664,20 +664,19 @@ static int e256_splitk_slices(long long tiles, long long steps, int k_split, boo
     if (ks * tiles * 10 < kx * tiles * 9) ks = kx;
   }
   while (ks > 1 && steps / ks < 2) ks--;
-  if (xcd_ok) *xcd_ok = (ks == 1 || ks == 2 || ks == 4 || ks % 8 == 0) && (tiles * ks) % 8 == 0 && (ks >= 8 || tiles % (8 / ks) == 0);
+  if (xcd_ok) *xcd_ok = pero_xcd_slices(tiles, ks);
   return ks;
 }
 // Bytes of caller-owned workspace with which a split-K product of this shape runs DETERMINISTICALLY on this kernel: every (tile, slice)
-// work item leaves its f32 partial tile there by plain stores and pero_splitk_reduce_k adds the slices of a tile in slice order.  0: the
-// shape does not take this kernel or has one slice.  Without (enough) workspace the product falls back to f32 atomics.
-long long pero_gemm_e256_splitk_ws_bytes(long long M, long long N, long long K, int k_split) {
-  if (M % E_BM || N % E_BN || K % E_BK || K < 2 * E_BK) return 0;
-  const long long tiles = (M / E_BM) * (N / E_BN);
-  const int ks = e256_splitk_slices(tiles, K / E_BK, k_split, nullptr);
-  return ks > 1 ? tiles * ks * (long long)(E_BM * E_BN * sizeof(float)) : 0;
+// work item leaves its f32 partial tile there by plain stores and pero_splitk_reduce_k adds the slices of a tile in slice order.  0: one
+// slice.  Without (enough) workspace the product falls back to f32 atomics.
+long long pero_gemm_e256_splitk_ws_bytes(long long M, long long N, int slices) {
+  return slices > 1 ? (M / E_BM) * (N / E_BN) * slices * (long long)(E_BM * E_BN * sizeof(float)) : 0;
 }
 
-int pero_stored_epilogue(const GemmP& p) {
+// EP_* epilogue mode of a stored bf16 product on this kernel, from its flags and pointers; -1: that combination (or a side input whose stride does not
+// fit 32-bit byte offsets) is another kernel's.
+static int e256_stored_epilogue(const GemmP& p) {
   const bool relu = p.flags & PERO_GEMM_RELU, bits = p.flags & PERO_GEMM_RELU_BITS, rowdot = p.flags & PERO_GEMM_ROWDOT, cs = p.flags & PERO_GEMM_COLSUM;
   int epi;
   if (rowdot) { if (relu || bits || cs || p.resid || !p.gate || !p.bias) return -1; epi = EP_ROWDOT; }
@@ -696,49 +695,56 @@ int pero_stored_epilogue(const GemmP& p) {
 }
 
 // Qualifies: one problem (batch 1), bf16 operands; stored bf16 output (alpha == 1) or a split-K f32 product; M % 256 == N % 256 == K % 64 == 0, K >= 128.
-// ws / ws_bytes: the caller's workspace for the split-K partial tiles (pero_gemm's `workspace`); never allocated here.
-bool pero_launch_gemm_e256(const GemmP& p0, long long batch, int k_split, bool ta, bool tb, bool out_f32, hipStream_t st, void* ws,
-                           long long ws_bytes) {
+bool pero_gemm_e256_takes(const GemmP& p0, long long batch, int k_split, bool out_f32, int* slices) {
   if (p0.M % E_BM || p0.N % E_BN || p0.K % E_BK || p0.K < 2 * E_BK || batch != 1) return false;
-  int ks = 0;
   if (p0.flags & PERO_GEMM_ATOMIC) {
-    // split-K: f32 C, plain product, equal slices of whole K-tiles, one slice set per XCD
+    // split-K: f32 C, plain product
     if (!out_f32 || p0.bias || p0.resid || p0.gate || (p0.flags & ~(PERO_GEMM_ATOMIC | PERO_GEMM_TRANS_A | PERO_GEMM_TRANS_B | PERO_GEMM_TILE_V | PERO_GEMM_TILE256))) return false;
-    const long long tiles = (p0.M / E_BM) * (p0.N / E_BN), steps = p0.K / E_BK;
-    bool xcd_ok = false;
-    ks = e256_splitk_slices(tiles, steps, k_split, &xcd_ok);
     if (!pero_ld_fits32({p0.lda, p0.ldb})) return false;
-    GemmP p = p0;
-    p.kchunk = 0;
-    dim3 grid((unsigned)(tiles * ks)), block(512);
-    const int nsl = ks;
-    const bool ws_ok = ws && (((size_t)ws) & 15) == 0 && ws_bytes >= tiles * ks * (long long)(E_BM * E_BN * sizeof(float));
-    p.resid = (g_opt.splitk_workspace && ws_ok && nsl > 1) ? ws : nullptr;
-    auto reduce = [&]() {
-      if (p.resid)
-        hipLaunchKernelGGL(pero_splitk_reduce_k, dim3((unsigned)(tiles * 64)), dim3(256), 0, st, (const f4v*)p.resid, (float*)p.C, (long long)p.ldc,
-                           (int)(p.N / E_BN), nsl, p.alpha, p.ldc % 4 == 0 && (((size_t)p.C) & 15) == 0);
-    };
-    if (!xcd_ok) {
-      ks = -ks;
-      p.kchunk = g_opt.splitk_table ? 1 : 0;   // work items handed out XCD by XCD (esplitk_xcd_item)
-    }
-#define LAUNCH_ES(TA_, TB_)                                                                                                \
-  do {                                                                                                                     \
-    PERO_LDS_ATTR((gemm_bf16_e256<TA_, TB_, EP_SPLITK>), E_LDS_BYTES);                                                     \
-    hipLaunchKernelGGL((gemm_bf16_e256<TA_, TB_, EP_SPLITK>), grid, block, E_LDS_BYTES, st, p, ks);                       \
-  } while (0)
-    if (!ta && !tb) LAUNCH_ES(false, false); else if (!ta && tb) LAUNCH_ES(false, true); else if (ta && tb) LAUNCH_ES(true, true); else LAUNCH_ES(true, false);
-#undef LAUNCH_ES
-    reduce();
+    *slices = e256_splitk_slices((p0.M / E_BM) * (p0.N / E_BN), p0.K / E_BK, k_split, nullptr);
     return true;
   }
   if (k_split > 1 || out_f32 || (p0.flags & PERO_GEMM_ACCUM)) return false;
   if (p0.alpha != 1.0f) return false;
   if (!pero_ld_fits32({p0.lda, p0.ldb, p0.ldc})) return false;
-  const int epi = pero_stored_epilogue(p0);
+  const int epi = e256_stored_epilogue(p0);
   if (epi < 0) return false;
-  if (epi != EP_PLAIN && (ta || tb)) return false;   // the fused epilogues exist for the K-contiguous products only
+  if (epi != EP_PLAIN && (p0.flags & (PERO_GEMM_TRANS_A | PERO_GEMM_TRANS_B))) return false;   // the fused epilogues exist for the K-contiguous products only
+  *slices = 1;
+  return true;
+}
+// ws / ws_bytes: the caller's workspace for the split-K partial tiles (pero_gemm's `workspace`); never allocated here.
+void pero_gemm_e256_launch(const GemmP& p0, int k_split, hipStream_t st, void* ws, long long ws_bytes) {
+  const bool ta = p0.flags & PERO_GEMM_TRANS_A, tb = p0.flags & PERO_GEMM_TRANS_B;
+  int ks = 0;
+  if (p0.flags & PERO_GEMM_ATOMIC) {
+    // equal slices of whole K-tiles, one slice set per XCD
+    const long long tiles = (p0.M / E_BM) * (p0.N / E_BN), steps = p0.K / E_BK;
+    bool xcd_ok = false;
+    ks = e256_splitk_slices(tiles, steps, k_split, &xcd_ok);
+    GemmP p = p0;
+    p.kchunk = 0;
+    dim3 grid((unsigned)(tiles * ks)), block(512);
+    const int nsl = ks;
+    const bool ws_ok = ws && (((size_t)ws) & 15) == 0 && ws_bytes >= pero_gemm_e256_splitk_ws_bytes(p.M, p.N, nsl);
+    p.resid = (g_opt.splitk_workspace && ws_ok && nsl > 1) ? ws : nullptr;
+    if (!xcd_ok) {
+      ks = -ks;
+      p.kchunk = g_opt.splitk_table ? 1 : 0;   // work items handed out XCD by XCD (esplitk_xcd_item)
+    }
+#define LAUNCH_ES(TA_, TB_, OF_)                                                                                           \
+  do {                                                                                                                     \
+    PERO_LDS_ATTR((gemm_bf16_e256<TA_, TB_, EP_SPLITK>), E_LDS_BYTES);                                                     \
+    hipLaunchKernelGGL((gemm_bf16_e256<TA_, TB_, EP_SPLITK>), grid, block, E_LDS_BYTES, st, p, ks);                       \
+  } while (0)
+    PERO_LAYOUT_LADDER(LAUNCH_ES, ta, tb, true);
+#undef LAUNCH_ES
+    if (p.resid)
+      hipLaunchKernelGGL(pero_splitk_reduce_k, dim3((unsigned)(tiles * 64)), dim3(256), 0, st, (const f4v*)p.resid, (float*)p.C, (long long)p.ldc,
+                         (int)(p.N / E_BN), nsl, p.alpha, p.ldc % 4 == 0 && (((size_t)p.C) & 15) == 0);
+    return;
+  }
+  const int epi = e256_stored_epilogue(p0);
   GemmP p = p0;
   p.kchunk = p.K;
   const long long nt = (p.M / E_BM) * (p.N / E_BN);
@@ -779,5 +785,4 @@ bool pero_launch_gemm_e256(const GemmP& p0, long long batch, int k_split, bool t
   else if (ta && tb) LAUNCH_E(true, true, EP_PLAIN);
   else LAUNCH_E(true, false, EP_PLAIN);
 #undef LAUNCH_E
-  return true;
 }

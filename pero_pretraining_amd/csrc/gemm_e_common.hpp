@@ -1,5 +1,5 @@
-// Shared by the three kernels on the eight-phase schedule: gemm_bf16_e256 (gemm_e.hip, where the schedule is described), gemm_bf16_d128
-// (gemm_d.hip) and gemm_bf16_n512 (gemm_n.hip): the epilogue modes, the uncounted loads / stores and their waits, the LDS-DMA addressing and
+// Shared by the two kernels on the eight-phase schedule: gemm_bf16_e256 (gemm_e.hip, where the schedule is described) and gemm_bf16_n512
+// (gemm_n.hip): the epilogue modes, the uncounted loads / stores and their waits, the LDS-DMA addressing and
 // the primitives of a phase.
 #pragma once
 #include "gemm_common.hpp"

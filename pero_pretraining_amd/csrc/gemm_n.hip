@@ -661,22 +661,21 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_n512(GemmP p, LnP q) {
 #undef N_RD_B
 }
 // "gemm_nw" = 1: N = 512 stored products with the plain / residual epilogue on the row-complete tile
-bool pero_launch_gemm_n512(const GemmP& p0, long long batch, bool ta, bool tb, bool out_f32, hipStream_t st) {
-  if (!g_opt.gemm_nw || batch != 1 || ta || tb || out_f32 || p0.N != 512 || p0.M % N_BM || p0.K % E_BK || p0.K < 3 * E_BK) return false;
-  if (p0.alpha != 1.0f || p0.gate || (p0.flags & ~(PERO_GEMM_TILE256))) return false;   // bias and residual only
-  if (!pero_ld_fits32({p0.lda, p0.ldb, p0.ldc, p0.resid ? p0.ldr : 0})) return false;
-  const long long nt = p0.M / N_BM;
-  const unsigned G = pero_persistent_grid(nt);
-  GemmP p = p0;
+bool pero_gemm_n512_takes(const GemmP& p0, long long batch, bool out_f32) {
+  if (!g_opt.gemm_nw || batch != 1 || out_f32 || p0.N != 512 || p0.M % N_BM || p0.K % E_BK || p0.K < 3 * E_BK) return false;
+  if (p0.alpha != 1.0f || p0.gate || (p0.flags & ~(PERO_GEMM_TILE256))) return false;   // bias and residual only, K-contiguous operands
+  return pero_ld_fits32({p0.lda, p0.ldb, p0.ldc, p0.resid ? p0.ldr : 0});
+}
+void pero_gemm_n512_launch(const GemmP& p, hipStream_t st) {
+  const unsigned G = pero_persistent_grid(p.M / N_BM);
   const LnP q = {nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr};
 #define LAUNCH_N(EP_, BI_)                                                                          \
   do {                                                                                              \
     PERO_LDS_ATTR((gemm_bf16_n512<EP_, BI_>), N_LDS_BYTES);                                          \
     hipLaunchKernelGGL((gemm_bf16_n512<EP_, BI_>), dim3(G), dim3(512), N_LDS_BYTES, st, p, q);       \
   } while (0)
-  if (p0.resid) { if (p0.bias) LAUNCH_N(EP_RESID, true); else LAUNCH_N(EP_RESID, false); }
-  else { if (p0.bias) LAUNCH_N(EP_PLAIN, true); else LAUNCH_N(EP_PLAIN, false); }
-  return true;
+  if (p.resid) { if (p.bias) LAUNCH_N(EP_RESID, true); else LAUNCH_N(EP_RESID, false); }
+  else { if (p.bias) LAUNCH_N(EP_PLAIN, true); else LAUNCH_N(EP_PLAIN, false); }
 }
 // y = A W^T + bias + resid (bf16, stored), t = LayerNorm(y) * gamma + beta (bf16), mean / rstd of every row: one launch on the row-complete
 // tile.  false: the shape does not take it (N must be 512).

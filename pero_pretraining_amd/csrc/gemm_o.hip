@@ -238,35 +238,22 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_o128(GemmP p, int ks_xcd) {
 }
 
 
-bool pero_launch_gemm_o128(const GemmP& p0, long long batch, int k_split, bool ta, bool tb, bool out_f32, hipStream_t st) {
-  if (p0.M % O_BM || p0.N % O_BN || p0.K % O_BK) return false;
-  GemmP p = p0;
-  if (k_split > 1) {
-    const long long steps = p.K / O_BK;
-    const long long per = (steps + k_split - 1) / k_split;
-    p.kchunk = per * O_BK;
-    k_split = (int)((steps + per - 1) / per);
-  } else {
-    p.kchunk = p.K;
-    k_split = 1;
-  }
-  dim3 grid((unsigned)((p.M / O_BM) * (p.N / O_BN)), (unsigned)batch, (unsigned)k_split), block(256);
-  int ks_xcd = 0;
+static_assert(O_BK == PERO_BK128, "gemm_plan chunks K in O_BK steps");
+bool pero_gemm_o128_takes(const GemmP& p) { return p.M % O_BM == 0 && p.N % O_BN == 0 && p.K % O_BK == 0; }
+void pero_gemm_o128_launch(const GemmP& p, long long batch, int k_split, bool out_f32, hipStream_t st) {
+  const bool ta = p.flags & PERO_GEMM_TRANS_A, tb = p.flags & PERO_GEMM_TRANS_B;
   const long long tiles = (p.M / O_BM) * (p.N / O_BN);
-  if (g_opt.splitk_xcd && batch == 1 && k_split > 1 && (k_split == 2 || k_split == 4 || k_split % 8 == 0) && (tiles * k_split) % 8 == 0 &&
-      (k_split >= 8 || tiles % (8 / k_split) == 0)) {
+  dim3 grid((unsigned)tiles, (unsigned)batch, (unsigned)k_split), block(256);
+  int ks_xcd = 0;
+  if (g_opt.splitk_xcd && batch == 1 && k_split > 1 && pero_xcd_slices(tiles, k_split)) {
     ks_xcd = k_split;
     grid = dim3((unsigned)(tiles * k_split), 1, 1);
   }
 #define LAUNCH_O(TA_, TB_, OF_)                                                                                           \
   do {                                                                                                                    \
     PERO_LDS_ATTR((gemm_bf16_o128<TA_, TB_, OF_>), O_LDS_BYTES);                                                          \
-    hipLaunchKernelGGL((gemm_bf16_o128<TA_, TB_, OF_>), grid, block, O_LDS_BYTES, st, p, ks_xcd);                                 \
+    hipLaunchKernelGGL((gemm_bf16_o128<TA_, TB_, OF_>), grid, block, O_LDS_BYTES, st, p, ks_xcd);                         \
   } while (0)
-  if (!ta && !tb) { if (out_f32) LAUNCH_O(false, false, true); else LAUNCH_O(false, false, false); }
-  else if (!ta && tb) { if (out_f32) LAUNCH_O(false, true, true); else LAUNCH_O(false, true, false); }
-  else if (ta && tb) { if (out_f32) LAUNCH_O(true, true, true); else LAUNCH_O(true, true, false); }
-  else { if (out_f32) LAUNCH_O(true, false, true); else LAUNCH_O(true, false, false); }
+  PERO_LAYOUT_LADDER(LAUNCH_O, ta, tb, out_f32);
 #undef LAUNCH_O
-  return true;
 }

@@ -298,35 +298,21 @@ __global__ __launch_bounds__(512, 4) void gemm_bf16_r256(GemmP p, int ks_xcd) {
   }
 }
 
-bool pero_launch_gemm_r256(const GemmP& p0, long long batch, int k_split, bool ta, bool tb, bool out_f32, hipStream_t st) {
-  if (p0.M % R_BM || p0.N % R_BN || p0.K % R_BK) return false;
-  GemmP p = p0;
-  if (k_split > 1) {
-    const long long steps = p.K / R_BK;
-    const long long per = (steps + k_split - 1) / k_split;
-    p.kchunk = per * R_BK;
-    k_split = (int)((steps + per - 1) / per);
-  } else {
-    p.kchunk = p.K;
-    k_split = 1;
-  }
-  dim3 grid((unsigned)((p.M / R_BM) * (p.N / R_BN)), (unsigned)batch, (unsigned)k_split), block(512);
-  int ks_xcd = 0;
+bool pero_gemm_r256_takes(const GemmP& p) { return p.M % R_BM == 0 && p.N % R_BN == 0 && p.K % R_BK == 0; }
+void pero_gemm_r256_launch(const GemmP& p, long long batch, int k_split, bool out_f32, hipStream_t st) {
+  const bool ta = p.flags & PERO_GEMM_TRANS_A, tb = p.flags & PERO_GEMM_TRANS_B;
   const long long tiles = (p.M / R_BM) * (p.N / R_BN);
-  if (batch == 1 && k_split > 1 && (k_split == 2 || k_split == 4 || k_split % 8 == 0) && (tiles * k_split) % 8 == 0 &&
-      (k_split >= 8 || tiles % (8 / k_split) == 0)) {
+  dim3 grid((unsigned)tiles, (unsigned)batch, (unsigned)k_split), block(512);
+  int ks_xcd = 0;
+  if (batch == 1 && k_split > 1 && pero_xcd_slices(tiles, k_split)) {
     ks_xcd = k_split;
     grid = dim3((unsigned)(tiles * k_split), 1, 1);
   }
 #define LAUNCH_R(TA_, TB_, OF_)                                                                                            \
   do {                                                                                                                     \
     PERO_LDS_ATTR((gemm_bf16_r256<TA_, TB_, OF_>), R_LDS_BYTES);                                                           \
-    hipLaunchKernelGGL((gemm_bf16_r256<TA_, TB_, OF_>), grid, block, R_LDS_BYTES, st, p, ks_xcd);                                  \
+    hipLaunchKernelGGL((gemm_bf16_r256<TA_, TB_, OF_>), grid, block, R_LDS_BYTES, st, p, ks_xcd);                          \
   } while (0)
-  if (!ta && !tb) { if (out_f32) LAUNCH_R(false, false, true); else LAUNCH_R(false, false, false); }
-  else if (!ta && tb) { if (out_f32) LAUNCH_R(false, true, true); else LAUNCH_R(false, true, false); }
-  else if (ta && tb) { if (out_f32) LAUNCH_R(true, true, true); else LAUNCH_R(true, true, false); }
-  else { if (out_f32) LAUNCH_R(true, false, true); else LAUNCH_R(true, false, false); }
+  PERO_LAYOUT_LADDER(LAUNCH_R, ta, tb, out_f32);
 #undef LAUNCH_R
-  return true;
 }

@@ -35,7 +35,7 @@ def ensure_grad(p):
 RELU_GATE_BITS = True    # linear1's ReLU leaves a bit mask (free in its epilogue); linear2's input gradient reads a byte per 8 columns, all of a
                          # tile's bytes ahead of the staging barriers, instead of eight dependent 16-byte gate rows: step -0.7 %
 RELU_BITS_TILED = True   # the mask per 256-column block ([N/256][M][32 B]) when N % 256 == 0: a tile's mask is whole cache lines, and linear1's product may walk its
-                         # tiles like the other K = 512 products (ops.gemm bits_tiled; csrc/gemm_e.hip pero_launch_gemm_e256)
+                         # tiles like the other K = 512 products (ops.gemm bits_tiled; csrc/gemm_e.hip pero_gemm_e256_launch)
 
 
 def bits_tiled(n):

@@ -1,5 +1,6 @@
 """Tensor-level wrappers over the C ABI (libpero_hip.so).  PyTorch supplies device memory and the
 current HIP stream; all arithmetic happens in the hand-written kernels.  No CPU fallback."""
+import ctypes
 import threading
 
 import numpy as np
@@ -20,7 +21,7 @@ def dt(t_or_dtype):
 
 
 def ptr(t):
-    return None if t is None else t.data_ptr()
+    return t.data_ptr() if isinstance(t, torch.Tensor) else t   # None, or a raw address
 
 
 def stream():
@@ -89,6 +90,23 @@ def gemm_raw(A, B, C, M, N, K, lda, ldb, ldc, *, bias=None, residual=None, gate=
         fast = idt == PERO_BF16 and M % 128 == 0 and N % 128 == 0 and K % 64 == 0 and not (flags & GEMM_FORCE_GENERIC)
         lay = ("T" if flags & GEMM_TRANS_A else "N") + ("T" if flags & GEMM_TRANS_B else "N")
         _timeline(e0, 2.0 * M * N * K * batch, ("gemm_bf16_tile" if fast else "gemm_generic") + ":" + lay)
+
+
+def gemm_plan(A, B, C, M, N, K, lda, ldb, ldc, *, bias=None, residual=None, gate=None, ldr=0, ldg=0, batch=1,
+              batch_inner=1, sA=(0, 0), sB=(0, 0), sC=(0, 0), alpha=1.0, flags=0, k_split=1, in_dtype=None,
+              out_dtype=None):
+    """What gemm_raw would run for these arguments (pero_gemm_plan; nothing is launched, the operands may be made-up addresses):
+    (kernel family - a name of _lib.GEMM_KERNELS, k-slices, extra pass over C - None / "colsum" / "rowdot").  Raises where pero_gemm would refuse."""
+    ks, extra = ctypes.c_int(0), ctypes.c_int(0)
+    idt = dt(A) if in_dtype is None else in_dtype
+    odt = dt(C) if out_dtype is None else out_dtype
+    h = _lib.lib()
+    rc = h.pero_gemm_plan(ptr(A), ptr(B), ptr(C), ptr(bias), ptr(residual), ptr(gate), M, N, K, lda, ldb, ldc, ldr, ldg,
+                          batch, batch_inner, sA[0], sA[1], sB[0], sB[1], sC[0], sC[1], float(alpha), int(flags), int(k_split),
+                          idt, odt, None, 0, None, ctypes.byref(ks), ctypes.byref(extra))
+    if rc <= 0:
+        raise _lib.PeroHipError(f"pero_gemm_plan failed ({rc}): {h.pero_last_error().decode()}")
+    return _lib.GEMM_KERNELS[rc], ks.value, _lib.GEMM_PASSES[extra.value]
 
 
 def gemm(a, b, out=None, *, bias=None, residual=None, gate=None, trans_a=False, trans_b=False, relu=False,

@@ -127,17 +127,17 @@ def test_argument_validation_without_gpu():
 def test_set_option_takes_the_tested_knobs_and_no_diagnostic_variant():
     """Every option of the library's table (csrc/options.hpp) is accepted (each set to its default here, so the process state does not change); the option
     that selected the eight-phase kernel's diagnostic builds, some of which gave wrong results by design, is gone and is rejected like any
-    unknown name, and so are the two that selected the retired attention variants."""
+    unknown name, and so are the two that selected the retired attention variants and the one of the retired gemm_bf16_d128."""
     from pero_pretraining_amd import _lib
     h = _lib.lib()
     defaults = {"gemm_policy": 0, "attn_bwd_pair": 1, "attn_order": 32, "splitk_workspace": 1, "splitk_table": 1,
-                "gemm_nw": 0, "gemm_d128": 0, "gemm_e_walk": 1, "gemm_e256_min": 192, "gemm_e_splitk_min": 4, "splitk_xcd": 1, "splitk_nearest": 0,
+                "gemm_nw": 0, "gemm_e_walk": 1, "gemm_e256_min": 192, "gemm_e_splitk_min": 4, "splitk_xcd": 1, "splitk_nearest": 0,
                 "splitk_items": 512}
     for name, value in defaults.items():
         assert h.pero_set_option(name.encode(), value) == 0, name
     assert h.pero_set_option(b"gemm_e_var", 1) == -1
     assert b"unknown option gemm_e_var" in h.pero_last_error()
-    for name in (b"attn_pipe", b"attn_lh"):
+    for name in (b"attn_pipe", b"attn_lh", b"gemm_d128"):
         assert h.pero_set_option(name, 1) == -1
         assert b"unknown option " + name in h.pero_last_error()
 
@@ -267,7 +267,7 @@ def test_masked_head_mode_is_validated_on_the_host():
 
 
 def test_inline_asm_vector_memory_of_the_tile_gemm_passes_the_isa_lint(tmp_path):
-    """tools/check_async_loads.py on the ISA of the three eight-phase kernel files csrc/gemm_e.hip, gemm_d.hip, gemm_n.hip (hipcc cross-compiles
+    """tools/check_async_loads.py on the ISA of the two eight-phase kernel files csrc/gemm_e.hip, gemm_n.hip (hipcc cross-compiles
     without a GPU): no instruction touches the destination of
     an inline-asm load before a counted s_waitcnt has retired it, and no vector-memory instruction reads an SGPR that a v_readlane_b32 (a
     restored spill) wrote fewer than five wait states earlier - the compiler pads neither for instructions inside an asm string (round 3: the
@@ -279,7 +279,7 @@ def test_inline_asm_vector_memory_of_the_tile_gemm_passes_the_isa_lint(tmp_path)
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    files = {"gemm_e": "gemm_bf16_e256", "gemm_d": "gemm_bf16_d128", "gemm_n": "gemm_bf16_n512"}
+    files = {"gemm_e": "gemm_bf16_e256", "gemm_n": "gemm_bf16_n512"}
     compiles = {name: subprocess.Popen([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-ffp-contract=off",
                                         "-Wno-unused-value", "-S", "--cuda-device-only",
                                         os.path.join(root, "pero_pretraining_amd", "csrc", name + ".hip"), "-o", str(tmp_path / (name + ".s"))],

@@ -1,11 +1,24 @@
-"""The eight-phase persistent 256x256x64 bf16 GEMM (csrc/gemm_e.hip) and its siblings on the same schedule (gemm_bf16_d128 in csrc/gemm_d.hip,
-gemm_bf16_n512 in csrc/gemm_n.hip) against exact / f32 references and against the other
-tile kernels (bit for bit): every operand layout, every fused epilogue, the split-K mode, many tiles per workgroup."""
+"""The eight-phase persistent 256x256x64 bf16 GEMM (csrc/gemm_e.hip) and its sibling on the same schedule (gemm_bf16_n512 in csrc/gemm_n.hip)
+against exact / f32 references and against the other
+tile kernels (bit for bit): every operand layout, every fused epilogue, the split-K mode, many tiles per workgroup.  Every test also asserts the
+kernel family that each of its products takes (pero_gemm_plan): a product that policy 20 does not send to the eight-phase kernel is named as such."""
 import numpy as np
 import pytest
 import torch
 
+import gemm_families
+
 pytestmark = pytest.mark.gpu
+
+
+class _Recorded:
+    """the ops module, plus `families`: the kernel family of every product issued through it so far"""
+
+    def __init__(self, ops, families):
+        self._ops, self.families = ops, families
+
+    def __getattr__(self, name):
+        return getattr(self._ops, name)
 
 
 @pytest.fixture()
@@ -13,8 +26,11 @@ def e256():
     from pero_pretraining_amd import _lib, ops
     lib = _lib.lib()
     lib.pero_set_option(b"gemm_policy", 20)
-    yield ops
-    lib.pero_set_option(b"gemm_policy", 0)
+    try:
+        with gemm_families.recorded() as families:
+            yield _Recorded(ops, families)
+    finally:
+        lib.pero_set_option(b"gemm_policy", 0)
 
 
 def _setpol(p):
@@ -33,12 +49,14 @@ def test_layouts_exact_integers(e256, ta, tb, K):
     ref = (a.t() if ta else a) @ (b.t() if tb else b).t()
     out = e256.gemm(a.cuda().bfloat16(), b.cuda().bfloat16(), trans_a=ta, trans_b=tb)
     assert torch.equal(out.float().cpu(), ref.bfloat16().float())
+    assert e256.families == ["e256"]
 
 
 @pytest.mark.parametrize("M,N,K", [(1024, 512, 512), (1024, 1536, 192), (2048, 256, 128)])
 def test_epilogues_match_the_other_tile_kernel_bit_for_bit(e256, M, N, K):
     """bias / ReLU / residual / bit mask out and in / column sums / row dots: same bytes as gemm_bf16_r256 (policy 7), whose
-    epilogue is the f32 acc * alpha + bias (+ residual) -> one rounding that every tile kernel of the library implements."""
+    epilogue is the f32 acc * alpha + bias (+ residual) -> one rounding that every tile kernel of the library implements.  The gated product
+    WITH an input bias is gemm_bf16_r256's under policy 20 as well (asserted below): that comparison pins the hand-over, not two kernels."""
     ops = e256
     torch.manual_seed(M + N + K)
     x = (torch.randn(M, K, device="cuda") * 0.5).bfloat16()
@@ -57,6 +75,7 @@ def test_epilogues_match_the_other_tile_kernel_bit_for_bit(e256, M, N, K):
     for kw in ({}, {"bias": bias}, {"bias": bias, "relu": True}, {"bias": bias, "residual": res}, {"residual": res}):
         a, b = both(lambda: ops.gemm(x, w, **kw))
         assert torch.equal(a, b), kw
+    assert ops.families == ["e256", "r256"] * 5
     ref = x.float() @ w.float().t()
     y = ops.gemm(x, w, bias=bias, residual=res)
     assert float((y.float() - (ref + bias + res.float())).abs().max()) <= 2e-2 * float(ref.abs().max())
@@ -73,6 +92,7 @@ def test_epilogues_match_the_other_tile_kernel_bit_for_bit(e256, M, N, K):
     gr = ops.gemm(x, w, gate=h)
     _setpol(20)
     assert torch.equal(gd, gr) and torch.equal(gd, ops.gemm(x, w, relu_bits=bits))
+    assert ops.families[10:] == ["e256"] * 4 + ["r256", "e256"]   # y, h, its plain twin, gd on the eight-phase kernel; gr (bf16 gate rows) on r256
     # ... and WITH an input bias (round-2 advisor finding: the e256 gate epilogue has no input-bias path and once dropped it silently; such a
     # product now goes to the 256x128x32 kernel at every tile count): the same bits under both policies, and the bias is really in them
     gb = ops.gemm(x, w, bias=bias, relu_bits=bits)
@@ -80,6 +100,7 @@ def test_epilogues_match_the_other_tile_kernel_bit_for_bit(e256, M, N, K):
     gb7 = ops.gemm(x, w, bias=bias, gate=h)
     _setpol(20)
     assert torch.equal(gb, gb7)
+    assert ops.families[16:] == ["r256", "r256"]   # under policy 20 too: the eight-phase gate epilogue has no input-bias path
     keep = h.float() > 0
     assert float(((gb.float() - (ref + bias)) * keep).abs().max()) <= 2e-2 * float(ref.abs().max()) and float((gb.float() * ~keep).abs().max()) == 0.0
     want_cs = 3.0 + gd.float().sum(0)
@@ -89,6 +110,7 @@ def test_epilogues_match_the_other_tile_kernel_bit_for_bit(e256, M, N, K):
         dots = torch.full((M, N // 128), 7.0, device="cuda")
         yd = ops.gemm(x, w, rowdot=(res, dots))
         assert torch.equal(yd, ops.gemm(x, w))
+        assert ops.families[18:] == ["e256", "e256"]
         dref = (yd.float() * res.float()).view(M, N // 128, 128).sum(-1)
         assert float((dots - dref).abs().max()) <= 1e-3 * max(1.0, float(dref.abs().max()))
 
@@ -111,6 +133,7 @@ def test_many_tiles_per_workgroup_and_repeatability(e256):
         _setpol(7)
         assert torch.equal(ops.gemm(x[:4096], w, **({"residual": res[:4096]} if kw else {})), y0[:4096])
         _setpol(20)
+    assert ops.families == (["e256"] * 11 + ["r256"]) * 2
 
 
 @pytest.mark.parametrize("N,K,rows", [(512, 512, 8192), (1536, 512, 65536), (768, 256, 16384)])
@@ -128,6 +151,7 @@ def test_split_k_weight_gradient_mode(e256, N, K, rows):
     c = torch.ones(N, K, device="cuda")
     ops.gemm(dy, x, out=c, trans_a=True, trans_b=True, atomic=True, k_split=0, alpha=0.5)
     assert float((c.double() - (1.0 + 0.5 * ref)).abs().max()) <= 1e-5 * float(ref.abs().max()) * max(1, rows // 8192)
+    assert ops.families == ["e256_splitk"] * 5
 
 
 def test_split_k_partial_tiles_are_summed_in_slice_order(e256):
@@ -155,6 +179,7 @@ def test_split_k_partial_tiles_are_summed_in_slice_order(e256):
     ref = 0.25 + dy[:, :64].float().t() @ x.float()
     assert float((runs[0][:64] - ref).abs().max()) < 2e-3 * float(ref.abs().max())
     assert float((runs[0] - ca).abs().max()) < 1e-3 * float(ca.abs().max())
+    assert ops.families == ["e256_splitk"] * 4
 
 
 def test_strided_views_of_every_operand(e256):
@@ -178,6 +203,7 @@ def test_strided_views_of_every_operand(e256):
         yd = ops.gemm(x, w, rowdot=(res, dots))
         outs[pol] = (ca, yd, dots)
     _setpol(20)
+    assert ops.families == ["e256", "e256", "r256", "r256"]
     assert torch.equal(outs[20][0], outs[7][0]) and torch.equal(outs[20][1], outs[7][1])
     assert float((outs[20][2] - outs[7][2]).abs().max()) <= 1e-3 * float(outs[7][2].abs().max())
     ca = outs[20][0]
@@ -204,31 +230,33 @@ def test_bit_mask_per_256_column_block_is_the_row_mask_rearranged(M, N, K, polic
     bias = torch.randn(N, device="cuda")
     L.pero_set_option(b"gemm_policy", policy)
     try:
-        b0 = torch.zeros(M, N // 8, device="cuda", dtype=torch.uint8)
-        b1 = torch.zeros(M, N // 8, device="cuda", dtype=torch.uint8)
-        c0 = ops.gemm(x, w, bias=bias, relu=True, relu_bits=b0)
-        c1 = ops.gemm(x, w, bias=bias, relu=True, relu_bits=b1, bits_tiled=True)
-        assert torch.equal(c0, c1)
-        assert torch.equal(_tile_mask(b0, M, N), b1)
-        want = torch.zeros_like(b0)
-        pos = (c0 > 0).view(M, N // 8, 8).to(torch.int32)
-        want = (pos * (2 ** torch.arange(8, device="cuda", dtype=torch.int32))).sum(-1).to(torch.uint8)
-        assert torch.equal(b0, want)
-        g = torch.randint(0, 256, (M, N // 8), device="cuda", dtype=torch.uint8)
-        cs0, cs1 = torch.zeros(N, device="cuda"), torch.zeros(N, device="cuda")
-        d0 = ops.gemm(x, w, relu_bits=g, colsum_into=cs0)
-        d1 = ops.gemm(x, w, relu_bits=_tile_mask(g, M, N), colsum_into=cs1, bits_tiled=True)
-        assert torch.equal(d0, d1)
-        assert float((cs0 - cs1).abs().max()) <= 1e-4 * float(cs0.abs().max()) + 1e-2
-        for _ in range(3):
-            assert torch.equal(ops.gemm(x, w, relu_bits=_tile_mask(g, M, N), bits_tiled=True), d0)
+        with gemm_families.recorded() as families:
+            b0 = torch.zeros(M, N // 8, device="cuda", dtype=torch.uint8)
+            b1 = torch.zeros(M, N // 8, device="cuda", dtype=torch.uint8)
+            c0 = ops.gemm(x, w, bias=bias, relu=True, relu_bits=b0)
+            c1 = ops.gemm(x, w, bias=bias, relu=True, relu_bits=b1, bits_tiled=True)
+            assert torch.equal(c0, c1)
+            assert torch.equal(_tile_mask(b0, M, N), b1)
+            want = torch.zeros_like(b0)
+            pos = (c0 > 0).view(M, N // 8, 8).to(torch.int32)
+            want = (pos * (2 ** torch.arange(8, device="cuda", dtype=torch.int32))).sum(-1).to(torch.uint8)
+            assert torch.equal(b0, want)
+            g = torch.randint(0, 256, (M, N // 8), device="cuda", dtype=torch.uint8)
+            cs0, cs1 = torch.zeros(N, device="cuda"), torch.zeros(N, device="cuda")
+            d0 = ops.gemm(x, w, relu_bits=g, colsum_into=cs0)
+            d1 = ops.gemm(x, w, relu_bits=_tile_mask(g, M, N), colsum_into=cs1, bits_tiled=True)
+            assert torch.equal(d0, d1)
+            assert float((cs0 - cs1).abs().max()) <= 1e-4 * float(cs0.abs().max()) + 1e-2
+            for _ in range(3):
+                assert torch.equal(ops.gemm(x, w, relu_bits=_tile_mask(g, M, N), bits_tiled=True), d0)
+        assert families == ["e256" if policy == 20 else "r256"] * 7
     finally:
         L.pero_set_option(b"gemm_policy", 0)
 
 
 @pytest.mark.parametrize("M,N,K", [(16384, 2048, 512), (32768, 1536, 512), (16384, 4096, 256), (65536, 2048, 512)])
 def test_sequential_walk_of_a_row_panel_gives_the_same_bits(e256, M, N, K):
-    """Stored K <= 512 products walk the N-tiles of a 256-row panel partly one after the other (round 4, pero_launch_gemm_e256: `gemm_e_walk`, default on for the
+    """Stored K <= 512 products walk the N-tiles of a 256-row panel partly one after the other (round 4, pero_gemm_e256_launch: `gemm_e_walk`, default on for the
     plain / ReLU / bit-mask-gate epilogues): a different tile -> workgroup order and nothing else, so the output must equal the side-by-side order's bit for bit,
     every tile written exactly once (a guard band around the output view stays untouched), column sums equal up to the order of the atomics."""
     ops = e256
@@ -266,63 +294,9 @@ def test_sequential_walk_of_a_row_panel_gives_the_same_bits(e256, M, N, K):
                 assert float((gcs - wcs).abs().max()) <= 1e-4 * float(wcs.abs().max()) + 1e-2, kind
         ref = x[:512].float() @ w.float().t()
         assert float((run("plain", 1)[0][:512].float() - ref).abs().max()) <= 2e-2 * float(ref.abs().max())
+        assert ops.families == ["e256"] * 16
     finally:
         call("pero_set_option", b"gemm_e_walk", 1)
-
-
-@pytest.mark.parametrize("M,N,K", [(32768, 512, 192), (16384, 1024, 512), (65536, 2048, 512), (32768, 1536, 1024)])
-def test_two_workgroups_per_cu_tile_gives_the_bits_of_the_256x256_tile(e256, M, N, K):
-    """gemm_bf16_d128 (opt-in "gemm_d128": 256 x 128 tiles, four waves per workgroup, two independent workgroups per CU - round 4's measurement of
-    'the epilogue of one tile under the main loop of another', slower than gemm_bf16_e256 and therefore off): same K-tile and MFMA order per
-    output, so plain / bias / ReLU / bit-mask-out / bit-mask-gate products must agree bit for bit with the 256 x 256 tile; repeated launches give
-    identical bytes (its counted vmcnt waits); strided views of every operand."""
-    ops = e256
-    from pero_pretraining_amd._lib import call
-    torch.manual_seed(11)
-    xa = (torch.randn(M, K + 64, device="cuda") * 0.5).bfloat16()
-    wa = (torch.randn(N, K + 128, device="cuda") * 0.5).bfloat16()
-    x, w = xa[:, 64:], wa[:, :K]
-    bias = torch.randn(N, device="cuda")
-    gbits = torch.randint(0, 256, (M, N // 8), device="cuda", dtype=torch.uint8)
-
-    def run(kind):
-        ca = torch.full((M, N + 256), 7.0, device="cuda").bfloat16()
-        out = ca[:, 128:128 + N]
-        bits = torch.zeros(M, N // 8, device="cuda", dtype=torch.uint8)
-        if kind == "plain":
-            ops.gemm(x, w, out=out)
-        elif kind == "bias":
-            ops.gemm(x, w, out=out, bias=bias)
-        elif kind == "relu":
-            ops.gemm(x, w, out=out, bias=bias, relu=True)
-        elif kind == "relu_bits":
-            ops.gemm(x, w, out=out, bias=bias, relu=True, relu_bits=bits)
-        else:
-            ops.gemm(x, w, out=out, relu_bits=gbits)
-        assert torch.all(ca[:, :128] == 7.0) and torch.all(ca[:, 128 + N:] == 7.0)
-        return out.clone(), bits
-
-    try:
-        for kind in ("plain", "bias", "relu", "relu_bits", "gate"):
-            call("pero_set_option", b"gemm_d128", 0)
-            want, wbits = run(kind)
-            call("pero_set_option", b"gemm_d128", 64)
-            for _ in range(3):
-                got, gb = run(kind)
-                assert torch.equal(got, want), kind
-                assert torch.equal(gb, wbits), kind
-        # the column sums of the gated product (linear1's bias gradient): f32 atomics in both kernels, equal up to the order of the additions
-        cs0, cs1 = torch.zeros(N, device="cuda"), torch.zeros(N, device="cuda")
-        call("pero_set_option", b"gemm_d128", 0)
-        a = ops.gemm(x, w, relu_bits=gbits, colsum_into=cs0)
-        call("pero_set_option", b"gemm_d128", 64)
-        b = ops.gemm(x, w, relu_bits=gbits, colsum_into=cs1)
-        assert torch.equal(a, b)
-        ref = a.float().sum(0)
-        assert float((cs1 - ref).abs().max()) <= 1e-3 * float(ref.abs().max()) + 1e-2
-        assert float((cs1 - cs0).abs().max()) <= 1e-4 * float(ref.abs().max()) + 1e-2
-    finally:
-        call("pero_set_option", b"gemm_d128", 0)
 
 
 @pytest.mark.parametrize("M,K", [(1024, 192), (2176, 512), (65536, 1536), (131072, 2048)])
@@ -356,6 +330,7 @@ def test_row_complete_tile_gives_the_bits_of_the_256x256_tile(e256, M, K):
             assert torch.all(ca[:, :256] == 7.0) and torch.all(ca[:, 256 + N:] == 7.0)
             for _ in range(5):
                 assert torch.equal(ops.gemm(x, w, **kw), got), kw
+        assert ops.families == ((["e256"] if M % 256 == 0 else []) + ["n512"] * 6) * 4
     finally:
         L.pero_set_option(b"gemm_nw", 0)
 
@@ -395,6 +370,7 @@ def test_fused_linear_residual_layernorm(e256, M, K):
         # the launch that does not store y (the backward then reads t: pero_layernorm_bwd_out): the same t, mean, rstd, bit for bit
         yn, tn, mn, rn = ops.gemm_resid_layernorm(x, w, b, res, gamma, beta, 1e-5, store_y=False)
         assert yn is None and torch.equal(tn, t) and torch.equal(mn, mean) and torch.equal(rn, rstd)
+    assert ops.families == ["n512", "n512"]   # the unfused products (the fused launches are not pero_gemm's)
 
 
 @pytest.mark.parametrize("M,K", [(1024, 192), (2176, 1536), (131072 + 384, 2048), (65536, 512)])
@@ -421,6 +397,7 @@ def test_fused_input_gradient_layernorm_backward(e256, M, K):
         dt = ops.gemm(dy, wt, residual=res)
     finally:
         L.pero_set_option(b"gemm_nw", 0)
+    assert ops.families == ["n512"]
     dg0, db0, dx0s = (torch.zeros(512, device="cuda") for _ in range(3))
     dx0 = ops.layernorm_bwd_out(dt, t, rstd, gamma, beta, dg0, db0, dx0s)
     init = torch.arange(512, device="cuda", dtype=torch.float32) * 0.25
@@ -475,6 +452,7 @@ def test_fused_layernorm_epilogues_with_trained_weights_within_rows_kept(e256):
     y, t, mean, rstd = ops.gemm_resid_layernorm(xc, wc, bc, rc, gc, btc, 1e-5)
     assert bool(((t.double().cpu() - t_ref).abs() <= 2 ** -8 * t_ref.abs() + 2 ** -6 * gamma.double().abs()).all())
     dt = ops.gemm(ac, wtc, residual=r2c)
+    assert ops.families == ["e256"]
     errs = {}
     for path in ("rows_kept", "from_output", "fused_from_output"):
         dg, db, dxs = (torch.zeros(512, device="cuda") for _ in range(3))

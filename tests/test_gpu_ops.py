@@ -14,6 +14,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import gemm_families  # noqa: E402
 import parity_ref as R  # noqa: E402
 from oracle import pero_oracle as O  # noqa: E402
 
@@ -132,16 +133,18 @@ def test_gemm_bf16_t128_layouts_and_epilogues(ops, ta, tb):
     a = torch.randint(-3, 4, (K, M) if ta else (M, K), generator=g).float()
     b = torch.randint(-3, 4, (K, N) if tb else (N, K), generator=g).float()
     ref = (a.t() if ta else a) @ (b.t() if tb else b).t()
-    for od in (torch.bfloat16, torch.float32):
-        out = ops.gemm(dev(a, torch.bfloat16), dev(b, torch.bfloat16), trans_a=ta, trans_b=tb, out_dtype=od, extra_flags=64)
-        assert torch.equal(out.float().cpu(), ref.to(od).float())
-    bias = torch.randn(N, generator=g)
-    res = torch.randn(M, N, generator=g).bfloat16()
-    gate = torch.randn(M, N, generator=g).bfloat16()
-    full = torch.relu(0.5 * ref.double() + bias.double() + res.double()) * (gate.double() > 0)
-    out = ops.gemm(dev(a, torch.bfloat16), dev(b, torch.bfloat16), trans_a=ta, trans_b=tb, bias=dev(bias), residual=dev(res),
-                   gate=dev(gate), relu=True, alpha=0.5, extra_flags=64)
-    assert rel_err(out, full) < 2 ** -8
+    with gemm_families.recorded() as families:
+        for od in (torch.bfloat16, torch.float32):
+            out = ops.gemm(dev(a, torch.bfloat16), dev(b, torch.bfloat16), trans_a=ta, trans_b=tb, out_dtype=od, extra_flags=64)
+            assert torch.equal(out.float().cpu(), ref.to(od).float())
+        bias = torch.randn(N, generator=g)
+        res = torch.randn(M, N, generator=g).bfloat16()
+        gate = torch.randn(M, N, generator=g).bfloat16()
+        full = torch.relu(0.5 * ref.double() + bias.double() + res.double()) * (gate.double() > 0)
+        out = ops.gemm(dev(a, torch.bfloat16), dev(b, torch.bfloat16), trans_a=ta, trans_b=tb, bias=dev(bias), residual=dev(res),
+                       gate=dev(gate), relu=True, alpha=0.5, extra_flags=64)
+        assert rel_err(out, full) < 2 ** -8
+    assert families == ["t128"] * 3
 
 
 @pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, False), (True, True)])
@@ -157,16 +160,18 @@ def test_gemm_bf16_r256_o128_layouts_and_epilogues(ops, ta, tb, policy):
     ref = (a.t() if ta else a) @ (b.t() if tb else b).t()
     _lib.lib().pero_set_option(b"gemm_policy", policy)
     try:
-        for od in (torch.bfloat16, torch.float32):
-            out = ops.gemm(dev(a, torch.bfloat16), dev(b, torch.bfloat16), trans_a=ta, trans_b=tb, out_dtype=od)
-            assert torch.equal(out.float().cpu(), ref.to(od).float())
-        bias = torch.randn(N, generator=g)
-        res = torch.randn(M, N, generator=g).bfloat16()
-        gate = torch.randn(M, N, generator=g).bfloat16()
-        full = torch.relu(0.5 * ref.double() + bias.double() + res.double()) * (gate.double() > 0)
-        out = ops.gemm(dev(a, torch.bfloat16), dev(b, torch.bfloat16), trans_a=ta, trans_b=tb, bias=dev(bias), residual=dev(res),
-                       gate=dev(gate), relu=True, alpha=0.5)
-        assert rel_err(out, full) < 2 ** -8
+        with gemm_families.recorded() as families:
+            for od in (torch.bfloat16, torch.float32):
+                out = ops.gemm(dev(a, torch.bfloat16), dev(b, torch.bfloat16), trans_a=ta, trans_b=tb, out_dtype=od)
+                assert torch.equal(out.float().cpu(), ref.to(od).float())
+            bias = torch.randn(N, generator=g)
+            res = torch.randn(M, N, generator=g).bfloat16()
+            gate = torch.randn(M, N, generator=g).bfloat16()
+            full = torch.relu(0.5 * ref.double() + bias.double() + res.double()) * (gate.double() > 0)
+            out = ops.gemm(dev(a, torch.bfloat16), dev(b, torch.bfloat16), trans_a=ta, trans_b=tb, bias=dev(bias), residual=dev(res),
+                           gate=dev(gate), relu=True, alpha=0.5)
+            assert rel_err(out, full) < 2 ** -8
+        assert families == ["r256" if policy == 7 else "o128"] * 3
     finally:
         _lib.lib().pero_set_option(b"gemm_policy", 0)
 
@@ -897,20 +902,25 @@ def test_gemm_relu_gate_as_bit_mask(M, N, K):
     b = torch.randn(N, device="cuda")
     dy = (torch.randn(M, K, device="cuda") * 0.5).to(torch.bfloat16)
     wt = (torch.randn(N, K, device="cuda") * 0.2).to(torch.bfloat16)  # (in = N, out = K) transposed copy of the next weight
-    # (policy 20 sends every stored product to the eight-phase kernel whatever the tile count, policy 7 to the 256x128x32 one)
+    # (policy 20 sends the stored products its epilogues cover to the eight-phase kernel whatever the tile count, policy 7 to the 256x128x32 one)
     for tile_flags, policy in ((0, 0), (0, 7), (0, 20)):
         _lib.lib().pero_set_option(b"gemm_policy", policy)
-        bits = torch.zeros((M, N // 8), device="cuda", dtype=torch.uint8)
-        h = ops.gemm(x, w, bias=b, relu=True, relu_bits=bits, extra_flags=tile_flags)
-        h_ref = ops.gemm(x, w, bias=b, relu=True, extra_flags=tile_flags)
-        assert torch.equal(h, h_ref)
-        want = np.packbits((h.float() > 0).cpu().numpy(), axis=1, bitorder="little")
-        assert np.array_equal(bits.cpu().numpy(), want)
-        cs_a = torch.zeros(N, device="cuda"); cs_b = torch.zeros(N, device="cuda")
-        for kw_a, kw_b in (({}, {}), ({"colsum_into": cs_a}, {"colsum_into": cs_b})):
-            got = ops.gemm(dy, wt, relu_bits=bits, extra_flags=tile_flags, **kw_a)
-            ref = ops.gemm(dy, wt, gate=h, extra_flags=tile_flags, **kw_b)
-            assert torch.equal(got, ref)
+        with gemm_families.recorded() as families:
+            bits = torch.zeros((M, N // 8), device="cuda", dtype=torch.uint8)
+            h = ops.gemm(x, w, bias=b, relu=True, relu_bits=bits, extra_flags=tile_flags)
+            h_ref = ops.gemm(x, w, bias=b, relu=True, extra_flags=tile_flags)
+            assert torch.equal(h, h_ref)
+            want = np.packbits((h.float() > 0).cpu().numpy(), axis=1, bitorder="little")
+            assert np.array_equal(bits.cpu().numpy(), want)
+            cs_a = torch.zeros(N, device="cuda"); cs_b = torch.zeros(N, device="cuda")
+            for kw_a, kw_b in (({}, {}), ({"colsum_into": cs_a}, {"colsum_into": cs_b})):
+                got = ops.gemm(dy, wt, relu_bits=bits, extra_flags=tile_flags, **kw_a)
+                ref = ops.gemm(dy, wt, gate=h, extra_flags=tile_flags, **kw_b)
+                assert torch.equal(got, ref)
+        # the mask producer, its plain twin and the mask consumers run on the eight-phase kernel under policy 20 where its tile fits (N % 256 == 0,
+        # K >= 128); the reference products gated by bf16 rows are gemm_bf16_r256's under every policy (the eight-phase epilogues have no such gate)
+        e = "e256" if policy == 20 and N % 256 == 0 and K >= 128 else "r256"
+        assert families == [e, e, e, "r256", e, "r256"]
         # (some epilogues add the f32 values before the rounding, others - and the fall-back pass - the stored bf16 ones: which
         #  one runs depends on the policy; both are within the rounding of the stored result of its exact column sums)
         want_cs = got.float().sum(0)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Lint for the kernels whose vector-memory loads are issued by inline asm and waited for by COUNTED s_waitcnt vmcnt (gemm_e.hip, gemm_d.hip, gemm_n.hip): walks a
+"""Lint for the kernels whose vector-memory loads are issued by inline asm and waited for by COUNTED s_waitcnt vmcnt (gemm_e.hip, gemm_n.hip): walks a
 kernel's ISA in program order with the in-order vmcnt queue (loads, stores, LDS-DMA, atomics) and reports every instruction that READS or
 OVERWRITES the destination registers of a load that no s_waitcnt has retired yet - the compiler is free to copy or re-home the result of an
 asm load before the wait it cannot see (it did, under register pressure, in the first LayerNorm epilogue: values of not-yet-arrived loads
