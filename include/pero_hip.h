@@ -516,6 +516,45 @@ int pero_ctc_bwd(const void* logits, const int64_t* targets, const int64_t* inpu
 int pero_ctc_greedy(const void* logits, const int64_t* input_lengths, int64_t* out, int64_t* out_lengths, int64_t N, int64_t S, int64_t C,
                     int64_t blank, int dtype, void* stream);
 
+/* ---- CTC decoding and scoring (evaluation of a recogniser; csrc/ctc_decode.hip, DESIGN.md "CTC decoding") --------------
+ * pero_ctc_beam: CTC prefix beam search of width W, one line per workgroup, no class pruning, no language model.  logits,
+ * input_lengths, blank, dtype and the clamp of the lengths as for pero_ctc_greedy; all arithmetic f32 in the log domain,
+ * logp_t(c) = x[n][t][c] - row_lse[n S + t] (a -inf logit has logp -inf), (+) = log-sum-exp (all -inf -> -inf, never NaN).
+ *   A beam entry is a label string p with pb, pnb: the log-probabilities of its alignments ending in blank / in a non-blank.
+ *   Before frame 0 the beam is {(): pb = 0, pnb = -inf}.  At frame t < T every entry, with tot = pb (+) pnb and last label e, gives
+ *     stay:           p    gets pb' (+)= tot + logp_t(blank), and for p != (): pnb' (+)= pnb + logp_t(e);
+ *     extend, c != blank: p+c gets pnb' (+)= logp_t(c) + (c == e ? pb : tot).
+ *   Contributions to the same STRING are merged before ranking (a string has one node in the line's trie of prefixes, found or
+ *   created through a hash of (parent node, label) that keeps every node ever created: a prefix that left the beam and comes
+ *   back gets its old node, so an extension that stayed in the beam still merges with it).  The W candidates with the largest
+ *   finite total pb' (+) pnb' are kept, in rank order.
+ *   Tie rule (equal f32 totals): the candidates of a frame are numbered - first the strings of the current beam in slot order,
+ *   then, for beam slot j = 0, 1, .. in turn, the new strings p_j + c for the row's classes c in the order (logit descending, class
+ *   ascending) - and the smaller number ranks first.  Only the first min(W + 1, C - 1) non-blank classes of that order are
+ *   candidates; the others cannot reach the best W under this rule.  Nothing depends on timing: two calls give the same bits.
+ * Outputs: out (N, W, S) int64 padded with -1; out_lengths (N, W) int64; out_scores (N, W) f32 totals, best first; out_count (N)
+ *   int64 <= W.  Slots >= out_count: score -inf, length 0.  T = 0: one hypothesis, the empty string, score 0.
+ * Trace (always written; the lattice of the search): node_parent, node_label (N, S W + 1) int32 - node 0 is the empty prefix
+ *   (parent, label -1), node k > 0 spells node_parent[k]'s string + node_label[k], parents have smaller numbers, entries
+ *   [0, node_count[n]) are written; node_count (N) int32; beam_node (N, S, W) int32: the node in each rank slot after frame
+ *   t < T, -1 for an unused slot; beam_score (N, S, W, 2) f32: (pb, pnb) of that slot, (-inf, -inf) if unused.  Rows t >= T are
+ *   not written.
+ * Workspaces (caller-owned, contents unspecified before and after): row_lse 4 N S bytes; top_logp 4 N S K and top_class 4 N S K
+ *   bytes, K = min(W + 1, C - 1); hash 8 N H bytes, H = the smallest power of two >= 2 S W (cleared by the call itself).
+ * Supported: 2 <= C <= 8192, 1 <= S <= 512, 1 <= W <= 32 (PERO_E_UNSUPPORTED above), N S < 2^31.
+ *
+ * pero_edit_distance: dist[n] (int64) = the Levenshtein distance (insertion, deletion, substitution: 1 each) of a[n][0, a_len[n])
+ * and b[n][0, b_len[n]).  a (N, La), b (N, Lb) int64, padded (entries behind the lengths are never read; a null pointer is
+ * allowed for a zero-width matrix); a_len, b_len (N) int64, clamped to [0, La], [0, Lb].  totals (2 int64 on the device, may be
+ * null; ACCUMULATED, the caller zeroes them once): totals[0] += sum_n dist[n], totals[1] += sum_n b_len[n] (clamped), by integer
+ * atomics: exact in any order.  Integer arithmetic only.  Supported: La, Lb <= 512 (PERO_E_UNSUPPORTED above). */
+int pero_ctc_beam(const void* logits, const int64_t* input_lengths, int64_t* out, int64_t* out_lengths, float* out_scores,
+                  int64_t* out_count, int32_t* node_parent, int32_t* node_label, int32_t* node_count, int32_t* beam_node,
+                  float* beam_score, float* row_lse, float* top_logp, int32_t* top_class, uint64_t* hash, int64_t N, int64_t S, int64_t C,
+                  int64_t blank, int64_t W, int dtype, void* stream);
+int pero_edit_distance(const int64_t* a, const int64_t* a_len, const int64_t* b, const int64_t* b_len, int64_t* dist, int64_t* totals,
+                       int64_t N, int64_t La, int64_t Lb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

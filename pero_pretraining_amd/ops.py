@@ -906,3 +906,57 @@ def ctc_greedy(logits, input_lengths, blank=0):
     out_lengths = torch.empty(n, device=logits.device, dtype=torch.int64)
     call("pero_ctc_greedy", ptr(logits), ptr(input_lengths), ptr(out), ptr(out_lengths), n, S, C, blank, dt(logits), stream())
     return out, out_lengths
+
+
+def ctc_beam_workspace(S, C, beam_width):
+    """(K, H) of pero_ctc_beam's workspaces (include/pero_hip.h): K best classes per row, H hash slots per line."""
+    H = 1
+    while H < 2 * S * beam_width:
+        H *= 2
+    return min(beam_width + 1, C - 1), H
+
+
+def ctc_beam(logits, input_lengths, beam_width, blank=0, return_trace=False):
+    """CTC prefix beam search of (N*S, C) logits, all on the device: (labels (N, W, S) int64 padded with -1, lengths (N, W) int64,
+    scores (N, W) f32 best first, count (N) int64).  return_trace: also the dict of include/pero_hip.h's trace (node_parent, node_label,
+    node_count, beam_node, beam_score)."""
+    _req_cuda(logits, input_lengths)
+    n = input_lengths.numel()
+    rows, C = logits.shape
+    if not logits.is_contiguous() or n == 0 or rows % n or input_lengths.dtype != torch.int64 or not input_lengths.is_contiguous():
+        raise ValueError("ctc_beam: logits must be contiguous (N*S, C), input_lengths contiguous int64 (N)")
+    S, W, dev = rows // n, int(beam_width), logits.device
+    if W < 1 or C < 2:
+        raise ValueError("ctc_beam: beam_width >= 1 and C >= 2")
+    K, H = ctc_beam_workspace(S, C, W)
+    i32, i64, f32 = torch.int32, torch.int64, torch.float32
+    out = torch.empty((n, W, S), device=dev, dtype=i64)
+    out_lengths, out_scores = torch.empty((n, W), device=dev, dtype=i64), torch.empty((n, W), device=dev, dtype=f32)
+    out_count = torch.empty(n, device=dev, dtype=i64)
+    trace = {"node_parent": torch.empty((n, S * W + 1), device=dev, dtype=i32), "node_label": torch.empty((n, S * W + 1), device=dev, dtype=i32),
+             "node_count": torch.empty(n, device=dev, dtype=i32), "beam_node": torch.empty((n, S, W), device=dev, dtype=i32),
+             "beam_score": torch.empty((n, S, W, 2), device=dev, dtype=f32)}
+    row_lse = torch.empty(rows, device=dev, dtype=f32)
+    top_logp, top_class = torch.empty((rows, K), device=dev, dtype=f32), torch.empty((rows, K), device=dev, dtype=i32)
+    table = torch.empty((n, H), device=dev, dtype=i64)
+    call("pero_ctc_beam", ptr(logits), ptr(input_lengths), ptr(out), ptr(out_lengths), ptr(out_scores), ptr(out_count), ptr(trace["node_parent"]),
+         ptr(trace["node_label"]), ptr(trace["node_count"]), ptr(trace["beam_node"]), ptr(trace["beam_score"]), ptr(row_lse), ptr(top_logp),
+         ptr(top_class), ptr(table), n, S, C, blank, W, dt(logits), stream())
+    return (out, out_lengths, out_scores, out_count, trace) if return_trace else (out, out_lengths, out_scores, out_count)
+
+
+def edit_distance(a, a_len, b, b_len, totals=None):
+    """Levenshtein distance per pair of padded int64 label matrices a (N, La), b (N, Lb) with lengths (N), all on the device: dist (N) int64.
+    totals (2 int64 on the device): totals[0] += sum dist, totals[1] += sum b_len, exact (integer atomics)."""
+    _req_cuda(a, a_len, b, b_len, totals)
+    n = a_len.numel()
+    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != n or b.shape[0] != n or b_len.numel() != n or n == 0:
+        raise ValueError("edit_distance: a (N, La), b (N, Lb), a_len and b_len (N)")
+    for t in (a, a_len, b, b_len) + (() if totals is None else (totals,)):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise ValueError("edit_distance: labels, lengths and totals must be contiguous int64 device tensors")
+    if totals is not None and totals.numel() != 2:
+        raise ValueError("edit_distance: totals holds two int64")
+    dist = torch.empty(n, device=a.device, dtype=torch.int64)
+    call("pero_edit_distance", ptr(a), ptr(a_len), ptr(b), ptr(b_len), ptr(dist), ptr(totals), n, a.shape[1], b.shape[1], stream())
+    return dist

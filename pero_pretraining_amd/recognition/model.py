@@ -87,10 +87,12 @@ class TransformerRecognizer(torch.nn.Module):
             loss = self.loss(output, targets, input_lengths, target_lengths)
         return {"output": output, "loss": loss}
 
-    def decode(self, images, input_lengths=None, key_ranges=None):
-        """Greedy labels (N, S) int64 padded with -1 and their lengths (N), on the device."""
+    def decode(self, images, input_lengths=None, key_ranges=None, beam_width=None, nbest=1):
+        """Greedy labels (N, S) int64 padded with -1 and their lengths (N), on the device.  With beam_width: beam_decode's three results."""
         with torch.no_grad():
             output = self.encode(images, **ops.key_ranges_kw(self._ranges(input_lengths, key_ranges)))
+        if beam_width is not None:
+            return beam_decode(output, input_lengths, getattr(self.loss, "blank", 0), beam_width, nbest)
         return greedy_decode(output, input_lengths, getattr(self.loss, "blank", 0))
 
     def save(self, path):
@@ -108,7 +110,7 @@ class TransformerRecognizer(torch.nn.Module):
         self.backbone.load_state_dict({k[len("backbone."):]: v for k, v in sd.items() if k.startswith("backbone.")}, strict=True)
 
 
-def greedy_decode(output, input_lengths=None, blank=0):
+def _decoder_args(output, input_lengths):
     n, S, C = output.shape
     lg = output.detach().reshape(-1, C)
     if not lg.is_contiguous():
@@ -117,7 +119,23 @@ def greedy_decode(output, input_lengths=None, blank=0):
         il = torch.full((n,), S, dtype=torch.int64, device=lg.device)
     else:
         il = torch.as_tensor(input_lengths).to(device=lg.device, dtype=torch.int64).contiguous()
-    return ops.ctc_greedy(lg, il, blank)
+    return lg, il
+
+
+def greedy_decode(output, input_lengths=None, blank=0):
+    return ops.ctc_greedy(*_decoder_args(output, input_lengths), blank)
+
+
+def beam_decode(output, input_lengths=None, blank=0, beam_width=16, nbest=1):
+    """CTC prefix beam search of (N, S, C) logits on the device: the nbest <= beam_width best label strings of every line,
+    (labels (N, nbest, S) int64 padded with -1, lengths (N, nbest) int64, scores (N, nbest) f32 log-probabilities, best first); a line with
+    fewer hypotheses has length 0 and score -inf in the rest.  nbest = 1 drops the hypothesis axis: (N, S), (N), (N)."""
+    if not 1 <= nbest <= beam_width:
+        raise ValueError(f"beam_decode: nbest {nbest} outside [1, beam_width = {beam_width}]")
+    labels, lengths, scores, _ = ops.ctc_beam(*_decoder_args(output, input_lengths), beam_width, blank)
+    if nbest == 1:
+        return labels[:, 0], lengths[:, 0], scores[:, 0]
+    return labels[:, :nbest], lengths[:, :nbest], scores[:, :nbest]
 
 
 def init_model(device, backbone_definition, head_definition, path=None, pretrained_path=None, blank=0, reduction="mean", zero_infinity=False):
@@ -132,4 +150,4 @@ def init_model(device, backbone_definition, head_definition, path=None, pretrain
     return model
 
 
-__all__ = ["CTCLoss", "TransformerRecognizer", "LinearHead", "greedy_decode", "init_backbone", "init_head", "init_model"]
+__all__ = ["CTCLoss", "TransformerRecognizer", "LinearHead", "beam_decode", "greedy_decode", "init_backbone", "init_head", "init_model"]

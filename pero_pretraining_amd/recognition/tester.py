@@ -1,11 +1,11 @@
-"""Tester of a recogniser: average loss and character error rate.  The logits never leave the device: pero_ctc_greedy decodes
-there, and the decoded labels and their lengths (N * (S + 1) integers) are read back once per batch; the edit distances are
-computed on the host."""
+"""Tester of a recogniser: average loss and character error rate.  Nothing leaves the device inside the loop: pero_ctc_greedy
+(or, with beam_width, pero_ctc_beam) decodes there, pero_edit_distance compares the decoded labels with the targets there and adds
+into one pair of integer totals, which is read once behind the last batch."""
 import torch
 
+from .. import ops
 from ..precision import autocast
-from .batch_operator import host_targets
-from .model import greedy_decode
+from .model import beam_decode, greedy_decode
 
 
 def levenshtein(a, b):
@@ -21,16 +21,17 @@ def levenshtein(a, b):
 
 
 class Tester:
-    def __init__(self, batch_operator, model, dataloader, max_lines=None, bfloat16=False):
+    def __init__(self, batch_operator, model, dataloader, max_lines=None, bfloat16=False, beam_width=None):
         self.batch_operator = batch_operator
         self.model = model
         self.dataloader = dataloader
         self.max_lines = max_lines
         self.bfloat16 = bfloat16
+        self.beam_width = beam_width   # None: greedy decoding
 
     def test(self):
         """{'loss': mean of the batch losses, 'cer': sum of edit distances / sum of target lengths}."""
-        total_loss, num_lines, num_batches, distance, characters = 0, 0, 0, 0, 0
+        total_loss, num_lines, num_batches, totals = 0, 0, 0, None
         self.model.eval()
         with torch.no_grad():
             for batch in self.dataloader:
@@ -38,14 +39,18 @@ class Tester:
                 with autocast(self.bfloat16):
                     result = self.model(images, targets, target_lengths, input_lengths)
                 total_loss = total_loss + result["loss"]
-                labels, lengths = greedy_decode(result["output"], input_lengths, getattr(self.model.loss, "blank", 0))
-                decoded = torch.cat((lengths[:, None], labels), dim=1).cpu().tolist()   # the batch's one device -> host transfer
-                for line, truth in zip(decoded, host_targets(batch)):
-                    distance += levenshtein(line[1:1 + line[0]], truth)
-                    characters += len(truth)
+                blank = getattr(self.model.loss, "blank", 0)
+                if self.beam_width is None:
+                    labels, lengths = greedy_decode(result["output"], input_lengths, blank)
+                else:
+                    labels, lengths, _ = beam_decode(result["output"], input_lengths, blank, self.beam_width)
+                if totals is None:
+                    totals = torch.zeros(2, dtype=torch.int64, device=labels.device)   # sum of distances, sum of target lengths
+                ops.edit_distance(labels.contiguous(), lengths.contiguous(), targets.contiguous(), target_lengths.contiguous(), totals)
                 num_lines += self.batch_operator.batch_size(batch)
                 num_batches += 1
                 if self.max_lines is not None and num_lines > self.max_lines:
                     break
         self.model.train()
+        distance, characters = totals.tolist()   # the run's one read of the counts
         return {"loss": float(total_loss) / num_batches, "cer": distance / max(characters, 1)}
