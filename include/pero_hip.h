@@ -555,6 +555,40 @@ int pero_ctc_beam(const void* logits, const int64_t* input_lengths, int64_t* out
 int pero_edit_distance(const int64_t* a, const int64_t* a_len, const int64_t* b, const int64_t* b_len, int64_t* dist, int64_t* totals,
                        int64_t N, int64_t La, int64_t Lb, void* stream);
 
+/* ---- CTC forced alignment (where each character of a known string sits, and how sure the model is of it; csrc/ctc_align.hip,
+ * DESIGN.md "CTC forced alignment") ---------------------------------------------------------------------------------------
+ * pero_ctc_align: the best state path (Viterbi) of every line's label string.  logits, targets, input_lengths, target_lengths,
+ * blank, dtype, the clamp of the lengths, the extended states l' and the treatment of labels outside [0, C) or equal to blank: as
+ * for pero_ctc_fwd.  x_t(c) = the logit converted to f32.  The best path does not depend on a frame's log-sum-exp, so the recursion
+ * runs on RAW logits and holds f32 additions and comparisons only:
+ *   v_0(s) = x_0(l'_s) for s < 2, -inf else;
+ *   v_t(s) = x_t(l'_s) + max(v_{t-1}(s), v_{t-1}(s-1), [l'_s != l'_{s-2}] v_{t-1}(s-2))          one f32 addition per state and frame;
+ *   back_t(s) in {0, 1, 2}: the step of the winning predecessor; equal values -> the SMALLEST step; all -inf -> 0;
+ *   end state: L'-1 if v_{T-1}(L'-1) >= v_{T-1}(L'-2), else L'-2 (L = 0: state 0); the path follows back_t from there to frame 0;
+ *   the line is feasible iff that v is finite.  T = 0: feasible iff L = 0, path_logit = score = 0.
+ *   Tie rule in words: among the paths with the best f32 value, the one whose state sequence is lexicographically LARGEST when read
+ *   from the last frame back to the first (it advances as early as it can).  The library is built without fused multiply-adds, so
+ *   a float32 restatement of these formulas gives the same bits for every input.
+ * Outputs (caller-owned, every entry written):
+ *   states (N, S) int32: the extended-state index at frame t < T; -1 for t >= T and for every frame of an infeasible line.
+ *   spans (N, Lmax, 2) int32: [first frame, last frame + 1) of label k's state 2 k + 1 (a feasible line gives every label at least
+ *     one frame); -1 for k >= L and for infeasible lines.
+ *   path_logit (N) f32: v_{T-1}(end) = the path's logits added in frame order; -inf for an infeasible line.
+ *   score (N) f32: the path's log-probability, path_logit - sum_{t < T} lse_t, with lse_t = max + log sum_c exp(x_t(c) - max) (the
+ *     arithmetic of pero_ctc_fwd's row_lse, recomputed here for the rows t < T) added in frame order; -inf for an infeasible line.
+ *   label_logp (N, Lmax) f32: sum_{t in span k} (x_t(l_k) - lse_t), added in frame order; 0 for k >= L and for infeasible lines.
+ * No float atomics, nothing depends on timing: two calls give the same bits.  Rows t >= T and targets behind L are never read.
+ * Workspaces (caller-owned, contents unspecified before and after): row_lse 4 N S bytes; back N S (2 Lmax + 1) bytes, one
+ *   backpointer byte per (t, s).  When S (2 Lmax + 1) <= PERO_CTC_ALIGN_LDS_BACK_BYTES (host-known sizes only) the backpointers stay
+ *   in LDS and `back` is not touched; flags = PERO_CTC_ALIGN_GLOBAL_BACK forces the workspace (for measurements; the results are the
+ *   same bits).  `back` is required either way.
+ * Supported: 2 <= C <= 8192, 1 <= S <= 512, 0 <= Lmax <= 512, N S < 2^31 (PERO_E_UNSUPPORTED above; Lmax may exceed S). */
+#define PERO_CTC_ALIGN_LDS_BACK_BYTES (96 * 1024)
+#define PERO_CTC_ALIGN_GLOBAL_BACK 1
+int pero_ctc_align(const void* logits, const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths,
+                   int32_t* states, int32_t* spans, float* path_logit, float* score, float* label_logp, float* row_lse, void* back,
+                   int64_t N, int64_t S, int64_t C, int64_t Lmax, int64_t blank, int flags, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,7 @@ SIGNATURES = {
     "pero_ctc_greedy": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
     "pero_ctc_beam": [_vp] * 15 + [_i64, _i64, _i64, _i64, _i64, _i32, _vp],
     "pero_edit_distance": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp],
+    "pero_ctc_align": [_vp] * 11 + [_i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp],
 }
 # pero_gemm's arguments + int* k_split, int* extra_pass (each may be null); returns the kernel family (> 0: a key of GEMM_KERNELS), so not for call()
 SIGNATURES["pero_gemm_plan"] = SIGNATURES["pero_gemm"] + [_vp, _vp]

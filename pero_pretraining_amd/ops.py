@@ -945,6 +945,31 @@ def ctc_beam(logits, input_lengths, beam_width, blank=0, return_trace=False):
     return (out, out_lengths, out_scores, out_count, trace) if return_trace else (out, out_lengths, out_scores, out_count)
 
 
+CTC_ALIGN_LDS_BACK_BYTES = 96 * 1024   # PERO_CTC_ALIGN_LDS_BACK_BYTES of include/pero_hip.h
+
+
+def ctc_align(logits, targets, input_lengths, target_lengths, blank=0, global_back=False):
+    """CTC forced alignment (pero_ctc_align) of (N*S, C) f32 / bf16 logits to targets (N, Lmax), all on the device.  Returns
+    (states (N, S) int32, spans (N, Lmax, 2) int32, path_logit (N) f32, score (N) f32, label_logp (N, Lmax) f32) as include/pero_hip.h
+    defines them.  global_back: keep the backpointers in the global workspace even where they fit LDS (the same bits; for measurements)."""
+    n, S, C, Lmax = _ctc_args(logits, targets, input_lengths, target_lengths)
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("ctc_align: logits must be f32 or bf16")
+    if not 0 <= blank < C:
+        raise ValueError(f"ctc_align: blank {blank} outside [0, {C})")
+    dev, i32, f32 = logits.device, torch.int32, torch.float32
+    states = torch.empty((n, S), device=dev, dtype=i32)
+    spans = torch.empty((n, Lmax, 2), device=dev, dtype=i32)
+    path_logit, score = torch.empty(n, device=dev, dtype=f32), torch.empty(n, device=dev, dtype=f32)
+    label_logp = torch.empty((n, Lmax), device=dev, dtype=f32)
+    row_lse = torch.empty(n * S, device=dev, dtype=f32)
+    in_lds = S * (2 * Lmax + 1) <= CTC_ALIGN_LDS_BACK_BYTES and not global_back
+    back = torch.empty(1 if in_lds else n * S * (2 * Lmax + 1), device=dev, dtype=torch.uint8)   # untouched when the backpointers fit LDS
+    call("pero_ctc_align", ptr(logits), ptr(targets), ptr(input_lengths), ptr(target_lengths), ptr(states), ptr(spans), ptr(path_logit),
+         ptr(score), ptr(label_logp), ptr(row_lse), ptr(back), n, S, C, Lmax, blank, int(bool(global_back)), dt(logits), stream())
+    return states, spans, path_logit, score, label_logp
+
+
 def edit_distance(a, a_len, b, b_len, totals=None):
     """Levenshtein distance per pair of padded int64 label matrices a (N, La), b (N, Lb) with lengths (N), all on the device: dist (N) int64.
     totals (2 int64 on the device): totals[0] += sum dist, totals[1] += sum b_len, exact (integer atomics)."""

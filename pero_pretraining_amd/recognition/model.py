@@ -1,5 +1,7 @@
 """CTC fine-tuning of a pre-trained backbone: CTCLoss over the HIP kernels of csrc/ctc.hip and TransformerRecognizer,
 the backbone + a character head.  (The reference has no recogniser: an extension, like FusedAdamW.)"""
+import collections
+
 import torch
 
 from .. import ops
@@ -95,6 +97,25 @@ class TransformerRecognizer(torch.nn.Module):
             return beam_decode(output, input_lengths, getattr(self.loss, "blank", 0), beam_width, nbest)
         return greedy_decode(output, input_lengths, getattr(self.loss, "blank", 0))
 
+    def align(self, images, targets, target_lengths, input_lengths=None, key_ranges=None):
+        """forced_align of the lines' own logits to the given strings: where every character sits and how sure the model is of it."""
+        with torch.no_grad():
+            output = self.encode(images, **ops.key_ranges_kw(self._ranges(input_lengths, key_ranges)))
+        return forced_align(output, targets, target_lengths, input_lengths, getattr(self.loss, "blank", 0))
+
+    def transcribe(self, images, input_lengths=None, key_ranges=None, beam_width=None):
+        """Decode (greedy, or with beam_width the best beam hypothesis) and align the decoded strings to the same logits, in one
+        encoder pass: (labels (N, S) int64 padded with -1, lengths (N), Alignment), all on the device."""
+        blank = getattr(self.loss, "blank", 0)
+        with torch.no_grad():
+            output = self.encode(images, **ops.key_ranges_kw(self._ranges(input_lengths, key_ranges)))
+            if beam_width is not None:
+                labels, lengths, _ = beam_decode(output, input_lengths, blank, beam_width)
+                labels, lengths = labels.contiguous(), lengths.contiguous()
+            else:
+                labels, lengths = greedy_decode(output, input_lengths, blank)
+            return labels, lengths, forced_align(output, labels, lengths, input_lengths, blank)
+
     def save(self, path):
         torch.save(self.state_dict(), path)
 
@@ -138,6 +159,35 @@ def beam_decode(output, input_lengths=None, blank=0, beam_width=16, nbest=1):
     return labels[:, :nbest], lengths[:, :nbest], scores[:, :nbest]
 
 
+Alignment = collections.namedtuple("Alignment", ["states", "spans", "label_logp", "score", "path_logit", "confidences", "nll", "path_share"])
+Alignment.__doc__ = """forced_align's results, on the device.  states (N, S) int32, spans (N, Lmax, 2) int32 [first frame, last frame + 1),
+label_logp (N, Lmax), score (N), path_logit (N): pero_ctc_align's outputs (include/pero_hip.h).  confidences (N, Lmax) f32: per label the
+geometric mean of its frames' probabilities, 0 where there is no label.  nll (N) and path_share (N) = exp(score + nll), the best path's share
+of the string's total probability (a line-level confidence): only with with_nll, else None."""
+
+
+def forced_align(output, targets, target_lengths, input_lengths=None, blank=0, with_nll=False):
+    """CTC forced alignment of (N, S, C) logits to targets (N, Lmax) (padding behind target_lengths is never read) on the device; nothing
+    is read back to the host.  An infeasible line (too few frames for its string) has states and spans -1, score -inf, confidences 0."""
+    if output.dim() != 3:
+        raise ValueError("forced_align: output must be (N, S, C)")
+    if not 0 <= blank < output.shape[-1]:
+        raise ValueError(f"forced_align: blank {blank} outside [0, {output.shape[-1]})")
+    lg, il = _decoder_args(output, input_lengths)
+    if lg.dtype not in (torch.float32, torch.bfloat16):
+        lg = lg.float()
+    tg, tl = (torch.as_tensor(t).to(device=lg.device, dtype=torch.int64).contiguous() for t in (targets, target_lengths))
+    states, spans, path_logit, score, label_logp = ops.ctc_align(lg, tg, il, tl, blank)
+    frames = spans[..., 1] - spans[..., 0]
+    confidences = torch.where(frames > 0, torch.exp(label_logp / frames.clamp_min(1)), torch.zeros_like(label_logp))
+    nll = path_share = None
+    if with_nll:
+        nll = ops.ctc_fwd(lg, tg, il, tl, blank)[0]
+        path_share = torch.exp(score + nll)   # an infeasible line: exp(-inf + inf) = NaN
+        path_share = torch.where(torch.isfinite(nll), path_share, torch.zeros_like(path_share))
+    return Alignment(states, spans, label_logp, score, path_logit, confidences, nll, path_share)
+
+
 def init_model(device, backbone_definition, head_definition, path=None, pretrained_path=None, blank=0, reduction="mean", zero_infinity=False):
     """The masked train.py helper for a recogniser.  path: a recogniser checkpoint; pretrained_path: a pre-training checkpoint whose backbone is taken."""
     model = TransformerRecognizer(init_backbone(backbone_definition), init_head(head_definition),
@@ -150,4 +200,5 @@ def init_model(device, backbone_definition, head_definition, path=None, pretrain
     return model
 
 
-__all__ = ["CTCLoss", "TransformerRecognizer", "LinearHead", "beam_decode", "greedy_decode", "init_backbone", "init_head", "init_model"]
+__all__ = ["Alignment", "CTCLoss", "TransformerRecognizer", "LinearHead", "beam_decode", "forced_align", "greedy_decode", "init_backbone", "init_head",
+           "init_model"]
