@@ -482,6 +482,39 @@ int pero_line_masks(const int32_t* widths1, const int32_t* widths2, const int32_
                     const int32_t* crop_shifts, uint8_t* image_masks1, uint8_t* image_masks2, uint8_t* shift_masks1,
                     uint8_t* shift_masks2, int32_t* shifts, int64_t B, int64_t S, int64_t subsampling, void* stream);
 
+/* ---- line augmentation fused into collation (csrc/augment.hip) ---------------------------------
+ * pero_stack_lines with a per-line warp, tone curve and noise on the way: the same packed / offsets / widths / left_px (packed
+ * readable 8 bytes past its end) and the same out (B, H, Wt, C) u8, every byte written exactly once.  The transform keeps the
+ * width: line b occupies columns [left_px[b], left_px[b] + w), w = widths[b], and every byte outside is zero.  C <= 4: the two
+ * horizontal taps of a source row are fetched as one 8-byte read, which may run into the 8 bytes behind the buffer.
+ *   params (B, P) i32, P = PERO_AUGMENT_PARAMS, columns: sy (vertical scale, 8.8 fixed point: 256 = 1), ty (vertical translation,
+ *     1/256 px), slope (vertical shift per pixel of x, 1/256 px), slant (horizontal shift per pixel of y, 1/256 px), noise_amp,
+ *     seed_lo, seed_hi (the last two as 32 raw bits).
+ *   knots (B, 2, NK) i32, NK = (Wt >> knot_shift) + 2: vertical ([b][0]) and horizontal ([b][1]) displacement in 1/256 px at the
+ *     line's own columns 0, K, 2 K, ..., K = 1 << knot_shift, knot_shift in [3, 8].
+ *   lut (B, C, 256) u8, a tone curve per line and channel; null = identity.
+ * All arithmetic is integer, in 64 bits (every product is i32 x i32; B, H < 65536, C <= 4, Wt < 2^24 keep every sum below 2^58),
+ * >> is the arithmetic shift (floor), clamp(v, a, b) = min(max(v, a), b).  No value of params or knots reads out of bounds.
+ * Output byte (b, y, x_out, c) with x = x_out - left_px[b] in [0, w), cy = (H - 1) * 128, xc = w / 2, yr = (y << 8) - cy:
+ *   j = clamp(x >> knot_shift, 0, NK - 2), t = x & (K - 1)
+ *   dy = (knots[b][0][j] * (K - t) + knots[b][0][j + 1] * t) >> knot_shift;   dx likewise from knots[b][1]
+ *   ys = cy + ((yr * sy) >> 8) + ty + slope * (x - xc) + dy
+ *   xs = (x << 8) + ((yr * slant) >> 8) + dx
+ *   y0 = clamp(ys >> 8, 0, H - 1), y1 = clamp((ys >> 8) + 1, 0, H - 1), x0 = clamp(xs >> 8, 0, w - 1), x1 = clamp((xs >> 8) + 1, 0, w - 1)
+ *     (edge replication: no tap leaves the line's own pixels);  fx = xs & 255, fy = ys & 255;  pYX = line b's byte (yY, xX, c)
+ *   v = ((p00 * (256 - fx) + p01 * fx) * (256 - fy) + (p10 * (256 - fx) + p11 * fx) * fy + 32768) >> 16
+ *   v = lut[b][c][v]
+ *   if noise_amp != 0:  i = ((b * H + y) * Wt + x_out) * C + c  (u64: the byte's index in out);
+ *     h = fmix32(fmix32((i & 0xffffffff) ^ seed_lo) ^ (i >> 32) ^ seed_hi), where fmix32 is murmur3's 32-bit finaliser on u32:
+ *       h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16;
+ *     s = (h & 255) + ((h >> 8) & 255) + ((h >> 16) & 255) + (h >> 24) - 510   (Irwin-Hall: mean 0, standard deviation 147.8);
+ *     v = clamp(v + ((s * noise_amp + 32768) >> 16), 0, 255)   (noise_amp = 65536 sigma / 147.8 for a standard deviation of sigma)
+ * Neutral values - sy = 256, every other column 0, zero knots, identity or null lut - give pero_stack_lines' bytes. */
+#define PERO_AUGMENT_PARAMS 7
+int pero_augment_stack_lines(const void* packed, const int64_t* offsets, const int32_t* widths, const int32_t* left_px,
+                             const int32_t* params, const int32_t* knots, const uint8_t* lut, void* out, int64_t B, int64_t H,
+                             int64_t Wt, int64_t C, int64_t P, int64_t knot_shift, void* stream);
+
 /* ---- CTC (fine-tuning a recogniser on a pre-trained backbone; csrc/ctc.hip, DESIGN.md "CTC") -------------------------
  * logits (N*S, C) row-major in `dtype` - the head's own output rows, line n at rows [n S, (n + 1) S); all arithmetic f32.
  * The log-softmax is fused: logp_t(c) = x[n][t][c] - row_lse[n S + t], row_lse = log sum_c exp(x) per row; no (N*S, C) f32

@@ -92,6 +92,7 @@ SIGNATURES = {
     "pero_label_rank": [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _vp],
     "pero_stack_lines": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
     "pero_line_masks": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp],
+    "pero_augment_stack_lines": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp],
     "pero_kmeans_update": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp],
     "pero_kmeans_sqnorm": [_vp, _vp, _i64, _i64, _vp],
     "pero_kmeans_pp_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp],

@@ -34,13 +34,20 @@ def create_dataloader(dataset, batch_creator=None, batch_size=16, shuffle=False,
 
 class BatchCreator:
     def __init__(self, subsampling_factor=8, padding_coefficient=32, crop_width=None, crop_step=1, same_left_paddings=False,
-                 device=None):
+                 device=None, augmenter=None, augment_views=(True, True)):
         self.subsampling_factor = subsampling_factor
         self.padding_coefficient = padding_coefficient
         self.crop_width = crop_width
         self.crop_step = crop_step
         self.same_left_paddings = same_left_paddings
         self.device = torch.device("cuda") if device is None else torch.device(device)
+        # a common.augment.LineAugmenter: the selected views are warped, recoloured and given noise by the kernel that pads them
+        # (pero_augment_stack_lines); widths, paddings, masks, labels and shifts are those of the plain batch.  None: nothing changes
+        if augmenter is not None and augmenter.warp_amplitude_x >= subsampling_factor:
+            raise ValueError("BatchCreator: the augmenter's warp_amplitude_x must stay below one patch width (subsampling_factor), "
+                             "or pixels leave their labels")
+        self.augmenter = augmenter
+        self.augment_views = tuple(bool(v) for v in augment_views)
 
     # ---- reference surface -------------------------------------------------------------------------------------
     def create_batch(self, data: List[Dict]) -> Dict:
@@ -85,11 +92,11 @@ class BatchCreator:
             lines2 = [d["image2"] for d in data]
             left2 = list(left1) if self.same_left_paddings else [self._draw_left_padding(l, target_width) for l in lines2]  # ... then view 2
 
-        images1, w1, l1 = self._stack(lines1, left1, H, target_width, C)
+        images1, w1, l1 = self._stack(lines1, left1, H, target_width, C, self.augment_views[0])
         images2 = None
         w2 = l2 = cs = None
         if paired:
-            images2, w2, l2 = self._stack(lines2, left2, H, target_width, C)
+            images2, w2, l2 = self._stack(lines2, left2, H, target_width, C, self.augment_views[1])
             cs = torch.tensor(crop_shifts, dtype=torch.int32).to(self.device, non_blocking=True)
         im1, im2, sm1, sm2, shifts_t = ops.line_masks(w1, l1, target_width // sub, sub, w2, l2, cs)
         shifts = [c + (a - b) for c, a, b in zip(crop_shifts, left1, left2)] if paired else None   # dataloader.py:126
@@ -164,8 +171,9 @@ class BatchCreator:
             return 0
         return np.random.randint(0, target_width - line_image.shape[1]) // self.subsampling_factor
 
-    def _stack(self, lines, left, H, target_width, C):
-        """Upload the ragged lines once (pinned staging buffer) and pad them on the device."""
+    def _stack(self, lines, left, H, target_width, C, augment=False):
+        """Upload the ragged lines once (pinned staging buffer) and pad them on the device; with an augmenter and `augment`, one
+        draw of its numbers travels beside `meta` and the augmenting form of the kernel pads."""
         sizes = [int(l.shape[0]) * int(l.shape[1]) * int(l.shape[2]) for l in lines]
         total = int(sum(sizes))
         staging = torch.empty(total + 8, dtype=torch.uint8, pin_memory=True)
@@ -185,7 +193,13 @@ class BatchCreator:
         meta = torch.tensor([offsets, [l.shape[1] for l in lines], [lp * self.subsampling_factor for lp in left], left],
                             dtype=torch.int64).to(dev, non_blocking=True)
         widths, left_px, left_pos = (meta[i].to(torch.int32) for i in (1, 2, 3))
-        images = ops.stack_lines(packed, meta[0].contiguous(), widths, left_px, len(lines), H, target_width, C)
+        if self.augmenter is not None and augment:
+            params, knots, lut = (t.to(dev, non_blocking=True)
+                                  for t in self.augmenter.draw([l.shape[1] for l in lines], H, target_width, C))
+            images = ops.augment_stack_lines(packed, meta[0].contiguous(), widths, left_px, params, knots, lut, len(lines), H,
+                                             target_width, C, self.augmenter.knot_shift)
+        else:
+            images = ops.stack_lines(packed, meta[0].contiguous(), widths, left_px, len(lines), H, target_width, C)
         return images, widths, left_pos
 
     @staticmethod

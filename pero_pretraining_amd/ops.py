@@ -843,6 +843,35 @@ def stack_lines(packed, offsets, widths, left_px, B, H, Wt, C):
     return out
 
 
+AUGMENT_PARAMS = 7   # PERO_AUGMENT_PARAMS: sy, ty, slope, slant, noise_amp, seed_lo, seed_hi
+
+
+def augment_stack_lines(packed, offsets, widths, left_px, params, knots, lut, B, H, Wt, C, knot_shift=5):
+    """stack_lines with a per-line warp, tone curve and noise on the way (include/pero_hip.h "line augmentation"): the same ragged
+    upload in, the same zero-padded (B, H, Wt, C) uint8 batch out, line b still at columns [left_px[b], left_px[b] + widths[b]).
+    params (B, AUGMENT_PARAMS) int32, knots (B, 2, (Wt >> knot_shift) + 2) int32, lut (B, C, 256) uint8 or None (identity): device
+    tensors (common/augment.py LineAugmenter.draw makes them on the host).  C is at most 4."""
+    NK = (Wt >> knot_shift) + 2
+    want = [("packed", packed, torch.uint8, None), ("offsets", offsets, torch.int64, (B,)), ("widths", widths, torch.int32, (B,)),
+            ("left_px", left_px, torch.int32, (B,)), ("params", params, torch.int32, (B, AUGMENT_PARAMS)),
+            ("knots", knots, torch.int32, (B, 2, NK))]
+    if lut is not None:
+        want.append(("lut", lut, torch.uint8, (B, C, 256)))
+    for name, t, dtype, shape in want:
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != packed.device \
+                or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"augment_stack_lines: {name} must be a contiguous {dtype} tensor"
+                             + (f" of shape {shape}" if shape is not None else "") + " on the device of packed")
+    if not packed.is_cuda:
+        raise ValueError("augment_stack_lines: the tensors must live on the GPU")
+    if not 3 <= knot_shift <= 8 or (Wt * C) % 16 or not 1 <= C <= 4:
+        raise ValueError("augment_stack_lines: knot_shift must be in [3, 8], Wt * C a multiple of 16 and C at most 4")
+    out = torch.empty((B, H, Wt, C), device=packed.device, dtype=torch.uint8)
+    call("pero_augment_stack_lines", ptr(packed), ptr(offsets), ptr(widths), ptr(left_px), ptr(params), ptr(knots), ptr(lut), ptr(out),
+         B, H, Wt, C, AUGMENT_PARAMS, knot_shift, stream())
+    return out
+
+
 def line_masks(widths1, left1, S, subsampling, widths2=None, left2=None, crop_shifts=None):
     """Image masks, shifts and three-valued shift masks (common/dataloader.py:92-96, 124-138) from the per-line widths (px)
     and left paddings (label positions): int32 device tensors.  Returns (im1, im2, sm1, sm2, shifts); the last four are
