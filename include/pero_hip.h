@@ -608,14 +608,14 @@ int pero_edit_distance(const int64_t* a, const int64_t* a_len, const int64_t* b,
  *     one frame); -1 for k >= L and for infeasible lines.
  *   path_logit (N) f32: v_{T-1}(end) = the path's logits added in frame order; -inf for an infeasible line.
  *   score (N) f32: the path's log-probability, path_logit - sum_{t < T} lse_t, with lse_t = max + log sum_c exp(x_t(c) - max) (the
- *     arithmetic of pero_ctc_fwd's row_lse, recomputed here for the rows t < T) added in frame order; -inf for an infeasible line.
+ *     kernel of pero_ctc_fwd's row_lse, run here for the rows t < T: the same bits) added in frame order; -inf for an infeasible line.
  *   label_logp (N, Lmax) f32: sum_{t in span k} (x_t(l_k) - lse_t), added in frame order; 0 for k >= L and for infeasible lines.
  * No float atomics, nothing depends on timing: two calls give the same bits.  Rows t >= T and targets behind L are never read.
  * Workspaces (caller-owned, contents unspecified before and after): row_lse 4 N S bytes; back N S (2 Lmax + 1) bytes, one
  *   backpointer byte per (t, s).  When S (2 Lmax + 1) <= PERO_CTC_ALIGN_LDS_BACK_BYTES (host-known sizes only) the backpointers stay
  *   in LDS and `back` is not touched; flags = PERO_CTC_ALIGN_GLOBAL_BACK forces the workspace (for measurements; the results are the
  *   same bits).  `back` is required either way.
- * Supported: 2 <= C <= 8192, 1 <= S <= 512, 0 <= Lmax <= 512, N S < 2^31 (PERO_E_UNSUPPORTED above; Lmax may exceed S). */
+ * Supported: 2 <= C <= 8192, 1 <= S <= 512, 0 <= Lmax <= 512 (PERO_E_UNSUPPORTED above; Lmax may exceed S), N S < 2^31. */
 #define PERO_CTC_ALIGN_LDS_BACK_BYTES (96 * 1024)
 #define PERO_CTC_ALIGN_GLOBAL_BACK 1
 int pero_ctc_align(const void* logits, const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths,

@@ -1,8 +1,9 @@
 // Evaluation of a recogniser on the device: CTC prefix beam search and batched edit distance.  Contract: include/pero_hip.h; derivation,
 // trie and tie rule: DESIGN.md "CTC decoding".
 //
-//   pero_ctc_beam      ctc_beam_top_k  one wave per logit row t < T: row_lse (the arithmetic of ctc_row_lse_k) and the K = min(W + 1, C - 1)
-//                                      best non-blank classes of the row with their log-probabilities (all rows in parallel)
+//   pero_ctc_beam      ctc_beam_top_k  one wave per logit row t < T: row_lse (ctc_wave_row_lse, the function of ctc_row_lse_k) and the
+//                                      K = min(W + 1, C - 1) best non-blank classes of the row with their log-probabilities (all rows in
+//                                      parallel)
 //                      ctc_beam_k      one workgroup per line, frame by frame: the <= W (K + 1) candidates of the frame are scored by the
 //                                      threads, ranked by counting, the kept ones find or create their prefix node; five barriers per frame
 //   pero_edit_distance edit_distance_k one workgroup per pair: the anti-diagonals of the unit-cost table out of LDS, one barrier each
@@ -10,37 +11,23 @@
 // Why K = W + 1 classes are enough: the extensions of one beam entry j score logp(c) + tot_j, except c = last_j, which scores logp(c) + pb_j
 // <= logp(c) + tot_j.  A class outside the row's best W + 1 is beaten, for the same j, by at least W extensions (or by the stay candidates
 // they merged into, whose totals are no smaller), so it is never among the frame's best W.
-#include "losses_common.hpp"
+#include "ctc_common.hpp"
 
-#define BEAM_THREADS 256
-#define BEAM_MAX_S 512
-#define BEAM_MAX_C 8192
 #define BEAM_MAX_W 32
 #define BEAM_MAX_K (BEAM_MAX_W + 1)
 #define BEAM_MAX_Q (BEAM_MAX_W * (BEAM_MAX_K + 1))                      // stay + extension candidates of one frame
-#define BEAM_QPT ((BEAM_MAX_Q + BEAM_THREADS - 1) / BEAM_THREADS)       // candidates of one thread
-#define BEAM_NEG_INF (-__builtin_huge_valf())
+#define BEAM_QPT ((BEAM_MAX_Q + CTC_THREADS - 1) / CTC_THREADS)         // candidates of one thread
 #define EDIT_THREADS 256
 #define EDIT_MAX_L 512
 
-static __device__ __forceinline__ int beam_clamp_len(int64_t v, int hi) { return v < 0 ? 0 : (v > hi ? hi : (int)v); }
-
-// log(exp(a) + exp(b) + exp(c)); an all -inf triple stays -inf (no inf - inf)
-static __device__ __forceinline__ float beam_lse3(float a, float b, float c) {
-  const float m = fmaxf(a, fmaxf(b, c));
-  if (m == BEAM_NEG_INF) return BEAM_NEG_INF;
-  return m + logf(expf(a - m) + expf(b - m) + expf(c - m));
-}
 // A candidate's sort key: the larger key ranks first.  High word: the total's bits made monotone (a float order is an unsigned order after
 // flipping the sign bit of a non-negative value and every bit of a negative one; -0 counts as +0); low word: ~q, so that equal totals rank by
 // candidate index and no two keys are equal.  0 = no candidate (a total of -inf, or a string merged into another candidate).
 static __device__ __forceinline__ unsigned long long beam_key(float total, int q) {
-  if (total == BEAM_NEG_INF) return 0;
+  if (total == CTC_NEG_INF) return 0;
   const unsigned u = __float_as_uint(total + 0.f);
   return ((unsigned long long)(u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u)) << 32) | (unsigned)~q;
 }
-// x - lse; a -inf logit has log-probability -inf whatever the row's lse is
-static __device__ __forceinline__ float beam_logp(float x, float lse) { return x == BEAM_NEG_INF ? BEAM_NEG_INF : x - lse; }
 
 // Number of hash slots of a line: the smallest power of two >= 2 S W, so that the S W nodes a line can create fill at most half of it.
 static inline int64_t beam_hash_slots(int64_t S, int64_t W) {
@@ -50,28 +37,21 @@ static inline int64_t beam_hash_slots(int64_t S, int64_t W) {
 }
 
 template <typename T>
-__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_top_k(const T* __restrict__ logits, const int64_t* __restrict__ input_lengths,
+__global__ __launch_bounds__(CTC_THREADS) void ctc_beam_top_k(const T* __restrict__ logits, const int64_t* __restrict__ input_lengths,
                                                                float* __restrict__ row_lse, float* __restrict__ top_logp,
                                                                int32_t* __restrict__ top_class, long long rows, int S, int C, int blank, int K) {
-  const long long row = (long long)blockIdx.x * (BEAM_THREADS / 64) + (threadIdx.x >> 6);
+  const long long row = (long long)blockIdx.x * (CTC_THREADS / 64) + (threadIdx.x >> 6);
   if (row >= rows) return;
-  if ((int)(row % S) >= beam_clamp_len(input_lengths[row / S], S)) return;   // a row behind the line's frames is never read
+  if ((int)(row % S) >= ctc_clamp_len(input_lengths[row / S], S)) return;   // a row behind the line's frames is never read
   const int lane = threadIdx.x & 63;
   const T* x = logits + row * C;
-  float mx = BEAM_NEG_INF;
-  for (int c = lane; c < C; c += 64) mx = fmaxf(mx, Elem<T>::ld(x + c));
-  mx = wave_max(mx);
-  float sum = 0.f;
-  if (mx != BEAM_NEG_INF)
-    for (int c = lane; c < C; c += 64) sum += expf(Elem<T>::ld(x + c) - mx);
-  sum = wave_sum(sum);
-  const float lse = mx == BEAM_NEG_INF ? BEAM_NEG_INF : mx + logf(sum);
+  const float lse = ctc_wave_row_lse(x, C, lane);
   if (lane == 0) row_lse[row] = lse;
-  // K rounds of "the best class behind the previous winner" in the order (logit descending, class ascending)
+  // K rounds of "the best non-blank class behind the previous winner" in the order (logit descending, class ascending)
   float px = __builtin_huge_valf();
   int pc = -1;
   for (int r = 0; r < K; r++) {
-    float best = BEAM_NEG_INF;
+    float best = CTC_NEG_INF;
     int at = C;   // no candidate yet
     for (int c = lane; c < C; c += 64) {
       if (c == blank) continue;
@@ -87,14 +67,14 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_top_k(const T* __restri
     }
     if (lane == 0) {   // at == C only for a row with NaNs: a valid class with probability 0, so that nothing downstream indexes out of range
       top_class[row * K + r] = at < C ? at : (blank == 0 ? 1 : 0);
-      top_logp[row * K + r] = at < C ? beam_logp(best, lse) : BEAM_NEG_INF;
+      top_logp[row * K + r] = at < C ? ctc_logp(best, lse) : CTC_NEG_INF;
     }
     px = best;
     pc = at;
   }
 }
 
-// The line's hash of prefix nodes, open addressing with linear probing: a slot is 0 (free) or ((parent * BEAM_MAX_C + label + 1) << 32) | node.
+// The line's hash of prefix nodes, open addressing with linear probing: a slot is 0 (free) or ((parent * CTC_MAX_C + label + 1) << 32) | node.
 // Every access is an atomic at device scope, so no read is served from a stale line of the CU's vector cache.
 static __device__ __forceinline__ unsigned beam_hash_of(unsigned key) {
   unsigned h = key * 2654435761u;
@@ -128,7 +108,7 @@ struct BeamLds {
 };
 
 template <typename T>
-__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_k(const T* __restrict__ logits, const int64_t* __restrict__ input_lengths,
+__global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ logits, const int64_t* __restrict__ input_lengths,
                                                            const float* __restrict__ row_lse, const float* __restrict__ top_logp,
                                                            const int32_t* __restrict__ top_class, unsigned long long* __restrict__ hash,
                                                            int64_t* __restrict__ out, int64_t* __restrict__ out_lengths, float* __restrict__ out_scores,
@@ -138,7 +118,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_k(const T* __restrict__
                                                            int W, int K, int H) {
   __shared__ BeamLds b;
   const int n = blockIdx.x, tid = threadIdx.x;
-  const int Tn = beam_clamp_len(input_lengths[n], S);
+  const int Tn = ctc_clamp_len(input_lengths[n], S);
   const T* x = logits + (long long)n * S * C;
   const float* lse = row_lse + (long long)n * S;
   const float* tv = top_logp + (long long)n * S * K;
@@ -149,10 +129,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_k(const T* __restrict__
   int32_t* bn = beam_node + (long long)n * S * W;
   float* bs = beam_score + (long long)n * S * W * 2;
 
-  for (int i = tid; i < H; i += BEAM_THREADS) hs[i] = 0;
+  for (int i = tid; i < H; i += CTC_THREADS) hs[i] = 0;
   if (tid == 0) {   // before frame 0: the empty prefix, pb = 0, pnb = -inf
     b.node[0][0] = 0; b.parent[0][0] = -1; b.last[0][0] = -1; b.len[0][0] = 0;
-    b.pb[0][0] = 0.f; b.pnb[0][0] = BEAM_NEG_INF;
+    b.pb[0][0] = 0.f; b.pnb[0][0] = CTC_NEG_INF;
     b.count[0] = 1;
     b.nodes = 1;
     np[0] = -1;
@@ -166,11 +146,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_k(const T* __restrict__
     const int nxt = cur ^ 1;
     const int B = b.count[cur];
     const float le = lse[t];
-    const float lpb = beam_logp(Elem<T>::ld(x + (long long)t * C + blank), le);
+    const float lpb = ctc_logp(Elem<T>::ld(x + (long long)t * C + blank), le);
     if (tid < B) {
       const int last = b.last[cur][tid], pn = b.parent[cur][tid];
-      b.tot[tid] = beam_lse3(b.pb[cur][tid], b.pnb[cur][tid], BEAM_NEG_INF);
-      b.lpe[tid] = last >= 0 ? beam_logp(Elem<T>::ld(x + (long long)t * C + last), le) : BEAM_NEG_INF;
+      b.tot[tid] = ctc_lse3(b.pb[cur][tid], b.pnb[cur][tid], CTC_NEG_INF);
+      b.lpe[tid] = last >= 0 ? ctc_logp(Elem<T>::ld(x + (long long)t * C + last), le) : CTC_NEG_INF;
       int ps = -1;
       if (pn >= 0)
         for (int j = 0; j < B; j++)
@@ -190,21 +170,21 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_k(const T* __restrict__
     float sc[BEAM_QPT];
 #pragma unroll
     for (int k = 0; k < BEAM_QPT; k++) {
-      const int q = tid + k * BEAM_THREADS;
-      float v = BEAM_NEG_INF;
+      const int q = tid + k * CTC_THREADS;
+      float v = CTC_NEG_INF;
       if (q < B) {
         const float lpe = b.lpe[q];
         const int ps = b.pslot[q];
         const float a0 = b.pnb[cur][q] + lpe;
-        float a1 = BEAM_NEG_INF, a2 = BEAM_NEG_INF;
+        float a1 = CTC_NEG_INF, a2 = CTC_NEG_INF;
         if (ps >= 0) {
           a1 = b.pb[cur][ps] + lpe;
           if (b.last[cur][ps] != b.last[cur][q]) a2 = b.pnb[cur][ps] + lpe;
         }
-        const float pb = b.tot[q] + lpb, pnb = beam_lse3(a0, a1, a2);
+        const float pb = b.tot[q] + lpb, pnb = ctc_lse3(a0, a1, a2);
         b.stay_pb[q] = pb;
         b.stay_pnb[q] = pnb;
-        v = beam_lse3(pb, pnb, BEAM_NEG_INF);
+        v = ctc_lse3(pb, pnb, CTC_NEG_INF);
       } else if (q < Q) {
         const int j = (q - B) / K, c = b.top_class[(q - B) % K];
         v = b.top_logp[(q - B) % K] + (c == b.last[cur][j] ? b.pb[cur][j] : b.tot[j]);
@@ -225,7 +205,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_k(const T* __restrict__
     int rk[BEAM_QPT];
 #pragma unroll
     for (int k = 0; k < BEAM_QPT; k++) {
-      const int q = tid + k * BEAM_THREADS;
+      const int q = tid + k * CTC_THREADS;
       mine[k] = q < Q ? b.key[q] : 0;
       rk[k] = 0;
     }
@@ -234,11 +214,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_k(const T* __restrict__
       const unsigned long long k0 = b.key[q2], k1 = b.key[q2 + 1];
 #pragma unroll
       for (int k = 0; k < BEAM_QPT; k++)
-        if (wave_first + k * BEAM_THREADS < Q) rk[k] += (k0 > mine[k]) + (k1 > mine[k]);
+        if (wave_first + k * CTC_THREADS < Q) rk[k] += (k0 > mine[k]) + (k1 > mine[k]);
     }
 #pragma unroll
     for (int k = 0; k < BEAM_QPT; k++) {
-      const int q = tid + k * BEAM_THREADS, slot = rk[k];
+      const int q = tid + k * CTC_THREADS, slot = rk[k];
       if (mine[k] != 0 && slot < W) {
         if (q < B) {
           b.node[nxt][slot] = b.node[cur][q]; b.parent[nxt][slot] = b.parent[cur][q]; b.last[nxt][slot] = b.last[cur][q];
@@ -249,7 +229,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_k(const T* __restrict__
           b.node[nxt][slot] = -1;   // found or created below
           b.parent[nxt][slot] = b.node[cur][j]; b.last[nxt][slot] = b.top_class[(q - B) % K];
           b.len[nxt][slot] = b.len[cur][j] + 1;
-          b.pb[nxt][slot] = BEAM_NEG_INF; b.pnb[nxt][slot] = sc[k];
+          b.pb[nxt][slot] = CTC_NEG_INF; b.pnb[nxt][slot] = sc[k];
         }
         atomicMax(&b.count[nxt], slot + 1);
       }
@@ -263,7 +243,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_k(const T* __restrict__
       unsigned key = 0;
       int id = 0;
       if (ext) {
-        key = (unsigned)b.parent[nxt][tid] * BEAM_MAX_C + (unsigned)b.last[nxt][tid];
+        key = (unsigned)b.parent[nxt][tid] * CTC_MAX_C + (unsigned)b.last[nxt][tid];
         id = beam_hash_find(hs, H, key);
       }
       const bool fresh = ext && id == 0;
@@ -279,8 +259,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_k(const T* __restrict__
       if (tid < W) {
         const bool live = tid < B2;
         bn[t * W + tid] = live ? (ext ? id : b.node[nxt][tid]) : -1;
-        bs[(t * W + tid) * 2] = live ? b.pb[nxt][tid] : BEAM_NEG_INF;
-        bs[(t * W + tid) * 2 + 1] = live ? b.pnb[nxt][tid] : BEAM_NEG_INF;
+        bs[(t * W + tid) * 2] = live ? b.pb[nxt][tid] : CTC_NEG_INF;
+        bs[(t * W + tid) * 2 + 1] = live ? b.pnb[nxt][tid] : CTC_NEG_INF;
       }
     }
     __syncthreads();
@@ -298,7 +278,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_k(const T* __restrict__
   if (tid < W) {
     const bool live = tid < B;
     const int len = live ? b.len[cur][tid] : 0;
-    out_scores[(long long)n * W + tid] = live ? beam_lse3(b.pb[cur][tid], b.pnb[cur][tid], BEAM_NEG_INF) : BEAM_NEG_INF;
+    out_scores[(long long)n * W + tid] = live ? ctc_lse3(b.pb[cur][tid], b.pnb[cur][tid], CTC_NEG_INF) : CTC_NEG_INF;
     out_lengths[(long long)n * W + tid] = len;
     int64_t* o = out + ((long long)n * W + tid) * S;
     int node = live ? b.node[cur][tid] : 0;
@@ -309,7 +289,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_k(const T* __restrict__
   }
   for (int k = 0; k < W; k++) {
     int64_t* o = out + ((long long)n * W + k) * S;
-    for (int p = (k < B ? b.len[cur][k] : 0) + tid; p < S; p += BEAM_THREADS) o[p] = -1;
+    for (int p = (k < B ? b.len[cur][k] : 0) + tid; p < S; p += CTC_THREADS) o[p] = -1;
   }
 }
 
@@ -320,7 +300,7 @@ __global__ __launch_bounds__(EDIT_THREADS) void edit_distance_k(const int64_t* _
   __shared__ int64_t sa[EDIT_MAX_L], sb[EDIT_MAX_L];
   __shared__ int diag[3][EDIT_MAX_L + 1];
   const int n = blockIdx.x, tid = threadIdx.x;
-  const int la = beam_clamp_len(a_len[n], La), lb = beam_clamp_len(b_len[n], Lb);
+  const int la = ctc_clamp_len(a_len[n], La), lb = ctc_clamp_len(b_len[n], Lb);
   for (int i = tid; i < la; i += EDIT_THREADS) sa[i] = a[(long long)n * La + i];
   for (int j = tid; j < lb; j += EDIT_THREADS) sb[j] = bq[(long long)n * Lb + j];
   __syncthreads();
@@ -351,10 +331,10 @@ __global__ __launch_bounds__(EDIT_THREADS) void edit_distance_k(const int64_t* _
 
 // ---------------------------------------------------------------------------------------------- host side
 #define BEAM_LAUNCH_TOP(T, ...)                                                                                                          \
-  hipLaunchKernelGGL((ctc_beam_top_k<T>), dim3((unsigned)((rows + 3) / 4)), dim3(BEAM_THREADS), 0, st, (const T*)logits, input_lengths, row_lse, \
+  hipLaunchKernelGGL((ctc_beam_top_k<T>), dim3((unsigned)((rows + 3) / 4)), dim3(CTC_THREADS), 0, st, (const T*)logits, input_lengths, row_lse, \
                      top_logp, top_class, (long long)rows, (int)S, (int)C, (int)blank, (int)K)
 #define BEAM_LAUNCH(T, ...)                                                                                                                  \
-  hipLaunchKernelGGL((ctc_beam_k<T>), dim3((unsigned)N), dim3(BEAM_THREADS), 0, st, (const T*)logits, input_lengths, (const float*)row_lse,        \
+  hipLaunchKernelGGL((ctc_beam_k<T>), dim3((unsigned)N), dim3(CTC_THREADS), 0, st, (const T*)logits, input_lengths, (const float*)row_lse,        \
                      (const float*)top_logp, (const int32_t*)top_class, (unsigned long long*)hash, out, out_lengths, out_scores, out_count,      \
                      node_parent, node_label, node_count, beam_node, beam_score, (int)S, (int)C, (int)blank, (int)W, (int)K, (int)H)
 
@@ -362,16 +342,13 @@ extern "C" int pero_ctc_beam(const void* logits, const int64_t* input_lengths, i
                              int64_t* out_count, int32_t* node_parent, int32_t* node_label, int32_t* node_count, int32_t* beam_node,
                              float* beam_score, float* row_lse, float* top_logp, int32_t* top_class, uint64_t* hash, int64_t N, int64_t S, int64_t C,
                              int64_t blank, int64_t W, int dtype, void* stream) {
-  PERO_REQUIRE(dtype == PERO_F32 || dtype == PERO_BF16, "pero_ctc_beam: bad dtype");
-  PERO_REQUIRE(N > 0 && N < (1LL << 31) && S > 0 && C >= 2 && W > 0, "pero_ctc_beam: bad sizes (N %lld, S %lld, C %lld, W %lld)", (long long)N,
-               (long long)S, (long long)C, (long long)W);
-  PERO_REQUIRE(blank >= 0 && blank < C, "pero_ctc_beam: blank %lld outside [0, C = %lld)", (long long)blank, (long long)C);
-  if (S > BEAM_MAX_S || C > BEAM_MAX_C || W > BEAM_MAX_W) {
-    pero_set_error("pero_ctc_beam: supported up to S = %d, C = %d and W = %d (got S %lld, C %lld, W %lld)", BEAM_MAX_S, BEAM_MAX_C, BEAM_MAX_W,
-                   (long long)S, (long long)C, (long long)W);
+  const int rc = ctc_check("pero_ctc_beam", N, S, C, 0, blank, dtype);
+  if (rc != PERO_OK) return rc;
+  PERO_REQUIRE(W > 0, "pero_ctc_beam: bad sizes (W %lld)", (long long)W);
+  if (W > BEAM_MAX_W) {
+    pero_set_error("pero_ctc_beam: supported up to W = %d (got W %lld)", BEAM_MAX_W, (long long)W);
     return PERO_E_UNSUPPORTED;
   }
-  PERO_REQUIRE(N * S < (1LL << 31), "pero_ctc_beam: N * S must be below 2^31");
   PERO_REQUIRE(logits && input_lengths && out && out_lengths && out_scores && out_count && node_parent && node_label && node_count && beam_node &&
                    beam_score && row_lse && top_logp && top_class && hash,
                "pero_ctc_beam: null pointer");

@@ -1,4 +1,4 @@
-// Host-side launch helpers shared by the loss kernels (losses.hip, ntxent_ragged.hip).
+// Host-side launch helpers shared by the loss kernels (losses.hip, ntxent_ragged.hip) and, through ctc_common.hpp, by the CTC sources.
 #pragma once
 #include "common.hpp"
 #include <initializer_list>

@@ -900,6 +900,16 @@ def _ctc_args(logits, targets, input_lengths, target_lengths):
     return n, rows // n, C, targets.shape[1]
 
 
+def _ctc_rows_args(name, logits, input_lengths):
+    """The decoders' arguments: (N, S, C) of contiguous (N*S, C) logits and contiguous int64 input_lengths (N), N >= 1."""
+    _req_cuda(logits, input_lengths)
+    n = input_lengths.numel()
+    rows, C = logits.shape
+    if not logits.is_contiguous() or n == 0 or rows % n or input_lengths.dtype != torch.int64 or not input_lengths.is_contiguous():
+        raise ValueError(f"{name}: logits must be contiguous (N*S, C), input_lengths contiguous int64 (N)")
+    return n, rows // n, C
+
+
 def ctc_fwd(logits, targets, input_lengths, target_lengths, blank=0):
     """logits (N*S, C) f32 / bf16; targets (N, Lmax), input_lengths, target_lengths (N) int64, all on the device.
     Returns (nll (N) f32, row_lse (N*S) f32, alpha (N, S, 2 Lmax + 1) f32); the last two go to ctc_bwd."""
@@ -925,12 +935,7 @@ def ctc_bwd(logits, targets, input_lengths, target_lengths, row_lse, alpha, nll,
 
 def ctc_greedy(logits, input_lengths, blank=0):
     """Greedy CTC decoding of (N*S, C) logits: (labels (N, S) int64 padded with -1, lengths (N) int64), on the device."""
-    _req_cuda(logits, input_lengths)
-    n = input_lengths.numel()
-    rows, C = logits.shape
-    if not logits.is_contiguous() or rows % n or input_lengths.dtype != torch.int64 or not input_lengths.is_contiguous():
-        raise ValueError("ctc_greedy: logits must be contiguous (N*S, C), input_lengths contiguous int64 (N)")
-    S = rows // n
+    n, S, C = _ctc_rows_args("ctc_greedy", logits, input_lengths)
     out = torch.empty((n, S), device=logits.device, dtype=torch.int64)
     out_lengths = torch.empty(n, device=logits.device, dtype=torch.int64)
     call("pero_ctc_greedy", ptr(logits), ptr(input_lengths), ptr(out), ptr(out_lengths), n, S, C, blank, dt(logits), stream())
@@ -949,12 +954,8 @@ def ctc_beam(logits, input_lengths, beam_width, blank=0, return_trace=False):
     """CTC prefix beam search of (N*S, C) logits, all on the device: (labels (N, W, S) int64 padded with -1, lengths (N, W) int64,
     scores (N, W) f32 best first, count (N) int64).  return_trace: also the dict of include/pero_hip.h's trace (node_parent, node_label,
     node_count, beam_node, beam_score)."""
-    _req_cuda(logits, input_lengths)
-    n = input_lengths.numel()
-    rows, C = logits.shape
-    if not logits.is_contiguous() or n == 0 or rows % n or input_lengths.dtype != torch.int64 or not input_lengths.is_contiguous():
-        raise ValueError("ctc_beam: logits must be contiguous (N*S, C), input_lengths contiguous int64 (N)")
-    S, W, dev = rows // n, int(beam_width), logits.device
+    n, S, C = _ctc_rows_args("ctc_beam", logits, input_lengths)
+    rows, W, dev = n * S, int(beam_width), logits.device
     if W < 1 or C < 2:
         raise ValueError("ctc_beam: beam_width >= 1 and C >= 2")
     K, H = ctc_beam_workspace(S, C, W)

@@ -187,6 +187,42 @@ def test_backpointers_in_the_global_workspace(dtype):
     assert same_bits(forced, raw_align(c["logits"].to(dtype), c["targets"], c["input_lengths"], c["target_lengths"], 0))
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_row_lse_has_the_same_bits_in_loss_aligner_and_beam(dtype):
+    """include/pero_hip.h defines score, label_logp and the beam's log-probabilities with pero_ctc_fwd's row_lse: the three entry points
+    write the same int32 patterns on every row t < T (T = 0, 5 and S), and the two workspaces keep their poison behind T."""
+    from pero_pretraining_amd import _lib
+    from pero_pretraining_amd.ops import ctc_beam_workspace, ctc_fwd, dt, ptr, stream
+    N, S, C, Lmax, W, blank = 3, 12, 37, 4, 4, 0
+    gen = torch.Generator().manual_seed(13)
+    lg = (4 * torch.randn(N * S, C, generator=gen)).to(dtype).cuda()
+    il, tl = torch.tensor([0, 5, 12]).cuda(), torch.tensor([0, 2, 4]).cuda()
+    tg = torch.randint(1, C, (N, Lmax), generator=gen).cuda()
+    K, H = ctc_beam_workspace(S, C, W)
+
+    def poisoned(kind, *shape):
+        return torch.full((int(np.prod(shape)) * kind.itemsize,), 0x5a, dtype=torch.uint8, device="cuda").view(kind).view(shape)
+
+    i32, i64 = torch.int32, torch.int64
+    from_fwd = ctc_fwd(lg, tg, il, tl, blank)[1]
+    from_align, from_beam = poisoned(F32, N * S), poisoned(F32, N * S)
+    outs = [poisoned(i32, N, S), poisoned(i32, N, Lmax, 2), poisoned(F32, N), poisoned(F32, N), poisoned(F32, N, Lmax)]
+    back = poisoned(torch.uint8, N * S * (2 * Lmax + 1))
+    _lib.call("pero_ctc_align", ptr(lg), ptr(tg), ptr(il), ptr(tl), *[ptr(o) for o in outs], ptr(from_align), ptr(back), N, S, C, Lmax, blank, 0,
+              dt(lg), stream())
+    outs = [poisoned(i64, N, W, S), poisoned(i64, N, W), poisoned(F32, N, W), poisoned(i64, N), poisoned(i32, N, S * W + 1),
+            poisoned(i32, N, S * W + 1), poisoned(i32, N), poisoned(i32, N, S, W), poisoned(F32, N, S, W, 2)]
+    work = [poisoned(F32, N * S, K), poisoned(i32, N * S, K), poisoned(i64, N, H)]
+    _lib.call("pero_ctc_beam", ptr(lg), ptr(il), *[ptr(o) for o in outs], ptr(from_beam), *[ptr(w) for w in work], N, S, C, blank, W, dt(lg),
+              stream())
+    written = (torch.arange(S)[None, :] < il.cpu()[:, None]).reshape(N * S)
+    assert int(written.sum()) == 17
+    fwd_bits, align_bits, beam_bits = (v.cpu().view(i32) for v in (from_fwd, from_align, from_beam))
+    assert bool(torch.isfinite(from_fwd).all())                                       # pero_ctc_fwd: every row
+    assert torch.equal(align_bits[written], fwd_bits[written]) and torch.equal(beam_bits[written], fwd_bits[written])
+    assert bool((align_bits[~written] == 0x5a5a5a5a).all()) and bool((beam_bits[~written] == 0x5a5a5a5a).all())
+
+
 def test_ops_wrapper_and_argument_checks(ops):
     from pero_pretraining_amd._lib import PeroHipError
     c = ctc_ref.case("mixed-C37-blank36-x4")
