@@ -576,6 +576,39 @@ int pero_ctc_greedy(const void* logits, const int64_t* input_lengths, int64_t* o
  *   bytes, K = min(W + 1, C - 1); hash 8 N H bytes, H = the smallest power of two >= 2 S W (cleared by the call itself).
  * Supported: 2 <= C <= 8192, 1 <= S <= 512, 1 <= W <= 32 (PERO_E_UNSUPPORTED above), N S < 2^31.
  *
+ * pero_ctc_beam_lm: pero_ctc_beam with shallow fusion of a back-off n-gram model over the class ids (the blank is no symbol); DESIGN.md
+ * section 15.  Arguments, outputs, trace, workspaces and tie rule of pero_ctc_beam, the same kernel body, and in addition:
+ *   The model, a deterministic automaton of M states in flat arrays on the device (read-only for the call).  State 0 is the empty context,
+ *   `start` the state before the first label.  Per state s: lm_backoff_state (M) int32 (-1 for state 0), lm_backoff_weight (M) f32,
+ *   lm_final (M) f32 = ln p(end | s) with the back-off already resolved (zeros for a model without an end symbol); all logs natural.
+ *   Arcs in CSR form: lm_arc_begin (M + 1) int32, and per arc lm_arc_label (A) int32 ascending inside a state, lm_arc_logp (A) f32,
+ *   lm_arc_next (A) int32, the state behind the arc.
+ *     lookup(s, c):  acc = 0;  while c is no arc of s: acc = acc + lm_backoff_weight[s], s = lm_backoff_state[s];
+ *                    lm = acc + lm_arc_logp[arc], next = lm_arc_next[arc]                      f32 additions in exactly this order.
+ *   c without an arc in state 0: p + c is NO candidate, whatever the weights are (how a caller forbids a class).  The kernel checks every
+ *   index it reads from these arrays against M and A and follows at most PERO_CTC_LM_MAX_ORDER back-off steps; a look-up that fails a check
+ *   counts as "no candidate", so malformed tables cannot make it read out of range.
+ *   Scores.  pb, pnb of a string carry alpha LM(string) + beta |string| inside them (alpha = lm_weight, beta = length_bonus, both finite).
+ *   With w(p, c) = fadd(fmul(alpha, lm(state(p), c)), beta), one f32 multiplication and one f32 addition, never fused:
+ *     stay:           p    gets pb' (+)= tot + logp_t(blank), and for p != (): pnb' (+)= pnb + logp_t(e);                       (unchanged)
+ *     extend, c != blank: p+c gets pnb' (+)= (logp_t(c) + w(p, c)) + (c == e ? pb : tot),                  the additions in this order,
+ *       if p + c is an entry of the current beam (the contribution is part of that entry's stay; every class, as in pero_ctc_beam), or
+ *       if c is among the first K non-blank classes of the frame's order (logit descending, class ascending) - a NEW string.
+ *   w is a function of the string, so the contributions merged into one string carry the same w.  K is clamped to [1, C - 1].  With a
+ *   language model the W + 1 argument of pero_ctc_beam fails (the score of p + c depends on p), so K < C - 1 is a pruning of the new
+ *   strings ("cutoff top n"), K = C - 1 the unpruned search.  Candidate numbers for the tie rule: as in pero_ctc_beam with this K.
+ *   Nodes.  node_lm_state, node_lm_weight (N, S W + 1) int32 / f32, entries [0, node_count[n]) written: node 0 has (start, 0); the node
+ *   of p + c gets (next, w(p, c)) when it is created, and a prefix that comes back into the beam takes both from its node.
+ *   node_lm_total[k] = fadd(node_lm_total[parent], node_lm_weight[k]) from the root down (node 0: 0) is the LM part of a string's score.
+ *   End of line.  use_final != 0: every hypothesis' total becomes fadd(total, fmul(alpha, lm_final[state])); the <= W hypotheses are
+ *   ranked again by these values (equal values: the order of the last frame); the trace's last frame keeps the order before.
+ *   out_scores (N, W): these totals, best first.  out_lm (N, W) f32: node_lm_total of the hypothesis, with use_final
+ *   fadd(that, fmul(alpha, lm_final[state])); 0 in unused slots.  T = 0: the empty string, score and out_lm 0 (+ alpha lm_final[start]).
+ *   With alpha = 0, beta = 0, use_final = 0 and K = min(W + 1, C - 1), w = +0 for finite tables and every output and trace entry that
+ *   pero_ctc_beam specifies has pero_ctc_beam's bits (state 0 must hold an arc for every non-blank class).
+ * Workspaces as pero_ctc_beam with this K.  Supported: as pero_ctc_beam, and W (K + 1) <= 1088 after the clamp (PERO_E_UNSUPPORTED
+ * above: K <= 67 at W = 16, K <= 33 at W = 32), 1 <= M, 0 <= A < 2^31, 0 <= start < M.
+ *
  * pero_edit_distance: dist[n] (int64) = the Levenshtein distance (insertion, deletion, substitution: 1 each) of a[n][0, a_len[n])
  * and b[n][0, b_len[n]).  a (N, La), b (N, Lb) int64, padded (entries behind the lengths are never read; a null pointer is
  * allowed for a zero-width matrix); a_len, b_len (N) int64, clamped to [0, La], [0, Lb].  totals (2 int64 on the device, may be
@@ -585,6 +618,14 @@ int pero_ctc_beam(const void* logits, const int64_t* input_lengths, int64_t* out
                   int64_t* out_count, int32_t* node_parent, int32_t* node_label, int32_t* node_count, int32_t* beam_node,
                   float* beam_score, float* row_lse, float* top_logp, int32_t* top_class, uint64_t* hash, int64_t N, int64_t S, int64_t C,
                   int64_t blank, int64_t W, int dtype, void* stream);
+#define PERO_CTC_LM_MAX_ORDER 16   /* back-off steps of one look-up the kernel follows: the longest context + 1 of a model it can walk */
+int pero_ctc_beam_lm(const void* logits, const int64_t* input_lengths, const int32_t* lm_backoff_state, const float* lm_backoff_weight,
+                     const float* lm_final, const int32_t* lm_arc_begin, const int32_t* lm_arc_label, const float* lm_arc_logp,
+                     const int32_t* lm_arc_next, int64_t* out, int64_t* out_lengths, float* out_scores, float* out_lm, int64_t* out_count,
+                     int32_t* node_parent, int32_t* node_label, int32_t* node_lm_state, float* node_lm_weight, int32_t* node_count,
+                     int32_t* beam_node, float* beam_score, float* row_lse, float* top_logp, int32_t* top_class, uint64_t* hash, int64_t N,
+                     int64_t S, int64_t C, int64_t blank, int64_t W, int64_t K, int64_t M, int64_t A, int64_t start, float lm_weight,
+                     float length_bonus, int use_final, int dtype, void* stream);
 int pero_edit_distance(const int64_t* a, const int64_t* a_len, const int64_t* b, const int64_t* b_len, int64_t* dist, int64_t* totals,
                        int64_t N, int64_t La, int64_t Lb, void* stream);
 

@@ -101,6 +101,7 @@ SIGNATURES = {
     "pero_ctc_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp],
     "pero_ctc_greedy": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
     "pero_ctc_beam": [_vp] * 15 + [_i64, _i64, _i64, _i64, _i64, _i32, _vp],
+    "pero_ctc_beam_lm": [_vp] * 25 + [_i64] * 9 + [_f32, _f32, _i32, _i32, _vp],
     "pero_edit_distance": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp],
     "pero_ctc_align": [_vp] * 11 + [_i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp],
 }

@@ -6,16 +6,21 @@
 //                                      parallel)
 //                      ctc_beam_k      one workgroup per line, frame by frame: the <= W (K + 1) candidates of the frame are scored by the
 //                                      threads, ranked by counting, the kept ones find or create their prefix node; five barriers per frame
+//   pero_ctc_beam_lm   the same two kernels; ctc_beam_k<T, true> adds the n-gram term of every new string (one walk of the LM automaton per
+//                                      extension candidate, issued ahead of the frame's first barrier) and takes K from the caller
 //   pero_edit_distance edit_distance_k one workgroup per pair: the anti-diagonals of the unit-cost table out of LDS, one barrier each
 //
 // Why K = W + 1 classes are enough: the extensions of one beam entry j score logp(c) + tot_j, except c = last_j, which scores logp(c) + pb_j
 // <= logp(c) + tot_j.  A class outside the row's best W + 1 is beaten, for the same j, by at least W extensions (or by the stay candidates
-// they merged into, whose totals are no smaller), so it is never among the frame's best W.
+// they merged into, whose totals are no smaller), so it is never among the frame's best W.  With a language model the score of p + c depends
+// on p and the argument is gone: K is the caller's (a pruning of the NEW strings), bounded by W (K + 1) <= BEAM_MAX_Q.
 #include "ctc_common.hpp"
 
 #define BEAM_MAX_W 32
 #define BEAM_MAX_K (BEAM_MAX_W + 1)
 #define BEAM_MAX_Q (BEAM_MAX_W * (BEAM_MAX_K + 1))                      // stay + extension candidates of one frame
+#define BEAM_LM_MAX_K (BEAM_MAX_Q - 1)                                  // W = 1: the largest K with W (K + 1) <= BEAM_MAX_Q
+#define BEAM_LM_MAX_HOPS PERO_CTC_LM_MAX_ORDER                          // back-off steps of one look-up
 #define BEAM_QPT ((BEAM_MAX_Q + CTC_THREADS - 1) / CTC_THREADS)         // candidates of one thread
 #define EDIT_THREADS 256
 #define EDIT_MAX_L 512
@@ -95,19 +100,66 @@ static __device__ __forceinline__ void beam_hash_insert(unsigned long long* hs, 
   }
 }
 
-// One beam entry: the prefix's node, its parent node and last label (-1 for the empty prefix), its length, pb and pnb.  Two copies in ping-pong.
+// The language model of pero_ctc_beam_lm (include/pero_hip.h): the automaton's arrays, the fusion weights and the LM part of the trace.  All null /
+// zero for pero_ctc_beam, whose kernel never reads it.
+struct BeamLm {
+  const int32_t* backoff_state;
+  const float* backoff_weight;
+  const float* final;
+  const int32_t* arc_begin;
+  const int32_t* arc_label;
+  const float* arc_logp;
+  const int32_t* arc_next;
+  float* out_lm;
+  int32_t* node_state;
+  float* node_weight;
+  int M, A, start, use_final;
+  float alpha, beta;
+};
+
+// lm(s, c) and the next state: the header's walk, f32 additions in its order.  false: c has no arc in state 0 (a forbidden class), or the tables
+// are malformed (an index outside its array, a back-off chain longer than BEAM_LM_MAX_HOPS): nothing out of range is ever read.
+static __device__ __forceinline__ bool beam_lm_lookup(const BeamLm& lm, int s, int c, float& logp, int& next) {
+  float acc = 0.f;
+  for (int hop = 0; hop <= BEAM_LM_MAX_HOPS; hop++) {
+    if ((unsigned)s >= (unsigned)lm.M) return false;
+    const int first = lm.arc_begin[s], end = lm.arc_begin[s + 1];
+    if (first < 0 || end > lm.A || first > end) return false;
+    int lo = first, hi = end;   // the first arc of s whose label is >= c
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (lm.arc_label[mid] < c) lo = mid + 1;
+      else hi = mid;
+    }
+    if (lo < end && lm.arc_label[lo] == c) {
+      logp = __fadd_rn(acc, lm.arc_logp[lo]);
+      next = lm.arc_next[lo];
+      return (unsigned)next < (unsigned)lm.M;
+    }
+    if (s == 0) return false;
+    acc = __fadd_rn(acc, lm.backoff_weight[s]);
+    s = lm.backoff_state[s];
+  }
+  return false;
+}
+
+// One beam entry: the prefix's node, its parent node and last label (-1 for the empty prefix), its length, pb and pnb; with a language model its LM
+// state, the weight w its last label added and the sum of the w from the root.  Two copies in ping-pong.  MAXK: the frame's classes.
+template <int MAXK>
 struct BeamLds {
   int node[2][BEAM_MAX_W], parent[2][BEAM_MAX_W], last[2][BEAM_MAX_W], len[2][BEAM_MAX_W];
   float pb[2][BEAM_MAX_W], pnb[2][BEAM_MAX_W];
+  int lm_state[2][BEAM_MAX_W];
+  float lm_w[2][BEAM_MAX_W], lm_total[2][BEAM_MAX_W];
   float tot[BEAM_MAX_W], lpe[BEAM_MAX_W], stay_pb[BEAM_MAX_W], stay_pnb[BEAM_MAX_W];
   int pslot[BEAM_MAX_W];   // the beam slot of the entry's parent prefix, -1 if that prefix is not in the beam
   alignas(16) unsigned long long key[BEAM_MAX_Q];   // the candidates' sort keys (beam_key), read two at a time by the ranking loop
-  int top_class[BEAM_MAX_K];             // the frame's best classes and their log-probabilities
-  float top_logp[BEAM_MAX_K];
+  int top_class[MAXK];                   // the frame's best classes and their log-probabilities
+  float top_logp[MAXK];
   int count[2], nodes;
 };
 
-template <typename T>
+template <typename T, bool LM>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ logits, const int64_t* __restrict__ input_lengths,
                                                            const float* __restrict__ row_lse, const float* __restrict__ top_logp,
                                                            const int32_t* __restrict__ top_class, unsigned long long* __restrict__ hash,
@@ -115,8 +167,8 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
                                                            int64_t* __restrict__ out_count, int32_t* __restrict__ node_parent,
                                                            int32_t* __restrict__ node_label, int32_t* __restrict__ node_count,
                                                            int32_t* __restrict__ beam_node, float* __restrict__ beam_score, int S, int C, int blank,
-                                                           int W, int K, int H) {
-  __shared__ BeamLds b;
+                                                           int W, int K, int H, BeamLm lm) {
+  __shared__ BeamLds<LM ? BEAM_LM_MAX_K : BEAM_MAX_K> b;
   const int n = blockIdx.x, tid = threadIdx.x;
   const int Tn = ctc_clamp_len(input_lengths[n], S);
   const T* x = logits + (long long)n * S * C;
@@ -128,6 +180,8 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
   int32_t* nl = node_label + (long long)n * (S * W + 1);
   int32_t* bn = beam_node + (long long)n * S * W;
   float* bs = beam_score + (long long)n * S * W * 2;
+  int32_t* ns = LM ? lm.node_state + (long long)n * (S * W + 1) : nullptr;
+  float* nw = LM ? lm.node_weight + (long long)n * (S * W + 1) : nullptr;
 
   for (int i = tid; i < H; i += CTC_THREADS) hs[i] = 0;
   if (tid == 0) {   // before frame 0: the empty prefix, pb = 0, pnb = -inf
@@ -137,6 +191,11 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
     b.nodes = 1;
     np[0] = -1;
     nl[0] = -1;
+    if (LM) {
+      b.lm_state[0][0] = lm.start; b.lm_w[0][0] = 0.f; b.lm_total[0][0] = 0.f;
+      ns[0] = lm.start;
+      nw[0] = 0.f;
+    }
   }
   __threadfence();   // the cleared slots are in memory before the first atomic reads one
   __syncthreads();
@@ -147,6 +206,22 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
     const int B = b.count[cur];
     const float le = lse[t];
     const float lpb = ctc_logp(Elem<T>::ld(x + (long long)t * C + blank), le);
+    // the LM term of the thread's extension candidates: w = alpha lm(state of p, c) + beta, and the state of p + c.  Chains of dependent loads,
+    // issued here so that they run beside the loads and the parent search below.
+    float lw[BEAM_QPT];
+    int ln[BEAM_QPT];
+    if (LM) {
+#pragma unroll
+      for (int k = 0; k < BEAM_QPT; k++) {
+        const int q = tid + k * CTC_THREADS;
+        lw[k] = CTC_NEG_INF;   // no candidate
+        ln[k] = 0;
+        if (q >= B && q < B * (K + 1)) {
+          float l;
+          if (beam_lm_lookup(lm, b.lm_state[cur][(q - B) / K], tc[t * K + (q - B) % K], l, ln[k])) lw[k] = __fadd_rn(__fmul_rn(lm.alpha, l), lm.beta);
+        }
+      }
+    }
     if (tid < B) {
       const int last = b.last[cur][tid], pn = b.parent[cur][tid];
       b.tot[tid] = ctc_lse3(b.pb[cur][tid], b.pnb[cur][tid], CTC_NEG_INF);
@@ -157,10 +232,11 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
           if (b.node[cur][j] == pn) ps = j;
       b.pslot[tid] = ps;
     }
-    if (tid >= 64 && tid < 64 + K) {   // the second wave, beside the first wave's work above
-      b.top_class[tid - 64] = tc[t * K + tid - 64];
-      b.top_logp[tid - 64] = tv[t * K + tid - 64];
-    }
+    if (tid >= 64)   // the other waves, beside the first wave's work above (K <= BEAM_MAX_K: the second wave alone, one round)
+      for (int r = tid - 64; r < K; r += CTC_THREADS - 64) {
+        b.top_class[r] = tc[t * K + r];
+        b.top_logp[r] = tv[t * K + r];
+      }
     if (tid == 0) b.count[nxt] = 0;
     __syncthreads();
 
@@ -177,9 +253,10 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
         const int ps = b.pslot[q];
         const float a0 = b.pnb[cur][q] + lpe;
         float a1 = CTC_NEG_INF, a2 = CTC_NEG_INF;
-        if (ps >= 0) {
-          a1 = b.pb[cur][ps] + lpe;
-          if (b.last[cur][ps] != b.last[cur][q]) a2 = b.pnb[cur][ps] + lpe;
+        if (ps >= 0) {   // the parent's extension carries the w of this entry's last label, as when the string was created
+          const float lpw = LM ? lpe + b.lm_w[cur][q] : lpe;
+          a1 = b.pb[cur][ps] + lpw;
+          if (b.last[cur][ps] != b.last[cur][q]) a2 = b.pnb[cur][ps] + lpw;
         }
         const float pb = b.tot[q] + lpb, pnb = ctc_lse3(a0, a1, a2);
         b.stay_pb[q] = pb;
@@ -187,7 +264,9 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
         v = ctc_lse3(pb, pnb, CTC_NEG_INF);
       } else if (q < Q) {
         const int j = (q - B) / K, c = b.top_class[(q - B) % K];
-        v = b.top_logp[(q - B) % K] + (c == b.last[cur][j] ? b.pb[cur][j] : b.tot[j]);
+        float lpw = b.top_logp[(q - B) % K];
+        if (LM) lpw = lw[k] == CTC_NEG_INF ? CTC_NEG_INF : lpw + lw[k];
+        v = lpw + (c == b.last[cur][j] ? b.pb[cur][j] : b.tot[j]);
       }
       sc[k] = v;
       if (q < Q2) b.key[q] = beam_key(v, q);
@@ -224,12 +303,14 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
           b.node[nxt][slot] = b.node[cur][q]; b.parent[nxt][slot] = b.parent[cur][q]; b.last[nxt][slot] = b.last[cur][q];
           b.len[nxt][slot] = b.len[cur][q];
           b.pb[nxt][slot] = b.stay_pb[q]; b.pnb[nxt][slot] = b.stay_pnb[q];
+          if (LM) { b.lm_state[nxt][slot] = b.lm_state[cur][q]; b.lm_w[nxt][slot] = b.lm_w[cur][q]; b.lm_total[nxt][slot] = b.lm_total[cur][q]; }
         } else {
           const int j = (q - B) / K;
           b.node[nxt][slot] = -1;   // found or created below
           b.parent[nxt][slot] = b.node[cur][j]; b.last[nxt][slot] = b.top_class[(q - B) % K];
           b.len[nxt][slot] = b.len[cur][j] + 1;
           b.pb[nxt][slot] = CTC_NEG_INF; b.pnb[nxt][slot] = sc[k];
+          if (LM) { b.lm_state[nxt][slot] = ln[k]; b.lm_w[nxt][slot] = lw[k]; b.lm_total[nxt][slot] = b.lm_total[cur][j]; }   // the parent's sum: + w below
         }
         atomicMax(&b.count[nxt], slot + 1);
       }
@@ -252,8 +333,16 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
         id = base + __popcll(m & ((1ull << tid) - 1));   // new nodes are numbered in rank order
         np[id] = b.parent[nxt][tid];
         nl[id] = b.last[nxt][tid];
+        if (LM) {
+          ns[id] = b.lm_state[nxt][tid];
+          nw[id] = b.lm_w[nxt][tid];
+        }
         beam_hash_insert(hs, H, key, id);
+      } else if (LM && ext) {   // a prefix that comes back takes state and weight from its node (written in an earlier frame, behind a barrier)
+        b.lm_state[nxt][tid] = __hip_atomic_load(ns + id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        b.lm_w[nxt][tid] = __hip_atomic_load(nw + id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
+      if (LM && ext) b.lm_total[nxt][tid] = __fadd_rn(b.lm_total[nxt][tid], b.lm_w[nxt][tid]);
       if (ext) b.node[nxt][tid] = id;
       if (tid == 0) b.nodes = base + __popcll(m);
       if (tid < W) {
@@ -267,21 +356,41 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
     cur = nxt;
   }
 
-  // the hypotheses, best first: the beam is in rank order.  One thread per hypothesis walks its prefix back to the root.
+  // the hypotheses, best first: the beam is in rank order; with the LM's final term the totals are ranked once more (ties by the beam's order).
+  // One thread per hypothesis walks its prefix back to the root.
   const int B = b.count[cur];
   if (tid == 0) {
     out_count[n] = B;
     node_count[n] = b.nodes;
   }
+  if (tid < W) {
+    float total = tid < B ? ctc_lse3(b.pb[cur][tid], b.pnb[cur][tid], CTC_NEG_INF) : CTC_NEG_INF;
+    if (LM && lm.use_final && tid < B) total = __fadd_rn(total, __fmul_rn(lm.alpha, lm.final[b.lm_state[cur][tid]]));
+    b.tot[tid] = total;
+    b.key[tid] = tid < B ? beam_key(total, tid) : 0;
+    b.pslot[tid] = tid;
+  }
   __threadfence();   // the node table written above is read back below
   __syncthreads();
+  if (LM && lm.use_final && tid < B) {
+    int rank = 0;
+    for (int j = 0; j < B; j++) rank += b.key[j] > b.key[tid];
+    b.pslot[rank] = tid;   // a total of -inf (key 0) cannot be in the beam: the ranks are a permutation
+  }
+  if (LM) __syncthreads();
   if (tid < W) {
     const bool live = tid < B;
-    const int len = live ? b.len[cur][tid] : 0;
-    out_scores[(long long)n * W + tid] = live ? ctc_lse3(b.pb[cur][tid], b.pnb[cur][tid], CTC_NEG_INF) : CTC_NEG_INF;
+    const int e = b.pslot[tid];   // the beam entry of hypothesis tid
+    const int len = live ? b.len[cur][e] : 0;
+    out_scores[(long long)n * W + tid] = live ? b.tot[e] : CTC_NEG_INF;
+    if (LM) {
+      float part = live ? b.lm_total[cur][e] : 0.f;
+      if (lm.use_final && live) part = __fadd_rn(part, __fmul_rn(lm.alpha, lm.final[b.lm_state[cur][e]]));
+      lm.out_lm[(long long)n * W + tid] = part;
+    }
     out_lengths[(long long)n * W + tid] = len;
     int64_t* o = out + ((long long)n * W + tid) * S;
-    int node = live ? b.node[cur][tid] : 0;
+    int node = live ? b.node[cur][e] : 0;
     for (int p = len - 1; p >= 0; p--) {
       o[p] = __hip_atomic_load(nl + node, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       node = __hip_atomic_load(np + node, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -289,7 +398,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
   }
   for (int k = 0; k < W; k++) {
     int64_t* o = out + ((long long)n * W + k) * S;
-    for (int p = (k < B ? b.len[cur][k] : 0) + tid; p < S; p += CTC_THREADS) o[p] = -1;
+    for (int p = (k < B ? b.len[cur][b.pslot[k]] : 0) + tid; p < S; p += CTC_THREADS) o[p] = -1;
   }
 }
 
@@ -333,32 +442,66 @@ __global__ __launch_bounds__(EDIT_THREADS) void edit_distance_k(const int64_t* _
 #define BEAM_LAUNCH_TOP(T, ...)                                                                                                          \
   hipLaunchKernelGGL((ctc_beam_top_k<T>), dim3((unsigned)((rows + 3) / 4)), dim3(CTC_THREADS), 0, st, (const T*)logits, input_lengths, row_lse, \
                      top_logp, top_class, (long long)rows, (int)S, (int)C, (int)blank, (int)K)
-#define BEAM_LAUNCH(T, ...)                                                                                                                  \
-  hipLaunchKernelGGL((ctc_beam_k<T>), dim3((unsigned)N), dim3(CTC_THREADS), 0, st, (const T*)logits, input_lengths, (const float*)row_lse,        \
+#define BEAM_LAUNCH(T, LM)                                                                                                                   \
+  hipLaunchKernelGGL((ctc_beam_k<T, LM>), dim3((unsigned)N), dim3(CTC_THREADS), 0, st, (const T*)logits, input_lengths, (const float*)row_lse,    \
                      (const float*)top_logp, (const int32_t*)top_class, (unsigned long long*)hash, out, out_lengths, out_scores, out_count,      \
-                     node_parent, node_label, node_count, beam_node, beam_score, (int)S, (int)C, (int)blank, (int)W, (int)K, (int)H)
+                     node_parent, node_label, node_count, beam_node, beam_score, (int)S, (int)C, (int)blank, (int)W, (int)K, (int)H, lm)
+
+// Both entry points: the checks they share, then the two launches.  with_lm: ctc_beam_k<T, true> with the caller's K.
+static int beam_run(const char* name, const void* logits, const int64_t* input_lengths, int64_t* out, int64_t* out_lengths, float* out_scores,
+                    int64_t* out_count, int32_t* node_parent, int32_t* node_label, int32_t* node_count, int32_t* beam_node, float* beam_score,
+                    float* row_lse, float* top_logp, int32_t* top_class, uint64_t* hash, int64_t N, int64_t S, int64_t C, int64_t blank, int64_t W,
+                    int64_t K, bool with_lm, const BeamLm& lm, int dtype, void* stream) {
+  const int rc = ctc_check(name, N, S, C, 0, blank, dtype);
+  if (rc != PERO_OK) return rc;
+  PERO_REQUIRE(W > 0, "%s: bad sizes (W %lld)", name, (long long)W);
+  if (W > BEAM_MAX_W) {
+    pero_set_error("%s: supported up to W = %d (got W %lld)", name, BEAM_MAX_W, (long long)W);
+    return PERO_E_UNSUPPORTED;
+  }
+  PERO_REQUIRE(logits && input_lengths && out && out_lengths && out_scores && out_count && node_parent && node_label && node_count && beam_node &&
+                   beam_score && row_lse && top_logp && top_class && hash,
+               "%s: null pointer", name);
+  K = K < 1 ? 1 : (K > C - 1 ? C - 1 : K);
+  if (W * (K + 1) > BEAM_MAX_Q) {
+    pero_set_error("%s: supported up to W (K + 1) = %d (got W %lld, K %lld)", name, BEAM_MAX_Q, (long long)W, (long long)K);
+    return PERO_E_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t rows = N * S, H = beam_hash_slots(S, W);
+  DISPATCH_T(dtype, BEAM_LAUNCH_TOP, 0);
+  PERO_CHECK_LAUNCH("pero_ctc_beam (row lse, best classes)");
+  if (with_lm) DISPATCH_T(dtype, BEAM_LAUNCH, true);
+  else DISPATCH_T(dtype, BEAM_LAUNCH, false);
+  PERO_CHECK_LAUNCH("pero_ctc_beam (search)");
+  return PERO_OK;
+}
 
 extern "C" int pero_ctc_beam(const void* logits, const int64_t* input_lengths, int64_t* out, int64_t* out_lengths, float* out_scores,
                              int64_t* out_count, int32_t* node_parent, int32_t* node_label, int32_t* node_count, int32_t* beam_node,
                              float* beam_score, float* row_lse, float* top_logp, int32_t* top_class, uint64_t* hash, int64_t N, int64_t S, int64_t C,
                              int64_t blank, int64_t W, int dtype, void* stream) {
-  const int rc = ctc_check("pero_ctc_beam", N, S, C, 0, blank, dtype);
-  if (rc != PERO_OK) return rc;
-  PERO_REQUIRE(W > 0, "pero_ctc_beam: bad sizes (W %lld)", (long long)W);
-  if (W > BEAM_MAX_W) {
-    pero_set_error("pero_ctc_beam: supported up to W = %d (got W %lld)", BEAM_MAX_W, (long long)W);
-    return PERO_E_UNSUPPORTED;
-  }
-  PERO_REQUIRE(logits && input_lengths && out && out_lengths && out_scores && out_count && node_parent && node_label && node_count && beam_node &&
-                   beam_score && row_lse && top_logp && top_class && hash,
-               "pero_ctc_beam: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t rows = N * S, K = W + 1 < C - 1 ? W + 1 : C - 1, H = beam_hash_slots(S, W);
-  DISPATCH_T(dtype, BEAM_LAUNCH_TOP, 0);
-  PERO_CHECK_LAUNCH("pero_ctc_beam (row lse, best classes)");
-  DISPATCH_T(dtype, BEAM_LAUNCH, 0);
-  PERO_CHECK_LAUNCH("pero_ctc_beam (search)");
-  return PERO_OK;
+  return beam_run("pero_ctc_beam", logits, input_lengths, out, out_lengths, out_scores, out_count, node_parent, node_label, node_count, beam_node,
+                  beam_score, row_lse, top_logp, top_class, hash, N, S, C, blank, W, W + 1, false, BeamLm{}, dtype, stream);
+}
+
+extern "C" int pero_ctc_beam_lm(const void* logits, const int64_t* input_lengths, const int32_t* lm_backoff_state, const float* lm_backoff_weight,
+                                const float* lm_final, const int32_t* lm_arc_begin, const int32_t* lm_arc_label, const float* lm_arc_logp,
+                                const int32_t* lm_arc_next, int64_t* out, int64_t* out_lengths, float* out_scores, float* out_lm, int64_t* out_count,
+                                int32_t* node_parent, int32_t* node_label, int32_t* node_lm_state, float* node_lm_weight, int32_t* node_count,
+                                int32_t* beam_node, float* beam_score, float* row_lse, float* top_logp, int32_t* top_class, uint64_t* hash, int64_t N,
+                                int64_t S, int64_t C, int64_t blank, int64_t W, int64_t K, int64_t M, int64_t A, int64_t start, float lm_weight,
+                                float length_bonus, int use_final, int dtype, void* stream) {
+  PERO_REQUIRE(M >= 1 && M < (1LL << 31) && A >= 0 && A < (1LL << 31) && start >= 0 && start < M,
+               "pero_ctc_beam_lm: bad language model sizes (M %lld, A %lld, start %lld)", (long long)M, (long long)A, (long long)start);
+  PERO_REQUIRE(std::isfinite(lm_weight) && std::isfinite(length_bonus), "pero_ctc_beam_lm: lm_weight and length_bonus must be finite");
+  PERO_REQUIRE(lm_backoff_state && lm_backoff_weight && lm_final && lm_arc_begin && (A == 0 || (lm_arc_label && lm_arc_logp && lm_arc_next)) && out_lm &&
+                   node_lm_state && node_lm_weight,
+               "pero_ctc_beam_lm: null pointer");
+  const BeamLm lm = {lm_backoff_state, lm_backoff_weight, lm_final, lm_arc_begin, lm_arc_label, lm_arc_logp, lm_arc_next, out_lm, node_lm_state,
+                     node_lm_weight, (int)M, (int)A, (int)start, use_final != 0, lm_weight, length_bonus};
+  return beam_run("pero_ctc_beam_lm", logits, input_lengths, out, out_lengths, out_scores, out_count, node_parent, node_label, node_count, beam_node,
+                  beam_score, row_lse, top_logp, top_class, hash, N, S, C, blank, W, K, true, lm, dtype, stream);
 }
 
 extern "C" int pero_edit_distance(const int64_t* a, const int64_t* a_len, const int64_t* b, const int64_t* b_len, int64_t* dist, int64_t* totals,

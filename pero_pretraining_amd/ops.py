@@ -950,29 +950,67 @@ def ctc_beam_workspace(S, C, beam_width):
     return min(beam_width + 1, C - 1), H
 
 
+def _ctc_beam_buffers(n, S, W, K, H, dev):
+    """Outputs, trace and workspaces of pero_ctc_beam / pero_ctc_beam_lm: (out, out_lengths, out_scores, out_count, trace, row_lse, top_logp, top_class, hash)."""
+    i32, i64, f32 = torch.int32, torch.int64, torch.float32
+    trace = {"node_parent": torch.empty((n, S * W + 1), device=dev, dtype=i32), "node_label": torch.empty((n, S * W + 1), device=dev, dtype=i32),
+             "node_count": torch.empty(n, device=dev, dtype=i32), "beam_node": torch.empty((n, S, W), device=dev, dtype=i32),
+             "beam_score": torch.empty((n, S, W, 2), device=dev, dtype=f32)}
+    return (torch.empty((n, W, S), device=dev, dtype=i64), torch.empty((n, W), device=dev, dtype=i64), torch.empty((n, W), device=dev, dtype=f32),
+            torch.empty(n, device=dev, dtype=i64), trace, torch.empty(n * S, device=dev, dtype=f32), torch.empty((n * S, K), device=dev, dtype=f32),
+            torch.empty((n * S, K), device=dev, dtype=i32), torch.empty((n, H), device=dev, dtype=i64))
+
+
 def ctc_beam(logits, input_lengths, beam_width, blank=0, return_trace=False):
     """CTC prefix beam search of (N*S, C) logits, all on the device: (labels (N, W, S) int64 padded with -1, lengths (N, W) int64,
     scores (N, W) f32 best first, count (N) int64).  return_trace: also the dict of include/pero_hip.h's trace (node_parent, node_label,
     node_count, beam_node, beam_score)."""
     n, S, C = _ctc_rows_args("ctc_beam", logits, input_lengths)
-    rows, W, dev = n * S, int(beam_width), logits.device
+    W = int(beam_width)
     if W < 1 or C < 2:
         raise ValueError("ctc_beam: beam_width >= 1 and C >= 2")
     K, H = ctc_beam_workspace(S, C, W)
-    i32, i64, f32 = torch.int32, torch.int64, torch.float32
-    out = torch.empty((n, W, S), device=dev, dtype=i64)
-    out_lengths, out_scores = torch.empty((n, W), device=dev, dtype=i64), torch.empty((n, W), device=dev, dtype=f32)
-    out_count = torch.empty(n, device=dev, dtype=i64)
-    trace = {"node_parent": torch.empty((n, S * W + 1), device=dev, dtype=i32), "node_label": torch.empty((n, S * W + 1), device=dev, dtype=i32),
-             "node_count": torch.empty(n, device=dev, dtype=i32), "beam_node": torch.empty((n, S, W), device=dev, dtype=i32),
-             "beam_score": torch.empty((n, S, W, 2), device=dev, dtype=f32)}
-    row_lse = torch.empty(rows, device=dev, dtype=f32)
-    top_logp, top_class = torch.empty((rows, K), device=dev, dtype=f32), torch.empty((rows, K), device=dev, dtype=i32)
-    table = torch.empty((n, H), device=dev, dtype=i64)
+    out, out_lengths, out_scores, out_count, trace, row_lse, top_logp, top_class, table = _ctc_beam_buffers(n, S, W, K, H, logits.device)
     call("pero_ctc_beam", ptr(logits), ptr(input_lengths), ptr(out), ptr(out_lengths), ptr(out_scores), ptr(out_count), ptr(trace["node_parent"]),
          ptr(trace["node_label"]), ptr(trace["node_count"]), ptr(trace["beam_node"]), ptr(trace["beam_score"]), ptr(row_lse), ptr(top_logp),
          ptr(top_class), ptr(table), n, S, C, blank, W, dt(logits), stream())
     return (out, out_lengths, out_scores, out_count, trace) if return_trace else (out, out_lengths, out_scores, out_count)
+
+
+CTC_BEAM_MAX_CANDIDATES = 1088   # pero_ctc_beam_lm: W (K + 1) of one frame (include/pero_hip.h)
+
+
+def ctc_beam_lm(logits, input_lengths, beam_width, lm, lm_weight=1.0, length_bonus=0.0, class_top=None, use_final=True, blank=0,
+                return_trace=False):
+    """ctc_beam with shallow fusion of an n-gram model (pero_ctc_beam_lm; lm: a recognition.NGramLM): (labels, lengths, scores, count,
+    lm_scores (N, W) f32), the scores holding lm_weight * LM(string) + length_bonus * |string| (and, with use_final, the model's end term),
+    lm_scores that part alone.  class_top: the K best classes of a frame that may start a new string, None = min(C - 1, 1088 // W - 1).
+    return_trace: also the trace dict, with node_lm_state and node_lm_weight."""
+    n, S, C = _ctc_rows_args("ctc_beam_lm", logits, input_lengths)
+    W, dev = int(beam_width), logits.device
+    if W < 1 or C < 2:
+        raise ValueError("ctc_beam_lm: beam_width >= 1 and C >= 2")
+    if lm.num_classes != C or lm.blank != blank:
+        raise ValueError(f"ctc_beam_lm: the model is over {lm.num_classes} classes with blank {lm.blank}, the call has C = {C}, blank = {blank}")
+    if class_top is None:
+        K = max(min(C - 1, CTC_BEAM_MAX_CANDIDATES // W - 1), 1)
+    else:
+        K = min(max(int(class_top), 1), C - 1)
+        if W * (K + 1) > CTC_BEAM_MAX_CANDIDATES:
+            raise ValueError(f"ctc_beam_lm: beam_width * (class_top + 1) = {W} * {K + 1} exceeds the limit of {CTC_BEAM_MAX_CANDIDATES} "
+                             f"candidates per frame (class_top <= {CTC_BEAM_MAX_CANDIDATES // W - 1} at this beam_width)")
+    _, H = ctc_beam_workspace(S, C, W)
+    t = lm.to(dev)
+    out, out_lengths, out_scores, out_count, trace, row_lse, top_logp, top_class, table = _ctc_beam_buffers(n, S, W, K, H, dev)
+    out_lm = torch.empty((n, W), device=dev, dtype=torch.float32)
+    trace["node_lm_state"] = torch.empty((n, S * W + 1), device=dev, dtype=torch.int32)
+    trace["node_lm_weight"] = torch.empty((n, S * W + 1), device=dev, dtype=torch.float32)
+    call("pero_ctc_beam_lm", ptr(logits), ptr(input_lengths), ptr(t["backoff_state"]), ptr(t["backoff_weight"]), ptr(t["final"]), ptr(t["arc_begin"]),
+         ptr(t["arc_label"]), ptr(t["arc_logp"]), ptr(t["arc_next"]), ptr(out), ptr(out_lengths), ptr(out_scores), ptr(out_lm), ptr(out_count),
+         ptr(trace["node_parent"]), ptr(trace["node_label"]), ptr(trace["node_lm_state"]), ptr(trace["node_lm_weight"]), ptr(trace["node_count"]),
+         ptr(trace["beam_node"]), ptr(trace["beam_score"]), ptr(row_lse), ptr(top_logp), ptr(top_class), ptr(table), n, S, C, blank, W, K,
+         lm.num_states, lm.num_arcs, lm.start, float(lm_weight), float(length_bonus), int(bool(use_final)), dt(logits), stream())
+    return (out, out_lengths, out_scores, out_count, out_lm, trace) if return_trace else (out, out_lengths, out_scores, out_count, out_lm)
 
 
 CTC_ALIGN_LDS_BACK_BYTES = 96 * 1024   # PERO_CTC_ALIGN_LDS_BACK_BYTES of include/pero_hip.h

@@ -89,12 +89,15 @@ class TransformerRecognizer(torch.nn.Module):
             loss = self.loss(output, targets, input_lengths, target_lengths)
         return {"output": output, "loss": loss}
 
-    def decode(self, images, input_lengths=None, key_ranges=None, beam_width=None, nbest=1):
-        """Greedy labels (N, S) int64 padded with -1 and their lengths (N), on the device.  With beam_width: beam_decode's three results."""
+    def decode(self, images, input_lengths=None, key_ranges=None, beam_width=None, nbest=1, lm=None, lm_weight=1.0, length_bonus=0.0,
+               class_top=None, return_lm_scores=False):
+        """Greedy labels (N, S) int64 padded with -1 and their lengths (N), on the device.  With beam_width: beam_decode's results (lm and the
+        keywords behind it: beam_decode's)."""
         with torch.no_grad():
             output = self.encode(images, **ops.key_ranges_kw(self._ranges(input_lengths, key_ranges)))
         if beam_width is not None:
-            return beam_decode(output, input_lengths, getattr(self.loss, "blank", 0), beam_width, nbest)
+            return beam_decode(output, input_lengths, getattr(self.loss, "blank", 0), beam_width, nbest, lm=lm, lm_weight=lm_weight,
+                               length_bonus=length_bonus, class_top=class_top, return_lm_scores=return_lm_scores)
         return greedy_decode(output, input_lengths, getattr(self.loss, "blank", 0))
 
     def align(self, images, targets, target_lengths, input_lengths=None, key_ranges=None):
@@ -103,14 +106,15 @@ class TransformerRecognizer(torch.nn.Module):
             output = self.encode(images, **ops.key_ranges_kw(self._ranges(input_lengths, key_ranges)))
         return forced_align(output, targets, target_lengths, input_lengths, getattr(self.loss, "blank", 0))
 
-    def transcribe(self, images, input_lengths=None, key_ranges=None, beam_width=None):
-        """Decode (greedy, or with beam_width the best beam hypothesis) and align the decoded strings to the same logits, in one
-        encoder pass: (labels (N, S) int64 padded with -1, lengths (N), Alignment), all on the device."""
+    def transcribe(self, images, input_lengths=None, key_ranges=None, beam_width=None, lm=None, lm_weight=1.0, length_bonus=0.0, class_top=None):
+        """Decode (greedy, or with beam_width the best beam hypothesis, with lm under that language model) and align the decoded strings to the
+        same logits, in one encoder pass: (labels (N, S) int64 padded with -1, lengths (N), Alignment), all on the device."""
         blank = getattr(self.loss, "blank", 0)
         with torch.no_grad():
             output = self.encode(images, **ops.key_ranges_kw(self._ranges(input_lengths, key_ranges)))
             if beam_width is not None:
-                labels, lengths, _ = beam_decode(output, input_lengths, blank, beam_width)
+                labels, lengths, _ = beam_decode(output, input_lengths, blank, beam_width, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
+                                                 class_top=class_top)
                 labels, lengths = labels.contiguous(), lengths.contiguous()
             else:
                 labels, lengths = greedy_decode(output, input_lengths, blank)
@@ -147,16 +151,31 @@ def greedy_decode(output, input_lengths=None, blank=0):
     return ops.ctc_greedy(*_decoder_args(output, input_lengths), blank)
 
 
-def beam_decode(output, input_lengths=None, blank=0, beam_width=16, nbest=1):
+def beam_decode(output, input_lengths=None, blank=0, beam_width=16, nbest=1, lm=None, lm_weight=1.0, length_bonus=0.0, class_top=None,
+                return_lm_scores=False):
     """CTC prefix beam search of (N, S, C) logits on the device: the nbest <= beam_width best label strings of every line,
     (labels (N, nbest, S) int64 padded with -1, lengths (N, nbest) int64, scores (N, nbest) f32 log-probabilities, best first); a line with
-    fewer hypotheses has length 0 and score -inf in the rest.  nbest = 1 drops the hypothesis axis: (N, S), (N), (N)."""
+    fewer hypotheses has length 0 and score -inf in the rest.  nbest = 1 drops the hypothesis axis: (N, S), (N), (N).
+    lm (an NGramLM over the same classes and blank): shallow fusion, scores = log-probability + lm_weight * LM(string) + length_bonus * |string|
+    with the model's end term (ops.ctc_beam_lm; class_top: the classes of a frame that may start a new string).  return_lm_scores: a fourth
+    result, the language-model part of every score (needs lm)."""
     if not 1 <= nbest <= beam_width:
         raise ValueError(f"beam_decode: nbest {nbest} outside [1, beam_width = {beam_width}]")
-    labels, lengths, scores, _ = ops.ctc_beam(*_decoder_args(output, input_lengths), beam_width, blank)
+    if lm is None:
+        if return_lm_scores:
+            raise ValueError("beam_decode: return_lm_scores needs lm")
+        labels, lengths, scores, _ = ops.ctc_beam(*_decoder_args(output, input_lengths), beam_width, blank)
+        results = (labels, lengths, scores)
+    else:
+        if lm.blank != blank or lm.num_classes != output.shape[-1]:
+            raise ValueError(f"beam_decode: the language model is over {lm.num_classes} classes with blank {lm.blank}, the logits have "
+                             f"{output.shape[-1]} classes and the call blank {blank}")
+        labels, lengths, scores, _, lm_scores = ops.ctc_beam_lm(*_decoder_args(output, input_lengths), beam_width, lm, lm_weight, length_bonus,
+                                                                class_top, True, blank)
+        results = (labels, lengths, scores, lm_scores) if return_lm_scores else (labels, lengths, scores)
     if nbest == 1:
-        return labels[:, 0], lengths[:, 0], scores[:, 0]
-    return labels[:, :nbest], lengths[:, :nbest], scores[:, :nbest]
+        return tuple(r[:, 0] for r in results)
+    return tuple(r[:, :nbest] for r in results)
 
 
 Alignment = collections.namedtuple("Alignment", ["states", "spans", "label_logp", "score", "path_logit", "confidences", "nll", "path_share"])

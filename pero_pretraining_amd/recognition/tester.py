@@ -1,5 +1,5 @@
 """Tester of a recogniser: average loss and character error rate.  Nothing leaves the device inside the loop: pero_ctc_greedy
-(or, with beam_width, pero_ctc_beam) decodes there, pero_edit_distance compares the decoded labels with the targets there and adds
+(or, with beam_width, pero_ctc_beam; with lm as well, pero_ctc_beam_lm) decodes there, pero_edit_distance compares the decoded labels with the targets there and adds
 into one pair of integer totals, which is read once behind the last batch."""
 import torch
 
@@ -21,13 +21,15 @@ def levenshtein(a, b):
 
 
 class Tester:
-    def __init__(self, batch_operator, model, dataloader, max_lines=None, bfloat16=False, beam_width=None):
+    def __init__(self, batch_operator, model, dataloader, max_lines=None, bfloat16=False, beam_width=None, lm=None, lm_weight=1.0, length_bonus=0.0,
+                 class_top=None):
         self.batch_operator = batch_operator
         self.model = model
         self.dataloader = dataloader
         self.max_lines = max_lines
         self.bfloat16 = bfloat16
         self.beam_width = beam_width   # None: greedy decoding
+        self.lm_kw = dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, class_top=class_top)   # beam_decode's; lm None: no language model
 
     def test(self):
         """{'loss': mean of the batch losses, 'cer': sum of edit distances / sum of target lengths}."""
@@ -43,7 +45,7 @@ class Tester:
                 if self.beam_width is None:
                     labels, lengths = greedy_decode(result["output"], input_lengths, blank)
                 else:
-                    labels, lengths, _ = beam_decode(result["output"], input_lengths, blank, self.beam_width)
+                    labels, lengths, _ = beam_decode(result["output"], input_lengths, blank, self.beam_width, **self.lm_kw)
                 if totals is None:
                     totals = torch.zeros(2, dtype=torch.int64, device=labels.device)   # sum of distances, sum of target lengths
                 ops.edit_distance(labels.contiguous(), lengths.contiguous(), targets.contiguous(), target_lengths.contiguous(), totals)
