@@ -629,6 +629,42 @@ int pero_ctc_beam_lm(const void* logits, const int64_t* input_lengths, const int
 int pero_edit_distance(const int64_t* a, const int64_t* a_len, const int64_t* b, const int64_t* b_len, int64_t* dist, int64_t* totals,
                        int64_t N, int64_t La, int64_t Lb, void* stream);
 
+/* ---- Edit operations (which symbols, or words, were wrong: the backtrace of pero_edit_distance's table; csrc/edit_ops.hip, DESIGN.md
+ * "Edit operations") ------------------------------------------------------------------------------------------------------
+ * pero_edit_ops: a is the hypothesis, b the reference.  a, a_len, b, b_len, their layout, padding, the clamp of the lengths and the null
+ * pointer for a zero-width matrix: as for pero_edit_distance.  With la, lb the clamped lengths of pair n and a_i, b_j its elements
+ * (1-based; the labels, or with is_sep the words):
+ *   Table.  D(i, j) = pero_edit_distance's table: D(i, 0) = i, D(0, j) = j,
+ *     D(i, j) = min(D(i-1, j) + 1, D(i, j-1) + 1, D(i-1, j-1) + [a_i != b_j]).
+ *   Script.  Walk from (la, lb) to (0, 0).  At (i, j):
+ *     1. if i > 0, j > 0 and D(i-1, j-1) + [a_i != b_j] == D(i, j): go to (i-1, j-1); a HIT (code 0) if a_i == b_j, else a SUBSTITUTION
+ *        (code 1);
+ *     2. otherwise, if j > 0 and D(i, j-1) + 1 == D(i, j): go to (i, j-1); a DELETION of b_j (code 3);
+ *     3. otherwise go to (i-1, j); an INSERTION of a_i (code 2).
+ *     This tie rule makes the script unique; it is a minimal script: substitutions + insertions + deletions = D(la, lb),
+ *     hits + substitutions + insertions = la, hits + substitutions + deletions = lb.
+ *   Outputs (caller-owned, every entry written):
+ *     counts (N, 4) int64: substitutions, insertions, deletions, hits of the pair.
+ *     script (N, La + Lb) int8 and script_len (N) int32, both null or both given (script may be null for La + Lb = 0: a zero-width
+ *       matrix): the codes in FORWARD order (the first element's operation first), script_len <= la + lb of them, -1 behind.
+ *   totals (6 int64 on the device, may be null; ACCUMULATED, the caller zeroes them once; integer atomics, exact in any order):
+ *     totals[0..3] += the pair's four counts; totals[4] += 1 per pair; totals[5] += 1 per pair with D(la, lb) > 0.
+ *   confusion ((C + 1, C + 1) int64 on the device, may be null; ACCUMULATED likewise; symbol level only): a hit or substitution of
+ *     reference label r by hypothesis label h: confusion[r][h] += 1; a deletion of r: confusion[r][C] += 1; an insertion of h:
+ *     confusion[C][h] += 1.  An operation that involves a label outside [0, C) is counted in counts and totals and skipped here: no
+ *     index is formed from it.
+ *   Word level (is_sep given: C bytes on the device, non-zero = class c separates words).  A word is a maximal run of labels c with
+ *     !(0 <= c < C && is_sep[c]): labels outside [0, C) belong to words; leading, trailing and repeated separators make no empty
+ *     words.  Two words are equal iff they have the same length and the same labels, decided by comparing the labels (a hash only
+ *     skips unequal words).  Table, script, counts and totals are over the two word sequences (script keeps its width La + Lb).
+ *     a_spans (N, (La + 1) / 2, 2), b_spans (N, (Lb + 1) / 2, 2) int32, each may be null: [begin, end) of every word in its row, -1
+ *     behind the last word.  confusion must be null (PERO_E_INVALID); without is_sep the spans must be null.
+ *   C is read only with confusion or is_sep and must then be >= 1.  Integer arithmetic only; nothing depends on timing: two calls give
+ *   the same bits.  Supported: La, Lb <= 512 (PERO_E_UNSUPPORTED above). */
+int pero_edit_ops(const int64_t* a, const int64_t* a_len, const int64_t* b, const int64_t* b_len, const uint8_t* is_sep, int64_t* counts,
+                  int8_t* script, int32_t* script_len, int32_t* a_spans, int32_t* b_spans, int64_t* totals, int64_t* confusion, int64_t N,
+                  int64_t La, int64_t Lb, int64_t C, void* stream);
+
 /* ---- CTC forced alignment (where each character of a known string sits, and how sure the model is of it; csrc/ctc_align.hip,
  * DESIGN.md "CTC forced alignment") ---------------------------------------------------------------------------------------
  * pero_ctc_align: the best state path (Viterbi) of every line's label string.  logits, targets, input_lengths, target_lengths,

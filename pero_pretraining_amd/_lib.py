@@ -103,6 +103,7 @@ SIGNATURES = {
     "pero_ctc_beam": [_vp] * 15 + [_i64, _i64, _i64, _i64, _i64, _i32, _vp],
     "pero_ctc_beam_lm": [_vp] * 25 + [_i64] * 9 + [_f32, _f32, _i32, _i32, _vp],
     "pero_edit_distance": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp],
+    "pero_edit_ops": [_vp] * 12 + [_i64, _i64, _i64, _i64, _vp],
     "pero_ctc_align": [_vp] * 11 + [_i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp],
 }
 # pero_gemm's arguments + int* k_split, int* extra_pass (each may be null); returns the kernel family (> 0: a key of GEMM_KERNELS), so not for call()

@@ -22,8 +22,6 @@
 #define BEAM_LM_MAX_K (BEAM_MAX_Q - 1)                                  // W = 1: the largest K with W (K + 1) <= BEAM_MAX_Q
 #define BEAM_LM_MAX_HOPS PERO_CTC_LM_MAX_ORDER                          // back-off steps of one look-up
 #define BEAM_QPT ((BEAM_MAX_Q + CTC_THREADS - 1) / CTC_THREADS)         // candidates of one thread
-#define EDIT_THREADS 256
-#define EDIT_MAX_L 512
 
 // A candidate's sort key: the larger key ranks first.  High word: the total's bits made monotone (a float order is an unsigned order after
 // flipping the sign bit of a non-negative value and every bit of a negative one; -0 counts as +0); low word: ~q, so that equal totals rank by

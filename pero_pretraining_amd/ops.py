@@ -1053,3 +1053,63 @@ def edit_distance(a, a_len, b, b_len, totals=None):
     dist = torch.empty(n, device=a.device, dtype=torch.int64)
     call("pero_edit_distance", ptr(a), ptr(a_len), ptr(b), ptr(b_len), ptr(dist), ptr(totals), n, a.shape[1], b.shape[1], stream())
     return dist
+
+
+def edit_separator_table(separators, num_classes, device):
+    """The is_sep byte table of pero_edit_ops on `device`: (num_classes) uint8, 1 at every class id of `separators` (ids outside
+    [0, num_classes) name no class and are dropped)."""
+    table = torch.zeros(num_classes, dtype=torch.uint8)
+    ids = sorted({int(c) for c in separators if 0 <= int(c) < num_classes})
+    if ids:
+        table[torch.tensor(ids)] = 1
+    return table.to(device)
+
+
+def edit_ops(a, a_len, b, b_len, num_classes=None, separators=None, totals=None, confusion=None, want_script=True, want_spans=False):
+    """Edit operations (pero_edit_ops) of hypotheses a (N, La) against references b (N, Lb), padded int64 label matrices with lengths (N), all
+    on the device.  Returns (counts (N, 4) int64: substitutions, insertions, deletions, hits; script (N, La + Lb) int8 and script_len (N)
+    int32, or None, None without want_script; a_spans (N, (La + 1) / 2, 2), b_spans (N, (Lb + 1) / 2, 2) int32 with want_spans, else None,
+    None) as include/pero_hip.h defines them.
+    separators: an iterable of class ids (or a ready table of edit_separator_table) -> word level; needs num_classes.
+    totals (6 int64 on the device) and confusion ((C + 1, C + 1) int64 on the device, symbol level only; C = num_classes, or taken from its
+    shape) are ACCUMULATED, exact (integer atomics)."""
+    _req_cuda(a, a_len, b, b_len, totals, confusion)
+    n = a_len.numel()
+    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != n or b.shape[0] != n or b_len.numel() != n or n == 0:
+        raise ValueError("edit_ops: a (N, La), b (N, Lb), a_len and b_len (N)")
+    for t in (a, a_len, b, b_len) + tuple(t for t in (totals, confusion) if t is not None):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise ValueError("edit_ops: labels, lengths, totals and confusion must be contiguous int64 device tensors")
+    if totals is not None and totals.numel() != 6:
+        raise ValueError("edit_ops: totals holds six int64")
+    if confusion is not None:
+        if separators is not None:
+            raise ValueError("edit_ops: the confusion matrix is symbol level only")
+        if confusion.dim() != 2 or confusion.shape[0] != confusion.shape[1] or confusion.shape[0] < 2:
+            raise ValueError("edit_ops: confusion is (C + 1, C + 1)")
+        if num_classes is None:
+            num_classes = confusion.shape[0] - 1
+        if confusion.shape[0] != num_classes + 1:
+            raise ValueError(f"edit_ops: confusion is {tuple(confusion.shape)}, expected ({num_classes + 1}, {num_classes + 1})")
+    if want_spans and separators is None:
+        raise ValueError("edit_ops: spans are word level only (give separators)")
+    is_sep = None
+    if separators is not None:
+        if num_classes is None or num_classes < 1:
+            raise ValueError("edit_ops: separators need num_classes >= 1")
+        if isinstance(separators, torch.Tensor) and separators.dtype == torch.uint8:
+            is_sep = separators
+            _req_cuda(is_sep)
+            if is_sep.numel() != num_classes or not is_sep.is_contiguous():
+                raise ValueError("edit_ops: a separator table is (num_classes) contiguous uint8")
+        else:
+            is_sep = edit_separator_table(separators, num_classes, a.device)
+    La, Lb, dev = a.shape[1], b.shape[1], a.device
+    counts = torch.empty((n, 4), device=dev, dtype=torch.int64)
+    script = torch.empty((n, La + Lb), device=dev, dtype=torch.int8) if want_script else None
+    script_len = torch.empty(n, device=dev, dtype=torch.int32) if want_script else None
+    a_spans = torch.empty((n, (La + 1) // 2, 2), device=dev, dtype=torch.int32) if want_spans else None
+    b_spans = torch.empty((n, (Lb + 1) // 2, 2), device=dev, dtype=torch.int32) if want_spans else None
+    call("pero_edit_ops", ptr(a), ptr(a_len), ptr(b), ptr(b_len), ptr(is_sep), ptr(counts), ptr(script), ptr(script_len), ptr(a_spans), ptr(b_spans),
+         ptr(totals), ptr(confusion), n, La, Lb, num_classes or 0, stream())
+    return counts, script, script_len, a_spans, b_spans

@@ -1,6 +1,8 @@
 """Tester of a recogniser: average loss and character error rate.  Nothing leaves the device inside the loop: pero_ctc_greedy
 (or, with beam_width, pero_ctc_beam; with lm as well, pero_ctc_beam_lm) decodes there, pero_edit_distance compares the decoded labels with the targets there and adds
-into one pair of integer totals, which is read once behind the last batch."""
+into one pair of integer totals, which is read once behind the last batch.  With word_separators or details, pero_edit_ops takes its place: the
+same table with its backtrace, so the totals also hold substitutions, insertions, deletions and hits, over characters and over words, and a
+confusion matrix grows on the device; all of it is still read once."""
 import torch
 
 from .. import ops
@@ -22,7 +24,7 @@ def levenshtein(a, b):
 
 class Tester:
     def __init__(self, batch_operator, model, dataloader, max_lines=None, bfloat16=False, beam_width=None, lm=None, lm_weight=1.0, length_bonus=0.0,
-                 class_top=None):
+                 class_top=None, word_separators=None, details=False):
         self.batch_operator = batch_operator
         self.model = model
         self.dataloader = dataloader
@@ -30,9 +32,16 @@ class Tester:
         self.bfloat16 = bfloat16
         self.beam_width = beam_width   # None: greedy decoding
         self.lm_kw = dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, class_top=class_top)   # beam_decode's; lm None: no language model
+        self.word_separators = None if word_separators is None else tuple(word_separators)   # class ids that separate words: adds 'wer'
+        self.details = details   # adds the operation counts, the line error rate and the confusion matrix
 
     def test(self):
-        """{'loss': mean of the batch losses, 'cer': sum of edit distances / sum of target lengths}."""
+        """{'loss': mean of the batch losses, 'cer': sum of edit distances / sum of target lengths}.
+        word_separators adds 'wer', the same ratio over words.  details adds 'substitutions', 'insertions', 'deletions', 'hits', 'lines',
+        'line_error_rate' (lines with any error / lines), 'confusion' ((C + 1, C + 1) int64 on the host, C = the logits' classes:
+        [reference][hypothesis], index C = the gap; see top_confusions) and, with word_separators, the counts again as 'word_...'."""
+        if self.word_separators is not None or self.details:
+            return self._test_with_operations()
         total_loss, num_lines, num_batches, totals = 0, 0, 0, None
         self.model.eval()
         with torch.no_grad():
@@ -56,3 +65,45 @@ class Tester:
         self.model.train()
         distance, characters = totals.tolist()   # the run's one read of the counts
         return {"loss": float(total_loss) / num_batches, "cer": distance / max(characters, 1)}
+
+    def _test_with_operations(self):
+        """test() over pero_edit_ops.  totals: six int64 per level (pero_edit_ops' totals), row 0 characters, row 1 words."""
+        total_loss, num_lines, num_batches, totals, confusion, is_sep = 0, 0, 0, None, None, None
+        self.model.eval()
+        with torch.no_grad():
+            for batch in self.dataloader:
+                images, targets, target_lengths, input_lengths = self.batch_operator.prepare_batch(batch)
+                with autocast(self.bfloat16):
+                    result = self.model(images, targets, target_lengths, input_lengths)
+                total_loss = total_loss + result["loss"]
+                blank = getattr(self.model.loss, "blank", 0)
+                if self.beam_width is None:
+                    labels, lengths = greedy_decode(result["output"], input_lengths, blank)
+                else:
+                    labels, lengths, _ = beam_decode(result["output"], input_lengths, blank, self.beam_width, **self.lm_kw)
+                if totals is None:
+                    C = result["output"].shape[-1]
+                    totals = torch.zeros((2, 6), dtype=torch.int64, device=labels.device)
+                    if self.details:
+                        confusion = torch.zeros((C + 1, C + 1), dtype=torch.int64, device=labels.device)
+                    if self.word_separators is not None:
+                        is_sep = ops.edit_separator_table(self.word_separators, C, labels.device)   # built once
+                pair = (labels.contiguous(), lengths.contiguous(), targets.contiguous(), target_lengths.contiguous())
+                ops.edit_ops(*pair, num_classes=C, totals=totals[0], confusion=confusion, want_script=False)
+                if is_sep is not None:
+                    ops.edit_ops(*pair, num_classes=C, separators=is_sep, totals=totals[1], want_script=False)
+                num_lines += self.batch_operator.batch_size(batch)
+                num_batches += 1
+                if self.max_lines is not None and num_lines > self.max_lines:
+                    break
+        self.model.train()
+        (sub, ins, dele, hit, lines, wrong), word = totals.tolist()   # the run's one read of the counts
+        out = {"loss": float(total_loss) / num_batches, "cer": (sub + ins + dele) / max(hit + sub + dele, 1)}
+        if self.word_separators is not None:
+            out["wer"] = (word[0] + word[1] + word[2]) / max(word[3] + word[0] + word[2], 1)
+        if self.details:
+            out.update(substitutions=sub, insertions=ins, deletions=dele, hits=hit, lines=lines, line_error_rate=wrong / max(lines, 1),
+                       confusion=confusion.cpu())
+            if self.word_separators is not None:
+                out.update(word_substitutions=word[0], word_insertions=word[1], word_deletions=word[2], word_hits=word[3])
+        return out
