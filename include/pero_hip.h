@@ -549,7 +549,7 @@ int pero_ctc_bwd(const void* logits, const int64_t* targets, const int64_t* inpu
 int pero_ctc_greedy(const void* logits, const int64_t* input_lengths, int64_t* out, int64_t* out_lengths, int64_t N, int64_t S, int64_t C,
                     int64_t blank, int dtype, void* stream);
 
-/* ---- CTC decoding and scoring (evaluation of a recogniser; csrc/ctc_decode.hip, DESIGN.md "CTC decoding") --------------
+/* ---- CTC decoding and scoring (evaluation of a recogniser; csrc/ctc_decode.hip, pero_edit_distance: csrc/edit.hip; DESIGN.md "CTC decoding")
  * pero_ctc_beam: CTC prefix beam search of width W, one line per workgroup, no class pruning, no language model.  logits,
  * input_lengths, blank, dtype and the clamp of the lengths as for pero_ctc_greedy; all arithmetic f32 in the log domain,
  * logp_t(c) = x[n][t][c] - row_lse[n S + t] (a -inf logit has logp -inf), (+) = log-sum-exp (all -inf -> -inf, never NaN).
@@ -629,7 +629,7 @@ int pero_ctc_beam_lm(const void* logits, const int64_t* input_lengths, const int
 int pero_edit_distance(const int64_t* a, const int64_t* a_len, const int64_t* b, const int64_t* b_len, int64_t* dist, int64_t* totals,
                        int64_t N, int64_t La, int64_t Lb, void* stream);
 
-/* ---- Edit operations (which symbols, or words, were wrong: the backtrace of pero_edit_distance's table; csrc/edit_ops.hip, DESIGN.md
+/* ---- Edit operations (which symbols, or words, were wrong: the backtrace of pero_edit_distance's table; csrc/edit.hip, DESIGN.md
  * "Edit operations") ------------------------------------------------------------------------------------------------------
  * pero_edit_ops: a is the hypothesis, b the reference.  a, a_len, b, b_len, their layout, padding, the clamp of the lengths and the null
  * pointer for a zero-width matrix: as for pero_edit_distance.  With la, lb the clamped lengths of pair n and a_i, b_j its elements

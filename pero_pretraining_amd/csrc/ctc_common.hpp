@@ -10,8 +10,6 @@
 #define CTC_MAX_C 8192
 #define CTC_MAXK 5   // ceil((2 * CTC_MAX_S + 1) / CTC_THREADS): extended states of one thread
 #define CTC_NEG_INF (-__builtin_huge_valf())
-#define EDIT_THREADS 256   // edit_distance_k (ctc_decode.hip) and edit_ops_k (edit_ops.hip): one workgroup per pair
-#define EDIT_MAX_L 512
 
 static __device__ __forceinline__ int ctc_clamp_len(int64_t v, int hi) { return v < 0 ? 0 : (v > hi ? hi : (int)v); }
 

@@ -1,4 +1,4 @@
-// Evaluation of a recogniser on the device: CTC prefix beam search and batched edit distance.  Contract: include/pero_hip.h; derivation,
+// Decoding of a recogniser's output on the device: CTC prefix beam search, with or without an n-gram language model.  Contract: include/pero_hip.h; derivation,
 // trie and tie rule: DESIGN.md "CTC decoding".
 //
 //   pero_ctc_beam      ctc_beam_top_k  one wave per logit row t < T: row_lse (ctc_wave_row_lse, the function of ctc_row_lse_k) and the
@@ -8,7 +8,6 @@
 //                                      threads, ranked by counting, the kept ones find or create their prefix node; five barriers per frame
 //   pero_ctc_beam_lm   the same two kernels; ctc_beam_k<T, true> adds the n-gram term of every new string (one walk of the LM automaton per
 //                                      extension candidate, issued ahead of the frame's first barrier) and takes K from the caller
-//   pero_edit_distance edit_distance_k one workgroup per pair: the anti-diagonals of the unit-cost table out of LDS, one barrier each
 //
 // Why K = W + 1 classes are enough: the extensions of one beam entry j score logp(c) + tot_j, except c = last_j, which scores logp(c) + pb_j
 // <= logp(c) + tot_j.  A class outside the row's best W + 1 is beaten, for the same j, by at least W extensions (or by the stay candidates
@@ -400,42 +399,6 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
   }
 }
 
-// Table entry (i, j) = distance of a[0, i) and b[0, j).  Anti-diagonal d = i + j, indexed by i, three of them in rotation.
-__global__ __launch_bounds__(EDIT_THREADS) void edit_distance_k(const int64_t* __restrict__ a, const int64_t* __restrict__ bq,
-                                                                const int64_t* __restrict__ a_len, const int64_t* __restrict__ b_len,
-                                                                int64_t* __restrict__ dist, unsigned long long* __restrict__ totals, int La, int Lb) {
-  __shared__ int64_t sa[EDIT_MAX_L], sb[EDIT_MAX_L];
-  __shared__ int diag[3][EDIT_MAX_L + 1];
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const int la = ctc_clamp_len(a_len[n], La), lb = ctc_clamp_len(b_len[n], Lb);
-  for (int i = tid; i < la; i += EDIT_THREADS) sa[i] = a[(long long)n * La + i];
-  for (int j = tid; j < lb; j += EDIT_THREADS) sb[j] = bq[(long long)n * Lb + j];
-  __syncthreads();
-  for (int d = 0; d <= la + lb; d++) {
-    int* cur = diag[d % 3];
-    const int* p1 = diag[(d + 2) % 3];   // diagonal d - 1: (i - 1, j) at i - 1, (i, j - 1) at i
-    const int* p2 = diag[(d + 1) % 3];   // diagonal d - 2: (i - 1, j - 1) at i - 1
-    const int lo = d > lb ? d - lb : 0, hi = d < la ? d : la;
-    for (int i = lo + tid; i <= hi; i += EDIT_THREADS) {
-      const int j = d - i;
-      int v;
-      if (i == 0) v = j;
-      else if (j == 0) v = i;
-      else v = min(min(p1[i - 1], p1[i]) + 1, p2[i - 1] + (sa[i - 1] != sb[j - 1] ? 1 : 0));
-      cur[i] = v;
-    }
-    __syncthreads();   // diagonal d is complete; its readers of d - 2 are done before d + 1 overwrites that buffer
-  }
-  if (tid == 0) {
-    const int v = diag[(la + lb) % 3][la];
-    dist[n] = v;
-    if (totals) {
-      atomicAdd(totals, (unsigned long long)v);
-      atomicAdd(totals + 1, (unsigned long long)lb);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------- host side
 #define BEAM_LAUNCH_TOP(T, ...)                                                                                                          \
   hipLaunchKernelGGL((ctc_beam_top_k<T>), dim3((unsigned)((rows + 3) / 4)), dim3(CTC_THREADS), 0, st, (const T*)logits, input_lengths, row_lse, \
@@ -500,19 +463,4 @@ extern "C" int pero_ctc_beam_lm(const void* logits, const int64_t* input_lengths
                      node_lm_weight, (int)M, (int)A, (int)start, use_final != 0, lm_weight, length_bonus};
   return beam_run("pero_ctc_beam_lm", logits, input_lengths, out, out_lengths, out_scores, out_count, node_parent, node_label, node_count, beam_node,
                   beam_score, row_lse, top_logp, top_class, hash, N, S, C, blank, W, K, true, lm, dtype, stream);
-}
-
-extern "C" int pero_edit_distance(const int64_t* a, const int64_t* a_len, const int64_t* b, const int64_t* b_len, int64_t* dist, int64_t* totals,
-                                  int64_t N, int64_t La, int64_t Lb, void* stream) {
-  PERO_REQUIRE(N > 0 && N < (1LL << 31) && La >= 0 && Lb >= 0, "pero_edit_distance: bad sizes (N %lld, La %lld, Lb %lld)", (long long)N, (long long)La,
-               (long long)Lb);
-  if (La > EDIT_MAX_L || Lb > EDIT_MAX_L) {
-    pero_set_error("pero_edit_distance: supported up to La, Lb = %d (got La %lld, Lb %lld)", EDIT_MAX_L, (long long)La, (long long)Lb);
-    return PERO_E_UNSUPPORTED;
-  }
-  PERO_REQUIRE((a || La == 0) && (b || Lb == 0) && a_len && b_len && dist, "pero_edit_distance: null pointer");
-  hipLaunchKernelGGL(edit_distance_k, dim3((unsigned)N), dim3(EDIT_THREADS), 0, (hipStream_t)stream, a, b, a_len, b_len, dist,
-                     (unsigned long long*)totals, (int)La, (int)Lb);
-  PERO_CHECK_LAUNCH("pero_edit_distance");
-  return PERO_OK;
 }

@@ -1,22 +1,81 @@
-// Edit operations on the device: the Levenshtein table of pero_edit_distance WITH its backtrace - the script of hits, substitutions,
-// insertions and deletions of every pair, their counts, a confusion matrix, and the same over words.  Contract: include/pero_hip.h;
-// kernel shape, LDS budget and measurements: DESIGN.md section 16.
+// Edit distance and edit operations on the device: the Levenshtein table of every pair of a batch, and - for pero_edit_ops - its backtrace:
+// the script of hits, substitutions, insertions and deletions, their counts, a confusion matrix, and the same over words.  Contract:
+// include/pero_hip.h; kernel shapes, LDS budgets and measurements: DESIGN.md sections 12 and 16.
 //
-//   pero_edit_ops   edit_ops_k<WORDS>  one workgroup per pair.  The table by anti-diagonals out of LDS, as edit_distance_k (three of them in
-//                                      rotation, one barrier each); every cell's 2-bit operation is written as the cell is computed, packed
-//                                      16 to a word, row-wise by i, in LDS - the directions never reach HBM.  One lane walks back from
-//                                      (la, lb) and leaves the reversed script in LDS; all threads copy it out forwards and add the
-//                                      confusion counts.  WORDS: the rows are split at the separators first (two ballots per row), every
-//                                      word gets the slot of the first word with the same content (a hash finds candidates, the labels
-//                                      decide), and the table runs over those slots.
+//   both kernels       edit_sweep<DIRS>   the table by anti-diagonals out of LDS, three of them in rotation, one barrier each
+//   pero_edit_distance edit_distance_k    one workgroup per pair, static LDS at the limits: the sweep, and the corner of the table
+//   pero_edit_ops      edit_ops_k<WORDS>  one workgroup per pair.  The sweep with DIRS: every cell's 2-bit operation is written as the cell
+//                                         is computed, packed 16 to a word, row-wise by i, in LDS - the directions never reach HBM.  One lane
+//                                         walks back from (la, lb) and leaves the reversed script in LDS; all threads copy it out forwards
+//                                         and add the confusion counts.  WORDS: the rows are split at the separators first (two ballots per
+//                                         row), every word gets the slot of the first word with the same content (a hash finds candidates,
+//                                         the labels decide), and the table runs over those slots.
 //
-// The dynamic LDS is sized from the call's La, Lb (edit_lds): about 4 KB at 70 labels, 86 KB at 512 x 512, so short lines keep many
-// workgroups on a CU.  A cell's operation IS the script code (0 hit, 1 substitution, 2 insertion, 3 deletion); every code moves i or j
+// The dynamic LDS of edit_ops_k is sized from the call's La, Lb (edit_lds): about 4 KB at 70 labels, 86 KB at 512 x 512, so short lines keep
+// many workgroups on a CU.  A cell's operation IS the script code (0 hit, 1 substitution, 2 insertion, 3 deletion); every code moves i or j
 // towards 0 and the walk is a loop over at most la + lb steps, so it ends and stays inside its arrays whatever the LDS holds.
 #include "ctc_common.hpp"
 
+#define EDIT_THREADS 256   // one workgroup per pair
+#define EDIT_MAX_L 512
+
 static_assert(EDIT_MAX_L <= 2 * EDIT_THREADS, "edit_split: two positions per thread");
 static_assert(EDIT_MAX_L < (1 << 10), "a step packs i and j into 10 bits each");
+
+// Table entry (i, j) = distance of a[0, i) and b[0, j); anti-diagonal d = i + j, indexed by i.  All EDIT_THREADS threads call it, after a
+// barrier behind the writes of ea and eb.  diag: three diagonals of W >= la + 1 ints in rotation; on return (behind a barrier) the distance is
+// diag[((la + lb) % 3) * W + la].  DIRS: cell (i, j), i, j >= 1, leaves its operation in dir (layout: edit_lds), tie rule of the header:
+// diagonal, then deletion, then insertion.
+template <bool DIRS>
+static __device__ __forceinline__ void edit_sweep(const int64_t* ea, const int64_t* eb, int la, int lb, int* diag, int W, unsigned* dir, int stride) {
+  const int tid = threadIdx.x;
+  for (int d = 0; d <= la + lb; d++) {
+    int* cur = diag + (d % 3) * W;
+    const int* p1 = diag + ((d + 2) % 3) * W;   // diagonal d - 1: (i - 1, j) at i - 1, (i, j - 1) at i
+    const int* p2 = diag + ((d + 1) % 3) * W;   // diagonal d - 2: (i - 1, j - 1) at i - 1
+    const int lo = d > lb ? d - lb : 0, hi = d < la ? d : la;
+    for (int i = lo + tid; i <= hi; i += EDIT_THREADS) {
+      int v;
+      if (i == 0 || i == d) v = d;   // the boundary cells (0, j) and (i, 0): the other index
+      else {
+        const int j = d - i;
+        const int ne = ea[i - 1] != eb[j - 1] ? 1 : 0;
+        const int dg = p2[i - 1] + ne, left = p1[i] + 1, up = p1[i - 1] + 1;
+        v = min(min(up, left), dg);
+        if (DIRS) {
+          const unsigned code = dg == v ? (unsigned)ne : (left == v ? 3u : 2u);
+          // a row has one cell per diagonal, so this word has one writer now; its first cell starts the word, the barrier orders the others
+          unsigned* word = dir + (i - 1) * stride + ((j - 1) >> 4);
+          const int sh = ((j - 1) & 15) * 2;
+          *word = sh == 0 ? code : (*word | (code << sh));
+        }
+      }
+      cur[i] = v;
+    }
+    __syncthreads();   // diagonal d is complete; its readers of d - 2 are done before d + 1 overwrites that buffer
+  }
+}
+
+__global__ __launch_bounds__(EDIT_THREADS) void edit_distance_k(const int64_t* __restrict__ a, const int64_t* __restrict__ bq,
+                                                                const int64_t* __restrict__ a_len, const int64_t* __restrict__ b_len,
+                                                                int64_t* __restrict__ dist, unsigned long long* __restrict__ totals, int La, int Lb) {
+  __shared__ int64_t sa[EDIT_MAX_L], sb[EDIT_MAX_L];
+  __shared__ int diag[3][EDIT_MAX_L + 1];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const int la = ctc_clamp_len(a_len[n], La), lb = ctc_clamp_len(b_len[n], Lb);
+  for (int i = tid; i < la; i += EDIT_THREADS) sa[i] = a[(long long)n * La + i];
+  for (int j = tid; j < lb; j += EDIT_THREADS) sb[j] = bq[(long long)n * Lb + j];
+  __syncthreads();
+  edit_sweep<false>(sa, sb, la, lb, &diag[0][0], EDIT_MAX_L + 1, nullptr, 0);
+  if (tid == 0) {
+    const int v = diag[(la + lb) % 3][la];
+    dist[n] = v;
+    if (totals) {
+      atomicAdd(totals, (unsigned long long)v);
+      atomicAdd(totals + 1, (unsigned long long)lb);
+    }
+  }
+}
 
 // Byte offsets into the dynamic LDS, the same function on both sides of the launch.  rows, cols: the widest table of the call (labels, or
 // words: a row of L labels holds at most (L + 1) / 2 words).  stride: words of one row of directions, odd, so that the cells of a diagonal
@@ -165,32 +224,7 @@ __global__ __launch_bounds__(EDIT_THREADS) void edit_ops_k(const int64_t* __rest
   }
   __syncthreads();
 
-  // Table entry (i, j) = distance of a[0, i) and b[0, j); anti-diagonal d = i + j, indexed by i (edit_distance_k's sweep).
-  const int W = l.rows + 1;
-  for (int d = 0; d <= la + lb; d++) {
-    int* cur = diag + (d % 3) * W;
-    const int* p1 = diag + ((d + 2) % 3) * W;   // diagonal d - 1: (i - 1, j) at i - 1, (i, j - 1) at i
-    const int* p2 = diag + ((d + 1) % 3) * W;   // diagonal d - 2: (i - 1, j - 1) at i - 1
-    const int lo = d > lb ? d - lb : 0, hi = d < la ? d : la;
-    for (int i = lo + tid; i <= hi; i += EDIT_THREADS) {
-      const int j = d - i;
-      int v;
-      if (i == 0) v = j;
-      else if (j == 0) v = i;
-      else {
-        const int ne = ea[i - 1] != eb[j - 1] ? 1 : 0;
-        const int dg = p2[i - 1] + ne, left = p1[i] + 1, up = p1[i - 1] + 1;
-        v = min(min(up, left), dg);
-        const unsigned code = dg == v ? (unsigned)ne : (left == v ? 3u : 2u);   // the header's tie rule: diagonal, then deletion, then insertion
-        // a row has one cell per diagonal, so this word has one writer now; its first cell starts the word, the barrier orders the others
-        unsigned* word = dir + (i - 1) * stride + ((j - 1) >> 4);
-        const int sh = ((j - 1) & 15) * 2;
-        *word = sh == 0 ? code : (*word | (code << sh));
-      }
-      cur[i] = v;
-    }
-    __syncthreads();   // diagonal d is complete; its readers of d - 2 are done before d + 1 overwrites that buffer
-  }
+  edit_sweep<true>(ea, eb, la, lb, diag, l.rows + 1, dir, stride);
 
   if (tid == 0) {
     int i = la, j = lb, k = 0;
@@ -250,18 +284,38 @@ __global__ __launch_bounds__(EDIT_THREADS) void edit_ops_k(const int64_t* __rest
                        (unsigned long long*)confusion, (int)La, (int)Lb, (int)C);                                                              \
   } while (0)
 
+// The refusals both entry points share: sizes, the limit, and the rows (a row of width 0 may be null).
+static int edit_check(const char* name, int64_t N, int64_t La, int64_t Lb, const int64_t* a, const int64_t* a_len, const int64_t* b,
+                      const int64_t* b_len) {
+  PERO_REQUIRE(N > 0 && N < (1LL << 31) && La >= 0 && Lb >= 0, "%s: bad sizes (N %lld, La %lld, Lb %lld)", name, (long long)N, (long long)La,
+               (long long)Lb);
+  if (La > EDIT_MAX_L || Lb > EDIT_MAX_L) {
+    pero_set_error("%s: supported up to La, Lb = %d (got La %lld, Lb %lld)", name, EDIT_MAX_L, (long long)La, (long long)Lb);
+    return PERO_E_UNSUPPORTED;
+  }
+  PERO_REQUIRE((a || La == 0) && (b || Lb == 0) && a_len && b_len, "%s: null pointer", name);
+  return PERO_OK;
+}
+
+extern "C" int pero_edit_distance(const int64_t* a, const int64_t* a_len, const int64_t* b, const int64_t* b_len, int64_t* dist, int64_t* totals,
+                                  int64_t N, int64_t La, int64_t Lb, void* stream) {
+  const int rc = edit_check("pero_edit_distance", N, La, Lb, a, a_len, b, b_len);
+  if (rc != PERO_OK) return rc;
+  PERO_REQUIRE(dist, "pero_edit_distance: null pointer");
+  hipLaunchKernelGGL(edit_distance_k, dim3((unsigned)N), dim3(EDIT_THREADS), 0, (hipStream_t)stream, a, b, a_len, b_len, dist,
+                     (unsigned long long*)totals, (int)La, (int)Lb);
+  PERO_CHECK_LAUNCH("pero_edit_distance");
+  return PERO_OK;
+}
+
 extern "C" int pero_edit_ops(const int64_t* a, const int64_t* a_len, const int64_t* b, const int64_t* b_len, const uint8_t* is_sep, int64_t* counts,
                              int8_t* script, int32_t* script_len, int32_t* a_spans, int32_t* b_spans, int64_t* totals, int64_t* confusion, int64_t N,
                              int64_t La, int64_t Lb, int64_t C, void* stream) {
-  PERO_REQUIRE(N > 0 && N < (1LL << 31) && La >= 0 && Lb >= 0, "pero_edit_ops: bad sizes (N %lld, La %lld, Lb %lld)", (long long)N, (long long)La,
-               (long long)Lb);
   PERO_REQUIRE(!(confusion || is_sep) || (C >= 1 && C < (1LL << 31) - 1), "pero_edit_ops: bad sizes (C %lld with a confusion matrix or separators)",
                (long long)C);
-  if (La > EDIT_MAX_L || Lb > EDIT_MAX_L) {
-    pero_set_error("pero_edit_ops: supported up to La, Lb = %d (got La %lld, Lb %lld)", EDIT_MAX_L, (long long)La, (long long)Lb);
-    return PERO_E_UNSUPPORTED;
-  }
-  PERO_REQUIRE((a || La == 0) && (b || Lb == 0) && a_len && b_len && counts, "pero_edit_ops: null pointer");
+  const int rc = edit_check("pero_edit_ops", N, La, Lb, a, a_len, b, b_len);
+  if (rc != PERO_OK) return rc;
+  PERO_REQUIRE(counts, "pero_edit_ops: null pointer");
   PERO_REQUIRE(script_len ? (script || La + Lb == 0) : !script, "pero_edit_ops: null pointer (script and script_len are given together)");
   PERO_REQUIRE(!(confusion && is_sep), "pero_edit_ops: the confusion matrix is symbol level only (is_sep must be null with it)");
   PERO_REQUIRE(is_sep || !(a_spans || b_spans), "pero_edit_ops: a_spans and b_spans are word level only (is_sep is null)");

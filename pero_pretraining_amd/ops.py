@@ -1038,16 +1038,23 @@ def ctc_align(logits, targets, input_lengths, target_lengths, blank=0, global_ba
     return states, spans, path_logit, score, label_logp
 
 
+def _edit_args(name, a, a_len, b, b_len, **accumulators):
+    """The checks edit_distance and edit_ops share; the accumulators (named as the message names them) may be None.  Returns N."""
+    tensors = (a, a_len, b, b_len, *accumulators.values())
+    _req_cuda(*tensors)
+    n = a_len.numel()
+    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != n or b.shape[0] != n or b_len.numel() != n or n == 0:
+        raise ValueError(f"{name}: a (N, La), b (N, Lb), a_len and b_len (N)")
+    if any(t is not None and (t.dtype != torch.int64 or not t.is_contiguous()) for t in tensors):
+        what = ["labels", "lengths", *accumulators]
+        raise ValueError(f"{name}: {', '.join(what[:-1])} and {what[-1]} must be contiguous int64 device tensors")
+    return n
+
+
 def edit_distance(a, a_len, b, b_len, totals=None):
     """Levenshtein distance per pair of padded int64 label matrices a (N, La), b (N, Lb) with lengths (N), all on the device: dist (N) int64.
     totals (2 int64 on the device): totals[0] += sum dist, totals[1] += sum b_len, exact (integer atomics)."""
-    _req_cuda(a, a_len, b, b_len, totals)
-    n = a_len.numel()
-    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != n or b.shape[0] != n or b_len.numel() != n or n == 0:
-        raise ValueError("edit_distance: a (N, La), b (N, Lb), a_len and b_len (N)")
-    for t in (a, a_len, b, b_len) + (() if totals is None else (totals,)):
-        if t.dtype != torch.int64 or not t.is_contiguous():
-            raise ValueError("edit_distance: labels, lengths and totals must be contiguous int64 device tensors")
+    n = _edit_args("edit_distance", a, a_len, b, b_len, totals=totals)
     if totals is not None and totals.numel() != 2:
         raise ValueError("edit_distance: totals holds two int64")
     dist = torch.empty(n, device=a.device, dtype=torch.int64)
@@ -1073,13 +1080,7 @@ def edit_ops(a, a_len, b, b_len, num_classes=None, separators=None, totals=None,
     separators: an iterable of class ids (or a ready table of edit_separator_table) -> word level; needs num_classes.
     totals (6 int64 on the device) and confusion ((C + 1, C + 1) int64 on the device, symbol level only; C = num_classes, or taken from its
     shape) are ACCUMULATED, exact (integer atomics)."""
-    _req_cuda(a, a_len, b, b_len, totals, confusion)
-    n = a_len.numel()
-    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != n or b.shape[0] != n or b_len.numel() != n or n == 0:
-        raise ValueError("edit_ops: a (N, La), b (N, Lb), a_len and b_len (N)")
-    for t in (a, a_len, b, b_len) + tuple(t for t in (totals, confusion) if t is not None):
-        if t.dtype != torch.int64 or not t.is_contiguous():
-            raise ValueError("edit_ops: labels, lengths, totals and confusion must be contiguous int64 device tensors")
+    n = _edit_args("edit_ops", a, a_len, b, b_len, totals=totals, confusion=confusion)
     if totals is not None and totals.numel() != 6:
         raise ValueError("edit_ops: totals holds six int64")
     if confusion is not None:

@@ -95,10 +95,8 @@ class TransformerRecognizer(torch.nn.Module):
         keywords behind it: beam_decode's)."""
         with torch.no_grad():
             output = self.encode(images, **ops.key_ranges_kw(self._ranges(input_lengths, key_ranges)))
-        if beam_width is not None:
-            return beam_decode(output, input_lengths, getattr(self.loss, "blank", 0), beam_width, nbest, lm=lm, lm_weight=lm_weight,
-                               length_bonus=length_bonus, class_top=class_top, return_lm_scores=return_lm_scores)
-        return greedy_decode(output, input_lengths, getattr(self.loss, "blank", 0))
+        return _decode_output(output, input_lengths, getattr(self.loss, "blank", 0), beam_width, nbest=nbest, lm=lm, lm_weight=lm_weight,
+                              length_bonus=length_bonus, class_top=class_top, return_lm_scores=return_lm_scores)
 
     def align(self, images, targets, target_lengths, input_lengths=None, key_ranges=None):
         """forced_align of the lines' own logits to the given strings: where every character sits and how sure the model is of it."""
@@ -112,12 +110,8 @@ class TransformerRecognizer(torch.nn.Module):
         blank = getattr(self.loss, "blank", 0)
         with torch.no_grad():
             output = self.encode(images, **ops.key_ranges_kw(self._ranges(input_lengths, key_ranges)))
-            if beam_width is not None:
-                labels, lengths, _ = beam_decode(output, input_lengths, blank, beam_width, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
-                                                 class_top=class_top)
-                labels, lengths = labels.contiguous(), lengths.contiguous()
-            else:
-                labels, lengths = greedy_decode(output, input_lengths, blank)
+            beam_kw = dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, class_top=class_top)
+            labels, lengths = (t.contiguous() for t in _decode_output(output, input_lengths, blank, beam_width, **beam_kw)[:2])
             return labels, lengths, forced_align(output, labels, lengths, input_lengths, blank)
 
     def save(self, path):
@@ -149,6 +143,13 @@ def _decoder_args(output, input_lengths):
 
 def greedy_decode(output, input_lengths=None, blank=0):
     return ops.ctc_greedy(*_decoder_args(output, input_lengths), blank)
+
+
+def _decode_output(output, input_lengths, blank, beam_width, **beam_kw):
+    """The package's one choice of decoder.  Both results begin with (labels, lengths); beam_kw: beam_decode's keywords, unused by greedy."""
+    if beam_width is None:
+        return greedy_decode(output, input_lengths, blank)
+    return beam_decode(output, input_lengths, blank, beam_width, **beam_kw)
 
 
 def beam_decode(output, input_lengths=None, blank=0, beam_width=16, nbest=1, lm=None, lm_weight=1.0, length_bonus=0.0, class_top=None,

@@ -7,7 +7,7 @@ import torch
 
 from .. import ops
 from ..precision import autocast
-from .model import beam_decode, greedy_decode
+from .model import _decode_output
 
 
 def levenshtein(a, b):
@@ -40,9 +40,8 @@ class Tester:
         word_separators adds 'wer', the same ratio over words.  details adds 'substitutions', 'insertions', 'deletions', 'hits', 'lines',
         'line_error_rate' (lines with any error / lines), 'confusion' ((C + 1, C + 1) int64 on the host, C = the logits' classes:
         [reference][hypothesis], index C = the gap; see top_confusions) and, with word_separators, the counts again as 'word_...'."""
-        if self.word_separators is not None or self.details:
-            return self._test_with_operations()
-        total_loss, num_lines, num_batches, totals = 0, 0, 0, None
+        scorer = self._distance_scorer if self.word_separators is None and not self.details else self._operations_scorer
+        total_loss, num_lines, num_batches, add, report = 0, 0, 0, None, None
         self.model.eval()
         with torch.no_grad():
             for batch in self.dataloader:
@@ -51,59 +50,45 @@ class Tester:
                     result = self.model(images, targets, target_lengths, input_lengths)
                 total_loss = total_loss + result["loss"]
                 blank = getattr(self.model.loss, "blank", 0)
-                if self.beam_width is None:
-                    labels, lengths = greedy_decode(result["output"], input_lengths, blank)
-                else:
-                    labels, lengths, _ = beam_decode(result["output"], input_lengths, blank, self.beam_width, **self.lm_kw)
-                if totals is None:
-                    totals = torch.zeros(2, dtype=torch.int64, device=labels.device)   # sum of distances, sum of target lengths
-                ops.edit_distance(labels.contiguous(), lengths.contiguous(), targets.contiguous(), target_lengths.contiguous(), totals)
+                labels, lengths = (t.contiguous() for t in _decode_output(result["output"], input_lengths, blank, self.beam_width, **self.lm_kw)[:2])
+                if add is None:
+                    add, report = scorer(result["output"].shape[-1], labels.device)
+                add(labels, lengths, targets.contiguous(), target_lengths.contiguous())
                 num_lines += self.batch_operator.batch_size(batch)
                 num_batches += 1
                 if self.max_lines is not None and num_lines > self.max_lines:
                     break
         self.model.train()
-        distance, characters = totals.tolist()   # the run's one read of the counts
-        return {"loss": float(total_loss) / num_batches, "cer": distance / max(characters, 1)}
+        return {"loss": float(total_loss) / num_batches, **report()}
 
-    def _test_with_operations(self):
-        """test() over pero_edit_ops.  totals: six int64 per level (pero_edit_ops' totals), row 0 characters, row 1 words."""
-        total_loss, num_lines, num_batches, totals, confusion, is_sep = 0, 0, 0, None, None, None
-        self.model.eval()
-        with torch.no_grad():
-            for batch in self.dataloader:
-                images, targets, target_lengths, input_lengths = self.batch_operator.prepare_batch(batch)
-                with autocast(self.bfloat16):
-                    result = self.model(images, targets, target_lengths, input_lengths)
-                total_loss = total_loss + result["loss"]
-                blank = getattr(self.model.loss, "blank", 0)
-                if self.beam_width is None:
-                    labels, lengths = greedy_decode(result["output"], input_lengths, blank)
-                else:
-                    labels, lengths, _ = beam_decode(result["output"], input_lengths, blank, self.beam_width, **self.lm_kw)
-                if totals is None:
-                    C = result["output"].shape[-1]
-                    totals = torch.zeros((2, 6), dtype=torch.int64, device=labels.device)
-                    if self.details:
-                        confusion = torch.zeros((C + 1, C + 1), dtype=torch.int64, device=labels.device)
-                    if self.word_separators is not None:
-                        is_sep = ops.edit_separator_table(self.word_separators, C, labels.device)   # built once
-                pair = (labels.contiguous(), lengths.contiguous(), targets.contiguous(), target_lengths.contiguous())
-                ops.edit_ops(*pair, num_classes=C, totals=totals[0], confusion=confusion, want_script=False)
-                if is_sep is not None:
-                    ops.edit_ops(*pair, num_classes=C, separators=is_sep, totals=totals[1], want_script=False)
-                num_lines += self.batch_operator.batch_size(batch)
-                num_batches += 1
-                if self.max_lines is not None and num_lines > self.max_lines:
-                    break
-        self.model.train()
-        (sub, ins, dele, hit, lines, wrong), word = totals.tolist()   # the run's one read of the counts
-        out = {"loss": float(total_loss) / num_batches, "cer": (sub + ins + dele) / max(hit + sub + dele, 1)}
-        if self.word_separators is not None:
-            out["wer"] = (word[0] + word[1] + word[2]) / max(word[3] + word[0] + word[2], 1)
-        if self.details:
-            out.update(substitutions=sub, insertions=ins, deletions=dele, hits=hit, lines=lines, line_error_rate=wrong / max(lines, 1),
-                       confusion=confusion.cpu())
+    # A scorer: (add(labels, lengths, targets, target_lengths), report()) over counters on the device; report is the run's one read of them.
+    def _distance_scorer(self, C, device):
+        totals = torch.zeros(2, dtype=torch.int64, device=device)   # sum of distances, sum of target lengths
+
+        def report():
+            distance, characters = totals.tolist()
+            return {"cer": distance / max(characters, 1)}
+        return lambda *pair: ops.edit_distance(*pair, totals), report
+
+    def _operations_scorer(self, C, device):
+        totals = torch.zeros((2, 6), dtype=torch.int64, device=device)   # pero_edit_ops' totals: row 0 characters, row 1 words
+        confusion = torch.zeros((C + 1, C + 1), dtype=torch.int64, device=device) if self.details else None
+        is_sep = None if self.word_separators is None else ops.edit_separator_table(self.word_separators, C, device)   # built once
+
+        def add(*pair):
+            ops.edit_ops(*pair, num_classes=C, totals=totals[0], confusion=confusion, want_script=False)
+            if is_sep is not None:
+                ops.edit_ops(*pair, num_classes=C, separators=is_sep, totals=totals[1], want_script=False)
+
+        def report():
+            (sub, ins, dele, hit, lines, wrong), word = totals.tolist()
+            out = {"cer": (sub + ins + dele) / max(hit + sub + dele, 1)}
             if self.word_separators is not None:
-                out.update(word_substitutions=word[0], word_insertions=word[1], word_deletions=word[2], word_hits=word[3])
-        return out
+                out["wer"] = (word[0] + word[1] + word[2]) / max(word[3] + word[0] + word[2], 1)
+            if self.details:
+                out.update(substitutions=sub, insertions=ins, deletions=dele, hits=hit, lines=lines, line_error_rate=wrong / max(lines, 1),
+                           confusion=confusion.cpu())
+                if self.word_separators is not None:
+                    out.update(word_substitutions=word[0], word_insertions=word[1], word_deletions=word[2], word_hits=word[3])
+            return out
+        return add, report

@@ -1,4 +1,4 @@
-"""GPU: pero_ctc_beam and pero_edit_distance (csrc/ctc_decode.hip) and their users in the recognition package against
+"""GPU: pero_ctc_beam (csrc/ctc_decode.hip) and pero_edit_distance (csrc/edit.hip) and their users in the recognition package against
 tests/ctc_beam_ref.py, whose search test_ctc_beam_ref_cpu.py pins to the CTC likelihood.  Every case goes through the REPLAY check
 (the kernel's own trace, replayed in f64: no line is left out, no margin is needed); the lines whose decisions have a margin of
 2 x the bound are also compared string by string with the independent search.  Every bound is the one ctc_beam_ref's docstring

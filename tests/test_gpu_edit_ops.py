@@ -1,4 +1,4 @@
-"""GPU: pero_edit_ops (csrc/edit_ops.hip) and its users in the recognition package against tests/edit_ops_ref.py, the specification in
+"""GPU: pero_edit_ops (csrc/edit.hip) and its users in the recognition package against tests/edit_ops_ref.py, the specification in
 plain Python that test_edit_ops_ref_cpu.py pins.  The arithmetic is integer and the tie rule makes the script unique, so every output
 is compared with torch.equal: counts, script, script lengths, spans, totals and the confusion matrix; every case is also run twice (equal
 bits, totals and confusion accumulated) and, at symbol level, checked against pero_edit_distance."""
@@ -113,6 +113,14 @@ def test_one_pair_at_the_limit(ops):
     """la = lb = 512 over two symbols, N = 1: the largest table, 1024 steps of walk at the most."""
     want = check(ops, *batch(long_pairs()["limit"]), C=2, confusion=True)
     assert 512 <= int(want["script_len"][0]) <= 1024
+
+
+def test_lengths_around_the_thread_count_and_the_limit(ops):
+    """The sweep both kernels share strides a diagonal by 256 threads and holds at most 512 + 1 cells of it: lengths at 0 and 1, on both
+    sides of 256, and at 512, in matrices of the full width, over two symbols (a tie in nearly every cell)."""
+    rng = random.Random(3)
+    lengths = [(0, 0), (0, 1), (1, 0), (255, 257), (256, 256), (257, 255), (512, 0), (512, 512)]
+    check(ops, *batch([(rand(rng, la, 2), rand(rng, lb, 2)) for la, lb in lengths], 512, 512), C=2, confusion=True)
 
 
 def test_identical_disjoint_and_empty_strings(ops):
@@ -257,3 +265,16 @@ def test_tester_reports_word_error_rate_and_details(beam_width):
     assert (full["word_substitutions"], full["word_insertions"], full["word_deletions"], full["word_hits"]) == (wsub, wins, wdel, whit)
     assert full["wer"] == (wsub + wins + wdel) / max(whit + wsub + wdel, 1) and wsub + wins + wdel > 0
     assert full["confusion"].dtype == I64 and not full["confusion"].is_cuda and torch.equal(full["confusion"], confusion)
+
+
+def test_tester_stops_at_max_lines_with_and_without_details():
+    """max_lines = 3 over three batches of two lines: the loop ends behind the second batch (4 > 3 lines) in both modes, so the details count
+    4 lines and both modes give the same 'cer'.  _recogniser's batches hold 3 and 2 lines; the two-line batches are cut from them."""
+    from pero_pretraining_amd.recognition import Tester
+    model, operator, (first, second), _ = _recogniser()
+    batches = [{k: v[rows] for k, v in b.items()} for b, rows in [(first, slice(0, 2)), (first, slice(1, 3)), (second, slice(0, 2))]]
+    assert [operator.batch_size(b) for b in batches] == [2, 2, 2]
+    plain = Tester(operator, model, batches, max_lines=3).test()
+    full = Tester(operator, model, batches, max_lines=3, details=True).test()
+    assert full["lines"] == 4 and full["cer"] == plain["cer"] and full["loss"] == plain["loss"]
+    assert Tester(operator, model, batches, details=True).test()["lines"] == 6          # without max_lines the third batch counts
