@@ -699,6 +699,47 @@ int pero_ctc_align(const void* logits, const int64_t* targets, const int64_t* in
                    int32_t* states, int32_t* spans, float* path_logit, float* score, float* label_logp, float* row_lse, void* back,
                    int64_t N, int64_t S, int64_t C, int64_t Lmax, int64_t blank, int flags, int dtype, void* stream);
 
+/* ---- Retrieval (evaluation of the joint-embedding model: does a position of one view find its twin in the other?  csrc/retrieval.hip,
+ * DESIGN.md "Retrieval").  The reference looks at this by eye (joint_embedding_pretraining/visualizer.py:63-97: normalise, the full
+ * similarity matrix, torch.topk).
+ *
+ * pero_sim_topk: q (M, D) and keys (N, D) of `dtype`, row pitches ldq, ldk in elements;
+ *   score[m][n] = ((q_m . key_n) * q_scale[m]) * key_scale[n]
+ * the dot accumulated in f32 on the MFMA units, the two multiplications in f32 in this order.  q_scale (M) and key_scale (N) are f32 and
+ * may be null = 1 (the multiplication by 1 is exact: null and a vector of ones give the same bits).  With pero_inv_rownorm's values (or the `inv` of
+ * pero_rownorm_fwd) as scales the score is the cosine; no normalised copy of the rows is written, and the (M, N) score matrix is never stored.
+ * Outputs idx (M, k) int32 and val (M, k) f32, every element written: the k best keys of query m under this STRICT order -
+ *   higher score first;  equal f32 scores: lower key index first
+ * - among the keys that qualify.  A key never enters a list when key_valid[n] == 0 (u8 (N), may be null = all valid), when
+ * n == skip[m] (int32 (M), may be null; self-retrieval, where queries and keys are the same rows), or when its score is NaN
+ * (+-inf scores qualify).  If fewer than k keys qualify the remaining slots are idx = -1, val = -inf.
+ * Because the order is strict the result depends neither on the number of key splits nor on anything else about how the keys are
+ * visited; no float atomics: two calls give the same bits.
+ * Key splits: the grid is (ceil(M / 64) query tiles, key_splits); split s takes the 128-key tiles [T s / S, T (s + 1) / S) of the
+ * T = ceil(N / 128) (a split may be empty), writes its lists to `work`, and a second kernel merges them.  0 <= key_splits <= 128;
+ * key_splits = 0 chooses pero_sim_topk_key_splits(M, N) = max(1, min(ceil(512 / ceil(M / 64)), ceil(N / 128), 128)): two workgroups for
+ * each CU of a 256-CU device where the query tiles alone do not give them, never less than one key tile per split (returns the count,
+ * not a status; a function of M and N alone).
+ * work: at least 8 * S * M * k bytes for S splits in effect (S * M * k f32 scores, then as many int32 indices); may be null for S = 1.
+ * 1 <= k <= PERO_SIM_TOPK_MAX; M, N >= 1; D % 8 == 0; q, keys and both pitches in bytes multiples of 16, pitches >= D: anything else
+ * is PERO_E_INVALID, checked on the host before any launch.
+ *
+ * pero_retrieval_hist: idx (M, k) int32 as written by pero_sim_topk, target (M) int32: the key index of query m's twin, -1 for none.
+ * hist (u64 [k + 2], ACCUMULATED: the caller zeroes it once per test()):  hist[0] += #{m : target[m] >= 0};  hist[1 + r] += #{m :
+ * target[m] >= 0 and idx[m][r] == target[m]} (the first such r);  hist[k + 1] += #{m : target[m] >= 0 and not in idx[m][0..k)}.
+ * recall@j = sum(hist[1..j]) / hist[0];  MRR@k = sum_r hist[1 + r] / (r + 1) / hist[0].  Integer atomics only.  M = 0 is a no-op.
+ *
+ * pero_inv_rownorm: inv[r] (f32) = 1 / max(sqrt(sum_c x[r][c]^2), 1e-12), the sum in f32 (pero_rownorm_fwd's `inv` without its normalised
+ * copy, and with a row pitch): the scales that make pero_sim_topk's score the cosine.  x (rows, D) of `dtype`, pitch ld in elements;
+ * D % 8 == 0 and 16-byte aligned rows as for pero_sim_topk. */
+#define PERO_SIM_TOPK_MAX 16
+int pero_inv_rownorm(const void* x, int64_t ld, float* inv, int64_t rows, int64_t D, int dtype, void* stream);
+int pero_sim_topk_key_splits(int64_t M, int64_t N);
+int pero_sim_topk(const void* q, int64_t ldq, const void* keys, int64_t ldk, const float* q_scale, const float* key_scale,
+                  const unsigned char* key_valid, const int32_t* skip, int32_t* idx, float* val, void* work, int64_t M, int64_t N, int64_t D,
+                  int32_t k, int32_t key_splits, int dtype, void* stream);
+int pero_retrieval_hist(const int32_t* idx, const int32_t* target, uint64_t* hist, int64_t M, int32_t k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,10 @@ SIGNATURES = {
     "pero_edit_distance": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp],
     "pero_edit_ops": [_vp] * 12 + [_i64, _i64, _i64, _i64, _vp],
     "pero_ctc_align": [_vp] * 11 + [_i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp],
+    "pero_sim_topk_key_splits": [_i64, _i64],   # returns the count, not a status
+    "pero_sim_topk": [_vp, _i64, _vp, _i64] + [_vp] * 7 + [_i64, _i64, _i64, _i32, _i32, _i32, _vp],
+    "pero_retrieval_hist": [_vp, _vp, _vp, _i64, _i32, _vp],
+    "pero_inv_rownorm": [_vp, _i64, _vp, _i64, _i64, _i32, _vp],
 }
 # pero_gemm's arguments + int* k_split, int* extra_pass (each may be null); returns the kernel family (> 0: a key of GEMM_KERNELS), so not for call()
 SIGNATURES["pero_gemm_plan"] = SIGNATURES["pero_gemm"] + [_vp, _vp]

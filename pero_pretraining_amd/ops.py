@@ -835,6 +835,57 @@ def label_rank(logits, labels, mask, ks=None, counters=None, want_ranks=False):
     return counters, ranks
 
 
+SIM_TOPK_MAX = 16
+
+
+def sim_topk_key_splits(M, N):
+    """The key-split count pero_sim_topk takes for key_splits = 0 (a function of M and N alone; no GPU needed)."""
+    return int(_lib.lib().pero_sim_topk_key_splits(int(M), int(N)))
+
+
+def sim_topk(q, keys, k, q_scale=None, key_scale=None, key_valid=None, skip=None, key_splits=0):
+    """The k best keys of every query under score = (q . key) * q_scale * key_scale: higher score first, equal scores: lower key index
+    first; keys with key_valid == 0, the key skip[m] and NaN scores never enter; unused slots are -1 / -inf (see pero_sim_topk).
+    q (M, D), keys (N, D) f32 or bf16 with unit inner stride (row pitch = stride(0)); q_scale (M), key_scale (N) f32; key_valid (N) u8 or
+    bool; skip (M) int32.  Returns (idx (M, k) int32, val (M, k) f32)."""
+    _req_cuda(q, keys, q_scale, key_scale, key_valid, skip)
+    M, D = q.shape
+    N = keys.shape[0]
+    if keys.shape[1] != D or keys.dtype != q.dtype or q.stride(1) != 1 or keys.stride(1) != 1:
+        raise ValueError("sim_topk: q (M, D) and keys (N, D) need one dtype, one D and unit inner strides")
+    for name, t, n, dtypes in (("q_scale", q_scale, M, (torch.float32,)), ("key_scale", key_scale, N, (torch.float32,)),
+                               ("key_valid", key_valid, N, (torch.uint8, torch.bool)), ("skip", skip, M, (torch.int32,))):
+        if t is not None and (t.numel() != n or t.dtype not in dtypes or not t.is_contiguous()):
+            raise ValueError(f"sim_topk: {name} must be a contiguous {dtypes[0]} tensor of {n} elements")
+    idx = torch.empty((M, int(k)), device=q.device, dtype=torch.int32)
+    val = torch.empty((M, int(k)), device=q.device, dtype=torch.float32)
+    splits = int(key_splits) if key_splits else sim_topk_key_splits(M, N)
+    work = torch.empty(8 * splits * M * int(k), device=q.device, dtype=torch.uint8) if splits > 1 else None
+    call("pero_sim_topk", ptr(q), q.stride(0), ptr(keys), keys.stride(0), ptr(q_scale), ptr(key_scale), ptr(key_valid), ptr(skip), ptr(idx),
+         ptr(val), ptr(work), M, N, D, int(k), int(key_splits), dt(q), stream())
+    return idx, val
+
+
+def inv_rownorm(x):
+    """inv (rows) f32 = 1 / max(|x_r|_2, 1e-12) of x (rows, D) f32 or bf16 (unit inner stride, row pitch = stride(0)): sim_topk's scales for the
+    cosine."""
+    _req_cuda(x)
+    rows, D = x.shape
+    inv = torch.empty(rows, device=x.device, dtype=torch.float32)
+    call("pero_inv_rownorm", ptr(x), x.stride(0), ptr(inv), rows, D, dt(x), stream())
+    return inv
+
+
+def retrieval_hist(idx, target, hist):
+    """hist (int64 [k + 2] on the device, ACCUMULATED): [0] += queries with target >= 0, [1 + r] += target at rank r of idx's row,
+    [k + 1] += target not in the row (see pero_retrieval_hist).  idx (M, k) int32, target (M) int32."""
+    M, k = idx.shape
+    assert idx.dtype == target.dtype == torch.int32 and idx.is_contiguous() and target.is_contiguous() and target.numel() == M
+    assert hist.dtype == torch.int64 and hist.numel() == k + 2 and hist.is_contiguous()
+    call("pero_retrieval_hist", ptr(idx), ptr(target), ptr(hist), M, k, stream())
+    return hist
+
+
 def stack_lines(packed, offsets, widths, left_px, B, H, Wt, C):
     """Ragged uint8 lines (device, back to back, readable 8 bytes past the end) -> zero-padded (B, H, Wt, C) uint8 batch
     (common/dataloader.py:80-100).  offsets int64, widths / left_px int32 device tensors."""
