@@ -359,12 +359,17 @@ def attention_bwd_fused(qkv, out, dout, lse, n, s, h, dbias=None, dvec=None, key
     return dqkv
 
 
+def ce_work_elems(rows):
+    """f32 elements of the masked cross entropy's workspace: the header's PERO_CE_WORK(rows)."""
+    return 2 * rows + 8 + 256
+
+
 def masked_ce_fwd(logits, labels, mask, unmasked_weight=None):
     """logits (rows,V); labels/mask int64 (rows).  Returns (loss: f32 tensor of 1 element, work buffer)."""
     _req_cuda(logits, labels, mask)
     rows, V = logits.shape
     loss = torch.empty(1, device=logits.device, dtype=torch.float32)
-    work = torch.empty(2 * rows + 8 + 256, device=logits.device, dtype=torch.float32)  # PERO_CE_WORK(rows)
+    work = torch.empty(ce_work_elems(rows), device=logits.device, dtype=torch.float32)
     call("pero_masked_ce_fwd", ptr(logits), ptr(labels), ptr(mask), -1.0 if unmasked_weight is None else float(unmasked_weight),
          ptr(loss), ptr(work), rows, V, dt(logits), stream())
     return loss, work
@@ -374,7 +379,7 @@ def masked_ce_fwd_rows(logits, labels, mask, index):
     """masked_ce_fwd with unmasked_weight None for a caller that lists the rows with mask == 1 (int64 device tensor): same bits."""
     rows, V = logits.shape
     loss = torch.empty(1, device=logits.device, dtype=torch.float32)
-    work = torch.empty(2 * rows + 8 + 256, device=logits.device, dtype=torch.float32)
+    work = torch.empty(ce_work_elems(rows), device=logits.device, dtype=torch.float32)
     call("pero_masked_ce_fwd_rows", ptr(logits), ptr(labels), ptr(mask), ptr(index), index.numel(), ptr(loss), ptr(work), rows, V,
          dt(logits), stream())
     return loss, work
@@ -818,7 +823,7 @@ def add_line_rows_ragged_(dst2, src, count, Sp):
     return dst2
 
 
-MAX_TOPK = 8
+MAX_TOPK = _lib.DEFINES["PERO_MAX_TOPK"]
 
 
 def label_rank(logits, labels, mask, ks=None, counters=None, want_ranks=False):
@@ -835,7 +840,7 @@ def label_rank(logits, labels, mask, ks=None, counters=None, want_ranks=False):
     return counters, ranks
 
 
-SIM_TOPK_MAX = 16
+SIM_TOPK_MAX = _lib.DEFINES["PERO_SIM_TOPK_MAX"]
 
 
 def sim_topk_key_splits(M, N):
@@ -894,7 +899,7 @@ def stack_lines(packed, offsets, widths, left_px, B, H, Wt, C):
     return out
 
 
-AUGMENT_PARAMS = 7   # PERO_AUGMENT_PARAMS: sy, ty, slope, slant, noise_amp, seed_lo, seed_hi
+AUGMENT_PARAMS = _lib.DEFINES["PERO_AUGMENT_PARAMS"]   # sy, ty, slope, slant, noise_amp, seed_lo, seed_hi
 
 
 def augment_stack_lines(packed, offsets, widths, left_px, params, knots, lut, B, H, Wt, C, knot_shift=5):
@@ -1064,7 +1069,7 @@ def ctc_beam_lm(logits, input_lengths, beam_width, lm, lm_weight=1.0, length_bon
     return (out, out_lengths, out_scores, out_count, out_lm, trace) if return_trace else (out, out_lengths, out_scores, out_count, out_lm)
 
 
-CTC_ALIGN_LDS_BACK_BYTES = 96 * 1024   # PERO_CTC_ALIGN_LDS_BACK_BYTES of include/pero_hip.h
+CTC_ALIGN_LDS_BACK_BYTES = _lib.DEFINES["PERO_CTC_ALIGN_LDS_BACK_BYTES"]
 
 
 def ctc_align(logits, targets, input_lengths, target_lengths, blank=0, global_back=False):

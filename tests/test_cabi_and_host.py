@@ -31,6 +31,108 @@ def test_library_exports_every_header_symbol():
     assert h.pero_abi_version() == _lib.ABI_VERSION == 2
 
 
+def test_pinned_signatures():
+    """The binding is parsed from the header; these rows are typed by hand from the header's text, one for every type token and
+    every kind of return value."""
+    import ctypes
+    from pero_pretraining_amd import _lib
+    vp, i64, i32, f32, f64, cp = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_char_p
+    gemm = [vp] * 6 + [i64] * 16 + [f32, i32, i32, i32, i32, vp, i64, vp]
+    assert len(gemm) == 30
+    pinned = {
+        "pero_gemm": (i32, gemm),
+        "pero_gemm_plan": (i32, gemm + [vp, vp]),
+        "pero_adam_step_ex": (i32, [vp] * 5 + [i64, f64, f64, f64, f64, i64, f64, f64, i32, vp, i32, vp, f64, vp]),
+        "pero_ctc_beam_lm": (i32, [vp] * 25 + [i64] * 9 + [f32, f32, i32, i32, vp]),
+        "pero_sim_topk": (i32, [vp, i64, vp, i64] + [vp] * 7 + [i64, i64, i64, i32, i32, i32, vp]),   # int32_t k, key_splits by value
+        "pero_label_rank": (i32, [vp, i64, vp, vp, i64, i64, vp, i32, vp, vp, i32, vp]),               # int32_t nk; uint64_t* is a pointer
+        "pero_gemm_workspace_bytes": (i64, [i64, i64, i64, i64, i32, i32, i32, i32]),
+        "pero_last_error": (cp, []),
+        "pero_abi_version": (i32, []),
+        "pero_set_option": (i32, [cp, i32]),
+    }
+    assert len(pinned["pero_ctc_beam_lm"][1]) == 39
+    for name, (restype, argtypes) in pinned.items():
+        assert _lib.FUNCTIONS[name] == (restype, argtypes), name
+    assert _lib.SIGNATURES["pero_gemm_plan"] == _lib.SIGNATURES["pero_gemm"] + [vp, vp]
+
+
+def test_every_declared_function_is_typed_on_the_handle():
+    import ctypes
+    from pero_pretraining_amd import _lib
+    h = _lib.lib()
+    names = header_functions()
+    assert set(_lib.FUNCTIONS) == set(names) and len(names) >= 86
+    for n in names:
+        fn = getattr(h, n)
+        assert fn.argtypes is not None and (fn.restype, list(fn.argtypes)) == _lib.FUNCTIONS[n], n
+    assert h.pero_gemm_workspace_bytes.restype is ctypes.c_int64 and h.pero_last_error.restype is ctypes.c_char_p
+
+
+def test_header_parser_is_strict():
+    import ctypes
+    from pero_pretraining_amd import _lib
+    fns, defs = _lib.parse_header("""
+        /* int pero_in_block_comment(int a);
+           #define PERO_IN_COMMENT 5 */
+        // int pero_in_line_comment(int a);
+        #ifndef PERO_GUARD_H
+        #define PERO_GUARD_H
+        #define PERO_NEG (-1)      /* comment */
+        #define PERO_BYTES (96 * 1024)
+        #define PERO_PLAIN 16384   // comment
+        #define PERO_SHIFT (1 << 4)
+        #define PERO_WORK(rows) (2 * (rows) + 8)
+        #define PERO_TEXT "1 + 1"
+        #define PERO_CALL __import__("os").getpid()
+        #define PERO_ALIAS PERO_PLAIN
+        const char* pero_text(void);
+        int64_t pero_size(int64_t n, int flags, int32_t k, uint64_t seed);
+        int pero_run(const void* a, float *b, const unsigned char* c, const char* name, float x, double y,
+                     void* stream);
+        #endif
+    """)
+    assert defs == {"PERO_NEG": -1, "PERO_BYTES": 96 * 1024, "PERO_PLAIN": 16384, "PERO_SHIFT": 16}
+    vp = ctypes.c_void_p
+    assert fns == {"pero_text": (ctypes.c_char_p, []),
+                   "pero_size": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_uint64]),
+                   "pero_run": (ctypes.c_int, [vp, vp, vp, ctypes.c_char_p, ctypes.c_float, ctypes.c_double, vp])}
+    for bad, token in [("int pero_f(void* p, half x);", "half"), ("int pero_f(unsigned n);", "unsigned"), ("int pero_f(long long n);", "long long"),
+                       ("void pero_f(int n);", "void"), ("float pero_f(int n);", "float"), ("int pero_f(int);", "int"), ("int pero_f();", "pero_f")]:
+        with pytest.raises(_lib.PeroHipError, match="pero_f") as e:
+            _lib.parse_header(bad)
+        assert token in str(e.value), (bad, str(e.value))
+    with pytest.raises(_lib.PeroHipError):
+        _lib.parse_header("int pero_f(int n); typedef int pero_t;")
+    with pytest.raises(_lib.PeroHipError):
+        _lib.parse_header("int other_f(int n);")
+    assert [_lib.int_expr(t) for t in ("(-1)", "(96 * 1024)", "16384", " 1 << 3 ", "2 * (7) + 8 + 256")] == [-1, 98304, 16384, 8, 278]
+    for text in ("__import__('os')", "2 ** 8", "1 < 2", "()", "1 +", "0x10", "1.5", "abs(1)", ""):
+        with pytest.raises(ValueError):
+            _lib.int_expr(text)
+
+
+def test_constants_come_from_the_header():
+    from pero_pretraining_amd import _lib, ops
+    D = _lib.DEFINES
+    text = open(os.path.join(ROOT, "include", "pero_hip.h")).read()
+    assert set(D) == set(re.findall(r"^#define (PERO_\w+)[ \t]+\S", text, flags=re.M)) and len(D) >= 34
+    for py, name in [("PERO_F32", "PERO_F32"), ("PERO_BF16", "PERO_BF16"), ("LN_BWD_BLOCKS", "PERO_LN_BWD_BLOCKS")] + [
+            ("GEMM_" + n, "PERO_GEMM_" + n) for n in ("RELU", "ATOMIC", "ACCUM", "TRANS_A", "TRANS_B", "FORCE_GENERIC", "ROWDOT", "RELU_BITS",
+                                                      "MASK_TILED", "COLSUM", "TILE_V", "TILE128", "TILE256")]:
+        assert getattr(_lib, py) == D[name] and type(getattr(_lib, py)) is int, py
+    for py, name in [("MAX_TOPK", "PERO_MAX_TOPK"), ("AUGMENT_PARAMS", "PERO_AUGMENT_PARAMS"), ("SIM_TOPK_MAX", "PERO_SIM_TOPK_MAX"),
+                     ("CTC_ALIGN_LDS_BACK_BYTES", "PERO_CTC_ALIGN_LDS_BACK_BYTES")]:
+        assert getattr(ops, py) == D[name], py
+    assert (_lib.PERO_F32, _lib.PERO_BF16, D["PERO_E_INVALID"], D["PERO_CTC_ALIGN_LDS_BACK_BYTES"], D["PERO_GEMM_MASK_TILED"]) == (0, 1, -1, 98304, 16384)
+    assert _lib.GEMM_KERNELS == {1: "generic", 2: "t128", 3: "o128", 4: "r256", 5: "e256", 6: "e256_splitk", 7: "n512"}
+    assert _lib.GEMM_PASSES == {0: None, 1: "colsum", 2: "rowdot"}
+    # the CE workspace: ops' helper against the text of the header's function-like macro
+    (body,) = re.findall(r"^#define PERO_CE_WORK\(rows\)[ \t]+(.+)$", text, flags=re.M)
+    for rows in (1, 7, 4096):
+        assert ops.ce_work_elems(rows) == _lib.int_expr(body.replace("rows", str(rows)))
+
+
 def test_library_never_allocates():
     """include/pero_hip.h: the caller owns every buffer.  No allocation, free, blocking copy or device synchronisation anywhere in csrc/."""
     import glob
