@@ -324,6 +324,57 @@ int pero_sumsq_num_partials(int64_t n);
 int pero_sumsq_partials(const float* x, int64_t n, float* partials, void* stream);
 int pero_grad_norm_finish(const float* partials, int64_t count, double scale, float* norm, void* stream);
 
+/* ---- layer-wise optimizers: LAMB (You et al. 2020) and LARS (You et al. 2017) over flat buffers (csrc/optim_layerwise.hip) ------------
+ * The reference has no counterpart (it trains with torch.optim.Adam); tests/layerwise_ref.py restates these formulas in f64.
+ *
+ * Layout.  A flat f32 buffer holds n_tensors parameter tensors.  table (DEVICE, int64[n_tensors][3]) = {offset, numel, first tile}:
+ * every tensor is cut into ceil(numel / PERO_LAYER_TILE) tiles of PERO_LAYER_TILE elements, tile 0 starting AT the tensor's offset and
+ * the last one possibly short, so no tile crosses a tensor; first tile = the number of tiles of the tensors in front; total_tiles = the
+ * sum.  Offsets are multiples of 8 elements (16-byte aligned f32 AND bf16 tiles) and numel >= 1; the library cannot read the table on
+ * the host, so the caller vouches for it.  The layout is a function of the tensor sizes alone.  One workgroup of 256 lanes takes one
+ * tile: lane t holds the four 16-byte pieces at elements (k * 256 + t) * 4, k = 0..3, of the tile.
+ *
+ * Three launches per step, no float atomics, no waiting between workgroups, no buffer for the update u:
+ *   stage 1   computes u per element and writes partials[2 * tile] = sum p^2, partials[2 * tile + 1] = sum u^2 over the tile (p: the
+ *             parameter BEFORE the step).  Each lane keeps four running f32 sums (one per element of a piece, over its four pieces: 4
+ *             additions), folds them ((a0+a1)+(a2+a3): 2), the 64 lanes of a wave by a butterfly (6), the four waves in order (3).
+ *             partials: f32 [2 * total_tiles].
+ *   finish    one workgroup per tensor adds its tiles' partials in index order in f64 (256 contiguous runs, then the run sums) and
+ *             writes stats[t] = (|p|, |u|, r) as f32: pn = (f32)sqrt(sum p^2), un = (f32)sqrt(sum u^2),
+ *             r = (c * pn) / un in f32 (c = (f32)coefficient) if adapt != 0 and pn > 0 and un > 0, else exactly 1.0 - so a NaN norm
+ *             gives 1 and the NaN reaches p through u.  stats: f32 [n_tensors][3].
+ *   stage 2   computes u again from the same operands by the same f32 operations (the library is compiled with -ffp-contract=off:
+ *             the same bits) and applies it with the tensor's r, writing p and, when p_bf16 is given, its round-to-nearest-even copy.
+ *
+ * Per element, every operation in f32 in exactly this order (coef, 1 / bc1, 1 / sqrt(bc2) with bc1 = 1 - beta1^step,
+ * bc2 = 1 - beta2^step are formed in f64 on the host and rounded once):
+ *   g = grad * grad_scale
+ *   grad_norm != null:  g = g * coef,  coef = min(1, max_norm / (*grad_norm + 1e-6))     (as pero_adam_step_ex; one device float)
+ *   maximize:           g = -g
+ *  LAMB  stage 1:  m = m * beta1 + (1 - beta1) * g ;  v = v * beta2 + ((1 - beta2) * g) * g        (stored)
+ *                  u = (m * (1 / bc1)) / (sqrt(v) * (1 / sqrt(bc2)) + eps) + weight_decay * p
+ *        stage 2:  u from the stored m, v and p as above ;  p = p - (lr * r) * u
+ *  LARS  stage 1:  u = g + weight_decay * p                                                        (nothing stored but the partials)
+ *        stage 2:  u as above ;  buf = momentum * buf + r * u ;  p = p - lr * buf
+ * With r = 1 (adapt == 0) LAMB is AdamW with the decay inside the step, p(1 - lr wd) - lr mhat / denom, and LARS is
+ * torch.optim.SGD(momentum, weight_decay).  Both stages of a step take the same grad_scale, weight_decay, maximize, grad_norm,
+ * max_norm (and betas, eps, step).  step is 1-based; maximize, adapt: 0 or 1. */
+#define PERO_LAYER_TILE 4096
+int pero_lamb_stage1(const float* p, const float* g, float* m, float* v, const int64_t* table, int64_t n_tensors,
+                     int64_t total_tiles, float* partials, double beta1, double beta2, int64_t step, double eps,
+                     double grad_scale, double weight_decay, int maximize, const float* grad_norm, double max_norm, void* stream);
+int pero_lamb_stage2(float* p, const float* m, const float* v, void* p_bf16, const int64_t* table, int64_t n_tensors,
+                     int64_t total_tiles, const float* stats, double lr, double beta1, double beta2, int64_t step, double eps,
+                     double weight_decay, void* stream);
+int pero_lars_stage1(const float* p, const float* g, const int64_t* table, int64_t n_tensors, int64_t total_tiles,
+                     float* partials, double grad_scale, double weight_decay, int maximize, const float* grad_norm,
+                     double max_norm, void* stream);
+int pero_lars_stage2(float* p, const float* g, float* buf, void* p_bf16, const int64_t* table, int64_t n_tensors,
+                     int64_t total_tiles, const float* stats, double lr, double momentum, double grad_scale,
+                     double weight_decay, int maximize, const float* grad_norm, double max_norm, void* stream);
+int pero_layer_ratio_finish(const float* partials, const int64_t* table, int64_t n_tensors, double coefficient, int adapt,
+                            float* stats, void* stream);
+
 /* ---- quantizers (models/autoencoders.py:212-217 ; scripts/produce_kmeans_labels.py:72-76) ---------------
  * indices[m] = argmin_k ( sum(x_m^2) + sum(e_k^2) - 2 x_m . e_k )  in exact f32, first minimum wins.
  * x (M,D) f32, codebook (K,D) f32, indices int64 (M).  best_dist (f32, M) may be null.

@@ -13,7 +13,7 @@ import torch
 
 from ..common.helpers import (get_checkpoint_path, get_training_state_path, load_training_state, save_training_state)
 from ..common.lr_scheduler import WarmupSchleduler
-from ..optim import FusedAdam, FusedAdamW, decay_groups
+from ..optim import FusedAdam, FusedAdamW, FusedLAMB, FusedLARS, decay_groups, layerwise_groups
 from .batch_operator import BatchOperator
 from .model import MaskedCrossEntropyLoss, MaskedTransformerEncoder, init_backbone, init_head
 from .tester import Tester
@@ -79,11 +79,21 @@ def view_step_handler(iteration, model, elapsed_time, iteration_count, trn_teste
 
 
 def init_training(batch_operator, model, dataset, trn_tester, tst_tester, learning_rate, warmup_iterations,
-                  checkpoints_directory, bfloat16=False, clearml_logger=None, data_parallel=None, weight_decay=0.0, max_grad_norm=None):
+                  checkpoints_directory, bfloat16=False, clearml_logger=None, data_parallel=None, weight_decay=0.0, max_grad_norm=None,
+                  optimizer="adam", momentum=0.9):
     """train.py:144-163 with FusedAdam in place of torch.optim.Adam (same hyper-parameters).
     weight_decay > 0 (not in the reference): FusedAdamW over decay_groups(model, weight_decay) - decoupled decay of the matrices, none of
-    the biases and norm weights; max_grad_norm: global-norm clip inside the optimizer's launches (optim.py)."""
-    if weight_decay > 0:
+    the biases and norm weights; max_grad_norm: global-norm clip inside the optimizer's launches (optim.py).
+    optimizer "lamb" / "lars" (not in the reference): FusedLAMB / FusedLARS over layerwise_groups(model, weight_decay) - layer-wise trust
+    ratios on the matrices, none on the biases and norm weights; `momentum` is LARS's."""
+    if optimizer == "lamb":
+        optimizer = FusedLAMB(layerwise_groups(model, weight_decay), lr=learning_rate, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+    elif optimizer == "lars":
+        optimizer = FusedLARS(layerwise_groups(model, weight_decay), lr=learning_rate, momentum=momentum, weight_decay=weight_decay,
+                              max_grad_norm=max_grad_norm)
+    elif optimizer != "adam":
+        raise ValueError(f"Unknown optimizer: {optimizer!r} (adam, lamb, lars)")
+    elif weight_decay > 0:
         optimizer = FusedAdamW(decay_groups(model, weight_decay), lr=learning_rate, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
     else:
         optimizer = FusedAdam(model.parameters(), lr=learning_rate, max_grad_norm=max_grad_norm)

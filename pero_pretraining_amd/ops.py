@@ -544,6 +544,93 @@ def grad_norm_finish(partials, scale, out):
     call("pero_grad_norm_finish", ptr(partials), partials.numel(), float(scale), ptr(out), stream())
 
 
+# layer-wise optimizers (csrc/optim_layerwise.hip): every tensor of a flat buffer in tiles of LAYER_TILE elements that start at the tensor
+LAYER_TILE = _lib.DEFINES["PERO_LAYER_TILE"]
+
+
+def layer_tiles(numel):
+    """Tiles of one tensor: ceil(numel / LAYER_TILE), the last one possibly short."""
+    return (int(numel) + LAYER_TILE - 1) // LAYER_TILE
+
+
+def layer_chain():
+    """Longest chain of f32 additions one tile partial goes through: the lane's running sum over its four pieces (4), the fold of the
+    piece's four elements (2), the wave butterfly (6), the four waves (3).  The tile is fixed, so the chain does not depend on the size."""
+    return 4 + 2 + 6 + 3
+
+
+def layer_table(entries, device):
+    """entries: [(offset, numel)] of the tensors of a flat buffer -> (table int64 [n][3] = {offset, numel, first tile} on `device`,
+    total tiles).  A function of the sizes alone.  The table carries its extent (the largest offset + numel) as `_pero_extent`, a host
+    integer, so that the wrappers below can refuse a flat buffer that is shorter than its table without reading the device."""
+    rows_, tiles = [], 0
+    for off, n in entries:
+        if off % 8 or off < 0 or n < 1:
+            raise ValueError(f"layer_table: offsets are multiples of 8 elements and tensors are not empty, got offset {off}, numel {n}")
+        rows_.append([off, n, tiles])
+        tiles += layer_tiles(n)
+    if not rows_ or tiles >= 1 << 31:
+        raise ValueError(f"layer_table: {len(rows_)} tensors, {tiles} tiles")
+    table = torch.tensor(rows_, dtype=torch.int64).to(device)
+    table._pero_extent = max(off + n for off, n, _ in rows_)
+    return table, tiles
+
+
+def _layer_check(name, table, tiles, f32, flat=(), **sized):
+    """f32: every f32 argument (None allowed); flat: those of them, and the bf16 copy, that the table indexes."""
+    _req_cuda(table, *f32, *flat)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or not table.is_contiguous():
+        raise TypeError(f"{name}: table is a contiguous int64 [n][3] device tensor (ops.layer_table)")
+    if any(t is not None and (t.dtype != torch.float32 or not t.is_contiguous()) for t in f32):
+        raise TypeError(f"{name}: contiguous f32 tensors")
+    for what, (t, need) in sized.items():
+        if t.numel() != need:
+            raise ValueError(f"{name}: {what} holds {t.numel()} elements, the table needs {need}")
+    extent = getattr(table, "_pero_extent", None)
+    if extent is None:
+        raise ValueError(f"{name}: the table does not come from ops.layer_table (its extent is unknown)")
+    for t in flat:
+        if t is not None and t.numel() < extent:
+            raise ValueError(f"{name}: a flat buffer of {t.numel()} elements is shorter than the table's extent {extent}")
+    return table.shape[0], int(tiles)
+
+
+def lamb_stage1(p, g, m, v, table, tiles, partials, beta1, beta2, step, eps, grad_scale=1.0, weight_decay=0.0, maximize=False,
+                grad_norm=None, max_norm=0.0):
+    """m, v <- the moments of this step; partials[2 * tile] = sum p^2, [2 * tile + 1] = sum u^2 of LAMB's update u (include/pero_hip.h)."""
+    n, tiles = _layer_check("lamb_stage1", table, tiles, (p, g, m, v, partials, grad_norm), (p, g, m, v), partials=(partials, 2 * tiles))
+    call("pero_lamb_stage1", ptr(p), ptr(g), ptr(m), ptr(v), ptr(table), n, tiles, ptr(partials), float(beta1), float(beta2), int(step),
+         float(eps), float(grad_scale), float(weight_decay), int(bool(maximize)), ptr(grad_norm), float(max_norm), stream())
+
+
+def lamb_stage2(p, m, v, p_bf16, table, tiles, stats, lr, beta1, beta2, step, eps, weight_decay=0.0):
+    """p <- p - (lr * r) * u with u computed again from the stored m, v and r = stats[tensor][2]; p_bf16 (may be None) <- its bf16 copy."""
+    n, tiles = _layer_check("lamb_stage2", table, tiles, (p, m, v, stats), (p, m, v, p_bf16), stats=(stats, 3 * table.shape[0]))
+    call("pero_lamb_stage2", ptr(p), ptr(m), ptr(v), ptr(p_bf16), ptr(table), n, tiles, ptr(stats), float(lr), float(beta1), float(beta2),
+         int(step), float(eps), float(weight_decay), stream())
+
+
+def lars_stage1(p, g, table, tiles, partials, grad_scale=1.0, weight_decay=0.0, maximize=False, grad_norm=None, max_norm=0.0):
+    """partials[2 * tile] = sum p^2, [2 * tile + 1] = sum u^2 of LARS's update u = g' + weight_decay * p; nothing else is written."""
+    n, tiles = _layer_check("lars_stage1", table, tiles, (p, g, partials, grad_norm), (p, g), partials=(partials, 2 * tiles))
+    call("pero_lars_stage1", ptr(p), ptr(g), ptr(table), n, tiles, ptr(partials), float(grad_scale), float(weight_decay),
+         int(bool(maximize)), ptr(grad_norm), float(max_norm), stream())
+
+
+def lars_stage2(p, g, buf, p_bf16, table, tiles, stats, lr, momentum, grad_scale=1.0, weight_decay=0.0, maximize=False, grad_norm=None,
+                max_norm=0.0):
+    """buf <- momentum * buf + r * u, p <- p - lr * buf with r = stats[tensor][2]; p_bf16 (may be None) <- its bf16 copy."""
+    n, tiles = _layer_check("lars_stage2", table, tiles, (p, g, buf, stats, grad_norm), (p, g, buf, p_bf16), stats=(stats, 3 * table.shape[0]))
+    call("pero_lars_stage2", ptr(p), ptr(g), ptr(buf), ptr(p_bf16), ptr(table), n, tiles, ptr(stats), float(lr), float(momentum),
+         float(grad_scale), float(weight_decay), int(bool(maximize)), ptr(grad_norm), float(max_norm), stream())
+
+
+def layer_ratio_finish(partials, table, tiles, coefficient, adapt, stats):
+    """stats[t] = (|p|, |u|, r): r = coefficient * |p| / |u| if `adapt` and both norms are > 0, else exactly 1."""
+    n, tiles = _layer_check("layer_ratio_finish", table, tiles, (partials, stats), partials=(partials, 2 * tiles), stats=(stats, 3 * table.shape[0]))
+    call("pero_layer_ratio_finish", ptr(partials), ptr(table), n, float(coefficient), int(bool(adapt)), ptr(stats), stream())
+
+
 def vq_argmin(x, codebook, want_dist=False):
     _req_cuda(x, codebook)
     M, D = x.shape

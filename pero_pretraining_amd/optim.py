@@ -14,6 +14,11 @@ finishing launch, and the Adam kernels read the norm from the device.  `optimize
 before clipping, the value torch.nn.utils.clip_grad_norm_ returns, with grad_scale applied - under parallel.DataParallel the norm of
 the averaged gradient, identical on every rank.  Nothing reads it on the host.  Unlike clip_grad_norm_, `.grad` itself is left
 unscaled: the coefficient is applied to the gradient on its way into the moments, so a `.grad` read after step() still holds the raw sum.
+
+FusedLAMB and FusedLARS subclass FusedAdam (the flat buffers, the bf16 and transposed copies, flat_grads / param_offsets / grad_scale /
+grad_norm / refresh_lowp and the clip are its own) and replace the step's launch by three per group: the update u and the tile sums of
+p^2 and u^2, the trust ratio r = c |p| / |u| of every parameter tensor, and the step with r (csrc/optim_layerwise.hip; formulas in
+include/pero_hip.h).  layerwise_groups(model, weight_decay) builds their usual pair of groups.
 """
 import torch
 
@@ -32,11 +37,22 @@ class FusedAdam(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
                                       foreach=None, capturable=False, differentiable=False, fused=None,
                                       decoupled_weight_decay=decoupled_weight_decay, max_grad_norm=max_grad_norm))
+        self._setup()
+
+    def _setup(self):
         self._flat = []  # per group: dict(p, g, m, v, vmax, lp, step)
         self.grad_scale = 1.0
         self.grad_norm = None   # one f32 on the device: the global gradient norm of the last clipped step, before clipping
         self._partials = None   # workspace of the norm: the partial sums of every group, one group behind the other
         self._flatten()
+
+    @staticmethod
+    def _moments(total, dev, group):
+        """The state buffers of one group beside p and g.  A subclass with other state allocates its own here and must then override
+        whatever reads the ones it leaves None: FusedLARS keeps v = None, and state_dict, load_state_dict and _vmax of this class would
+        fail on such an entry - it overrides the first two and never has amsgrad."""
+        return dict(m=ops.zeros((total,), dev, torch.float32), v=ops.zeros((total,), dev, torch.float32),
+                    vmax=ops.zeros((total,), dev, torch.float32) if group["amsgrad"] else None)
 
     def _flatten(self):
         self._flat = []
@@ -75,8 +91,7 @@ class FusedAdam(torch.optim.Optimizer):
                 for p, o in zip(ps, offs):
                     if p.dim() >= 2:
                         lowp.put_t(p, flpt[o:o + p.numel()].view(p.numel() // p.shape[0], p.shape[0]))
-            self._flat.append(dict(p=fp, g=fg, m=ops.zeros((total,), dev, torch.float32), v=ops.zeros((total,), dev, torch.float32),
-                                   vmax=ops.zeros((total,), dev, torch.float32) if group["amsgrad"] else None, lp=flp, step=0,
+            self._flat.append(dict(p=fp, g=fg, **self._moments(total, dev, group), lp=flp, step=0,
                                    params=ps, offsets=offs, lpt=flpt, ttable=ttable, ttiles=ttiles))
 
     def refresh_lowp(self):
@@ -196,9 +211,8 @@ class FusedAdam(torch.optim.Optimizer):
             start += c
         ops.grad_norm_finish(self._partials, self.grad_scale, self.grad_norm)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
+    def _link_grads(self):
+        """Every gradient into its flat buffer; True if any group clips."""
         clipped = False
         for group, f in zip(self.param_groups, self._flat):
             if f is None:
@@ -216,18 +230,27 @@ class FusedAdam(torch.optim.Optimizer):
                     f["g"][o:o + p.numel()].copy_(p.grad.reshape(-1))
                     p.grad = f["g"][o:o + p.numel()].view(p.shape)
             clipped = clipped or group.get("max_grad_norm") is not None
-        if clipped:   # over ALL groups, whichever of them clip, and after every gradient is in its flat buffer
+        return clipped
+
+    def _step_group(self, group, f):
+        """The launches of one group's step (f["step"] is already this step's number)."""
+        b1, b2 = group["betas"]
+        max_norm = group.get("max_grad_norm")
+        ops.adam_step_ex(f["p"], f["g"], f["m"], f["v"], f["lp"], group["lr"], b1, b2, group["eps"], f["step"], self.grad_scale,
+                         weight_decay=group["weight_decay"], decoupled=group.get("decoupled_weight_decay", False),
+                         vmax=self._vmax(f) if group["amsgrad"] else None, maximize=group["maximize"],
+                         grad_norm=self.grad_norm if max_norm is not None else None, max_norm=max_norm or 0.0)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        if self._link_grads():   # over ALL groups, whichever of them clip, and after every gradient is in its flat buffer
             self._global_norm()
         for group, f in zip(self.param_groups, self._flat):
             if f is None:
                 continue
             f["step"] += 1
-            b1, b2 = group["betas"]
-            max_norm = group.get("max_grad_norm")
-            ops.adam_step_ex(f["p"], f["g"], f["m"], f["v"], f["lp"], group["lr"], b1, b2, group["eps"], f["step"], self.grad_scale,
-                             weight_decay=group["weight_decay"], decoupled=group.get("decoupled_weight_decay", False),
-                             vmax=self._vmax(f) if group["amsgrad"] else None, maximize=group["maximize"],
-                             grad_norm=self.grad_norm if max_norm is not None else None, max_norm=max_norm or 0.0)
+            self._step_group(group, f)
             self._transpose(f)
         return loss
 
@@ -239,6 +262,142 @@ class FusedAdamW(FusedAdam):
                  decoupled_weight_decay=True, max_grad_norm=None):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
                          decoupled_weight_decay=decoupled_weight_decay, max_grad_norm=max_grad_norm)
+
+
+class _LayerWise(FusedAdam):
+    """What FusedLAMB and FusedLARS share: the tile table of every group's tensors, the workspace of the tile sums, and `layer_stats`."""
+
+    def _flatten(self):
+        super()._flatten()
+        for f in self._flat:
+            if f is not None:
+                dev = f["p"].device
+                f["ltable"], f["ltiles"] = ops.layer_table([(o, p.numel()) for p, o in zip(f["params"], f["offsets"])], dev)
+                f["lpartials"] = torch.empty(2 * f["ltiles"], device=dev, dtype=torch.float32)
+                f["stats"] = ops.zeros((len(f["params"]), 3), dev, torch.float32)
+
+    @property
+    def layer_stats(self):
+        """One entry per group (None for a group without parameters): the device tensor [n_tensors][3] = (|p| before the step, |u|, trust
+        ratio r) of the last step, in the order of the group's parameters.  step() never reads it on the host."""
+        return [f["stats"] if f is not None else None for f in self._flat]
+
+    @staticmethod
+    def _check(name, lr, weight_decay, max_grad_norm):
+        if lr < 0 or weight_decay < 0:
+            raise ValueError(f"{name}: invalid lr / weight_decay: {lr}, {weight_decay}")
+        if max_grad_norm is not None and not max_grad_norm >= 0:
+            raise ValueError(f"{name}: invalid max_grad_norm: {max_grad_norm}")
+
+
+class FusedLAMB(_LayerWise):
+    """LAMB (You et al., "Large Batch Optimization for Deep Learning", 2020) on FusedAdam's flat buffers: Adam's moments, the update
+    u = mhat / (sqrt(vhat) + eps) + weight_decay * p, and p -= lr * r * u with the trust ratio r = |p| / |u| of each parameter TENSOR
+    (1 where a norm is 0, or in a group with layer_adaptation=False).  Three launches per group and step (csrc/optim_layerwise.hip); the
+    state dict has torch.optim.Adam's layout.  No amsgrad, no clamp on r."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, maximize=False, *, layer_adaptation=True,
+                 max_grad_norm=None, amsgrad=False):
+        if amsgrad:
+            raise ValueError("FusedLAMB: amsgrad is not supported")
+        self._check("FusedLAMB", lr, weight_decay, max_grad_norm)
+        if eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1:
+            raise ValueError(f"FusedLAMB: invalid betas / eps: {betas}, {eps}")
+        torch.optim.Optimizer.__init__(self, params, dict(
+            lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=maximize, foreach=None, capturable=False,
+            differentiable=False, fused=None, decoupled_weight_decay=False, layer_adaptation=layer_adaptation, max_grad_norm=max_grad_norm))
+        self._setup()
+
+    def _step_group(self, group, f):
+        if group["amsgrad"]:
+            raise ValueError("FusedLAMB: amsgrad is not supported")
+        b1, b2 = group["betas"]
+        max_norm = group.get("max_grad_norm")
+        ops.lamb_stage1(f["p"], f["g"], f["m"], f["v"], f["ltable"], f["ltiles"], f["lpartials"], b1, b2, f["step"], group["eps"],
+                        self.grad_scale, group["weight_decay"], group["maximize"], self.grad_norm if max_norm is not None else None,
+                        max_norm or 0.0)
+        ops.layer_ratio_finish(f["lpartials"], f["ltable"], f["ltiles"], 1.0, group.get("layer_adaptation", True), f["stats"])
+        ops.lamb_stage2(f["p"], f["m"], f["v"], f["lp"], f["ltable"], f["ltiles"], f["stats"], group["lr"], b1, b2, f["step"], group["eps"],
+                        group["weight_decay"])
+
+
+class FusedLARS(_LayerWise):
+    """LARS (You et al., "Large Batch Training of Convolutional Networks", 2017) on FusedAdam's flat buffers: u = g + weight_decay * p,
+    buf = momentum * buf + r * u, p -= lr * buf with r = trust_coefficient * |p| / |u| per parameter TENSOR (1 where a norm is 0, or in a
+    group with layer_adaptation=False: torch.optim.SGD).  One state buffer (no second moment); the state dict has torch.optim.SGD's
+    layout.  No Nesterov momentum, no dampening."""
+
+    def __init__(self, params, lr, momentum=0.9, weight_decay=0, trust_coefficient=1e-3, maximize=False, *, layer_adaptation=True,
+                 max_grad_norm=None):
+        self._check("FusedLARS", lr, weight_decay, max_grad_norm)
+        if momentum < 0 or trust_coefficient < 0:
+            raise ValueError(f"FusedLARS: invalid momentum / trust_coefficient: {momentum}, {trust_coefficient}")
+        torch.optim.Optimizer.__init__(self, params, dict(
+            lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=False, maximize=maximize, foreach=None,
+            differentiable=False, fused=None, trust_coefficient=trust_coefficient, layer_adaptation=layer_adaptation,
+            max_grad_norm=max_grad_norm))
+        self._setup()
+
+    @staticmethod
+    def _moments(total, dev, group):
+        return dict(m=ops.zeros((total,), dev, torch.float32), v=None, vmax=None)   # m: the momentum buffer
+
+    def _step_group(self, group, f):
+        if group.get("nesterov") or group.get("dampening"):
+            raise ValueError("FusedLARS: nesterov / dampening are not supported")
+        max_norm = group.get("max_grad_norm")
+        clip = dict(grad_scale=self.grad_scale, weight_decay=group["weight_decay"], maximize=group["maximize"],
+                    grad_norm=self.grad_norm if max_norm is not None else None, max_norm=max_norm or 0.0)
+        ops.lars_stage1(f["p"], f["g"], f["ltable"], f["ltiles"], f["lpartials"], **clip)
+        ops.layer_ratio_finish(f["lpartials"], f["ltable"], f["ltiles"], group["trust_coefficient"], group.get("layer_adaptation", True),
+                               f["stats"])
+        ops.lars_stage2(f["p"], f["g"], f["m"], f["lp"], f["ltable"], f["ltiles"], f["stats"], group["lr"], group["momentum"], **clip)
+
+    # ---- checkpointing: torch.optim.SGD's layout (per-parameter 'momentum_buffer', no step counter)
+    def state_dict(self):
+        state, groups, idx = {}, [], 0
+        for group, f in zip(self.param_groups, self._flat):
+            offs = {id(p): o for p, o in zip(f["params"], f["offsets"])} if f is not None else {}
+            ids = []
+            for p in group["params"]:
+                if id(p) in offs and f["step"] > 0:
+                    o, n = offs[id(p)], p.numel()
+                    state[idx] = {"momentum_buffer": f["m"][o:o + n].view(p.shape).clone()}
+                ids.append(idx)
+                idx += 1
+            g = {k: v for k, v in group.items() if k != "params"}
+            g["params"] = ids
+            groups.append(g)
+        return {"state": state, "param_groups": groups}
+
+    def load_state_dict(self, state_dict):
+        groups = state_dict["param_groups"]
+        if len(groups) != len(self.param_groups):
+            raise ValueError("loaded state dict has a different number of parameter groups")
+        for group, saved, f in zip(self.param_groups, groups, self._flat):
+            if len(saved["params"]) != len(group["params"]):
+                raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
+            for k, v in saved.items():
+                if k != "params":
+                    group[k] = v
+            if f is None:
+                continue
+            offs = {id(p): o for p, o in zip(f["params"], f["offsets"])}
+            f["m"].zero_()
+            f["step"] = 0   # counts this object's steps only: the update does not depend on it
+            for p, idx in zip(group["params"], saved["params"]):
+                buf = (state_dict["state"].get(idx) or {}).get("momentum_buffer")
+                if buf is not None and id(p) in offs:
+                    o = offs[id(p)]
+                    f["m"][o:o + p.numel()].copy_(buf.reshape(-1))
+                    f["step"] = 1
+
+
+def layerwise_groups(model, weight_decay):
+    """decay_groups for FusedLAMB / FusedLARS: the biases and norm weights (dim() < 2) are neither decayed nor adapted (their group has
+    weight_decay=0 and layer_adaptation=False), as the published LARS / LAMB recipes exclude them."""
+    decayed, rest = decay_groups(model, weight_decay)
+    return [dict(decayed, layer_adaptation=True), dict(rest, weight_decay=0.0, layer_adaptation=False)]
 
 
 def decay_groups(model, weight_decay):
