@@ -791,6 +791,52 @@ int pero_sim_topk(const void* q, int64_t ldq, const void* keys, int64_t ldk, con
                   int32_t k, int32_t key_splits, int dtype, void* stream);
 int pero_retrieval_hist(const int32_t* idx, const int32_t* target, uint64_t* hist, int64_t M, int32_t k, void* stream);
 
+/* ---- latent-target self-distillation: EMA teacher, normalised layer-averaged targets, regression loss (csrc/latent.hip) --------------
+ * The reference has no counterpart (it predicts discrete labels); tests/latent_ref.py restates these formulas in f64.  No float atomics:
+ * every addition has a fixed place, so the same inputs give the same bits from run to run.  All HBM-bound.
+ *
+ * pero_ema_update: the weight average of a whole model in one launch.  table (DEVICE, int64[n_segments][4]) = {source address, destination
+ * offset, count, first tile}: segment s averages `count` f32 values at the device ADDRESS table[s][0] (any 4-byte alignment, any
+ * allocation) into avg[offset .. offset + count).  Every segment is cut into ceil(count / PERO_LAYER_TILE) tiles that start AT the segment,
+ * the last one possibly short; first tile = the tiles of the segments in front, total_tiles = the sum.  Offsets are multiples of 8 elements
+ * (16-byte aligned f32 and bf16 pieces: optim.FusedAdam's layout), count >= 1; the library cannot read the table on the host, so the
+ * caller vouches for it.  One workgroup of 256 lanes per tile, lane t holding the four 16-byte pieces at elements (k * 256 + t) * 4; a
+ * tile whose source is not 16-byte aligned reads it by scalar loads (a branch per workgroup).  Per element, in f32, in this order:
+ *   a = a + w * (p - a),  w = (float)(1 - tau) formed by the caller in f64 and rounded once
+ * avg_bf16 (may be null; the layout of avg) <- round-to-nearest-even(a) in the same launch.  Elements of avg between the segments (the
+ * padding to 8) are neither read nor written.
+ *
+ * pero_latent_targets: mats = HOST array of K DEVICE pointers (the one host pointer of this header: read during the call, the addresses
+ * travel in the kernel's arguments), 1 <= K <= PERO_LATENT_MAX_K matrices (rows, d) of `dtype`, contiguous; index (n) int64, unique rows;
+ * y f32 (n_pad, d), n_pad >= n.  For i < n, r = index[i], for every matrix t_k (all statistics in f32):
+ *   mu = (sum_j t_k[r][j]) / d ;  var = (sum_j (t_k[r][j] - mu)^2) / d ;  rs = 1 / sqrt(var + eps) ;  xhat_k[j] = (t_k[r][j] - mu) * rs
+ *   y[i][j] = (xhat_0[j] + xhat_1[j] + ... + xhat_{K-1}[j]) * (float)(1 / K)          (added in the order k = 0 .. K - 1)
+ * Rows n <= i < n_pad are exact zeros; a row with an index outside [0, rows) is NaN (nothing is read for it).  One 64-lane wave per row
+ * holds the row in registers, so each row of each matrix is read exactly once.  Order of the two row sums: lane l adds its elements in
+ * ascending column order - columns (c * 64 + l) * 4 .. + 3 for c = 0, 1, .. - then the 64 lanes by a butterfly (xor 32, 16, .. 1).
+ * Supported widths: d % 4 == 0, 4 <= d <= PERO_LATENT_MAX_D, every matrix 16-byte aligned; anything else is PERO_E_INVALID, checked on
+ * the host before any launch (no scalar path for other widths).
+ *
+ * pero_latent_loss_fwd / _bwd: pred (n_pad, d) of `dtype`, y f32 (n_pad, d), rows i < n count.  e = pred - y in f32;
+ *   beta > 0:  l(e) = ((0.5 * e) * e) / beta  if |e| < beta,  else |e| - 0.5 * beta         (torch smooth_l1_loss)
+ *   beta == 0: l(e) = e * e                                                                   (MSE)
+ *   loss[0] = (float)((sum_{i < n} rowsum[i]) / ((double)n * d)),  rowsum[i] = sum_j l(e[i][j]) in f32
+ * rowsum (work, f32 [n]): one wave per row, lane l adding columns (c * 64 + l) * 4 .. + 3 for c = 0, 1, .. in ascending order, then the
+ * butterfly; the finishing pass is one workgroup adding rowsum in f64 in index order (256 contiguous runs, then the run sums).  n = 0
+ * gives NaN (0 / 0), as a mean over nothing does.
+ *   dpred[i][j] = g * l'(e),  g = dloss[0] * (float)(1 / ((double)n * d)) in f32;  l'(e) = e / beta if |e| < beta else sign(e);  MSE: 2 * e
+ * written in pred's dtype; rows n <= i < n_pad are exact zeros.  dloss: DEVICE pointer to one f32 (null = 1).  d % 4 == 0, d >= 4,
+ * pred / y / dpred 16-byte aligned, beta >= 0: anything else is PERO_E_INVALID. */
+#define PERO_LATENT_MAX_K 16
+#define PERO_LATENT_MAX_D 4096
+int pero_ema_update(float* avg, void* avg_bf16, const int64_t* table, int64_t n_segments, int64_t total_tiles, float w, void* stream);
+int pero_latent_targets(const void** mats, int64_t K, const int64_t* index, float* y, int64_t rows, int64_t n, int64_t n_pad, int64_t d,
+                        float eps, int dtype, void* stream);
+int pero_latent_loss_fwd(const void* pred, const float* y, float* work, float* loss, int64_t n, int64_t d, float beta, int dtype,
+                         void* stream);
+int pero_latent_loss_bwd(const void* pred, const float* y, const float* dloss, void* dpred, int64_t n, int64_t n_pad, int64_t d, float beta,
+                         int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,294 @@
+// Latent-target self-distillation: the EMA of a whole model in one launch, the normalised layer-averaged targets at the listed rows, and
+// the regression loss (smooth L1 / MSE) with its gradient.  All HBM-bound, no float atomics, every sum in a fixed order.  Formulas,
+// operation order and layouts: include/pero_hip.h ("latent-target self-distillation").
+#include "common.hpp"
+
+#define LT PERO_LAYER_TILE   // elements of a tile = 256 lanes x 4 pieces of 16 bytes
+
+// ---------------------------------------------------------------------------------------------
+// EMA.  table[s] = {source address, destination offset, count, first tile}; the segment of tile `bid` is the last one whose first tile is
+// <= bid (binary search, as optim_layerwise.hip).  A tile behind its segment's end has count 0 and touches no element.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ema_update_k(float* avg, bf16raw* avg_bf16, const long long* table, int n, float w) {
+  const long long bid = blockIdx.x;
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (table[mid * 4 + 3] <= bid) lo = mid; else hi = mid - 1;
+  }
+  const long long local = bid - table[lo * 4 + 3];
+  const long long left = local >= 0 ? table[lo * 4 + 2] - local * LT : 0;
+  const int count = left >= LT ? LT : (left > 0 ? (int)left : 0);
+  const float* src = (const float*)(uintptr_t)table[lo * 4] + local * LT;
+  float* a = avg + table[lo * 4 + 1] + local * LT;
+  bf16raw* ab = avg_bf16 ? avg_bf16 + table[lo * 4 + 1] + local * LT : nullptr;
+  const bool vec = (((uintptr_t)src) & 15) == 0;   // uniform over the workgroup: a source that is not 16-byte aligned takes scalar loads
+  f4v pp[4], aa[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int e = (k * 256 + threadIdx.x) * 4;
+    pp[k] = (f4v){0.f, 0.f, 0.f, 0.f};
+    aa[k] = (f4v){0.f, 0.f, 0.f, 0.f};
+    if (e + 4 <= count) {
+      aa[k] = *(const f4v*)(a + e);
+      if (vec) pp[k] = *(const f4v*)(src + e);
+      else { pp[k][0] = src[e]; pp[k][1] = src[e + 1]; pp[k][2] = src[e + 2]; pp[k][3] = src[e + 3]; }
+    } else {
+      for (int j = 0; j < 4; j++)
+        if (e + j < count) { aa[k][j] = a[e + j]; pp[k][j] = src[e + j]; }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int e = (k * 256 + threadIdx.x) * 4;
+#pragma unroll
+    for (int j = 0; j < 4; j++) aa[k][j] = aa[k][j] + w * (pp[k][j] - aa[k][j]);
+    if (e + 4 <= count) {
+      *(f4v*)(a + e) = aa[k];
+      if (ab) { uint2 o; o.x = pack2bf(aa[k][0], aa[k][1]); o.y = pack2bf(aa[k][2], aa[k][3]); *(uint2*)(ab + e) = o; }
+    } else {
+      for (int j = 0; j < 4; j++)
+        if (e + j < count) { a[e + j] = aa[k][j]; if (ab) ab[e + j] = f2bf(aa[k][j]); }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Four consecutive elements as one 16-byte (f32) or 8-byte (bf16) access
+// ---------------------------------------------------------------------------------------------
+template <typename T> __device__ __forceinline__ f4v load4(const T* p);
+template <> __device__ __forceinline__ f4v load4<float>(const float* p) { return *(const f4v*)p; }
+template <> __device__ __forceinline__ f4v load4<bf16raw>(const bf16raw* p) {
+  const uint2 r = *(const uint2*)p;
+  return (f4v){__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
+}
+template <typename T> __device__ __forceinline__ void store4(T* p, f4v v);
+template <> __device__ __forceinline__ void store4<float>(float* p, f4v v) { *(f4v*)p = v; }
+template <> __device__ __forceinline__ void store4<bf16raw>(bf16raw* p, f4v v) {
+  uint2 o;
+  o.x = pack2bf(v[0], v[1]); o.y = pack2bf(v[2], v[3]);
+  *(uint2*)p = o;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Targets.  One wave per output row, the row of one matrix in registers: NCH chunks of 256 columns, lane l holding columns
+// (c * 64 + l) * 4 .. + 3 of chunk c.  d <= 256 * NCH.
+// ---------------------------------------------------------------------------------------------
+struct LatentMats { const void* p[PERO_LATENT_MAX_K]; };
+
+template <typename T, int NCH>
+__global__ __launch_bounds__(256) void latent_targets_k(LatentMats mats, int K, const long long* index, float* y, long long rows,
+                                                        long long n, long long n_pad, int d, float eps, float inv_k) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n_pad) return;
+  float* out = y + i * d;
+  const long long r = i < n ? index[i] : 0;
+  if (i >= n || r < 0 || r >= rows) {   // padding: exact zeros; an index outside the matrices: NaN, nothing read
+    const float fill = i >= n ? 0.f : __uint_as_float(0x7fc00000u);
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+      const int col = (c * 64 + lane) * 4;
+      if (col < d) *(f4v*)(out + col) = (f4v){fill, fill, fill, fill};
+    }
+    return;
+  }
+  f4v acc[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; c++) acc[c] = (f4v){0.f, 0.f, 0.f, 0.f};
+  for (int k = 0; k < K; k++) {
+    const T* x = (const T*)mats.p[k] + r * d;
+    f4v v[NCH];
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+      const int col = (c * 64 + lane) * 4;
+      v[c] = (f4v){0.f, 0.f, 0.f, 0.f};
+      if (col < d) v[c] = load4<T>(x + col);
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; c++)
+      if ((c * 64 + lane) * 4 < d) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) s += v[c][j];
+      }
+    const float mu = wave_sum(s) / (float)d;
+    float q = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; c++)
+      if ((c * 64 + lane) * 4 < d) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) { const float t = v[c][j] - mu; q += t * t; }
+      }
+    const float rs = 1.0f / sqrtf(wave_sum(q) / (float)d + eps);
+#pragma unroll
+    for (int c = 0; c < NCH; c++)
+#pragma unroll
+      for (int j = 0; j < 4; j++) acc[c][j] = acc[c][j] + (v[c][j] - mu) * rs;
+  }
+#pragma unroll
+  for (int c = 0; c < NCH; c++) {
+    const int col = (c * 64 + lane) * 4;
+    if (col < d) *(f4v*)(out + col) = (f4v){acc[c][0] * inv_k, acc[c][1] * inv_k, acc[c][2] * inv_k, acc[c][3] * inv_k};
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Loss.  MSE: beta == 0.
+// ---------------------------------------------------------------------------------------------
+template <bool MSE> __device__ __forceinline__ float latent_l(float e, float beta) {
+  if (MSE) return e * e;
+  const float ae = fabsf(e);
+  return ae < beta ? ((0.5f * e) * e) / beta : ae - 0.5f * beta;
+}
+template <bool MSE> __device__ __forceinline__ float latent_dl(float e, float beta) {
+  if (MSE) return 2.0f * e;
+  return fabsf(e) < beta ? e / beta : (e > 0.f ? 1.0f : (e < 0.f ? -1.0f : e));   // (|e| >= beta > 0 leaves no zero here; a NaN stays a NaN)
+}
+
+template <typename T, bool MSE>
+__global__ __launch_bounds__(256) void latent_loss_rows_k(const T* pred, const float* y, float* rowsum, long long n, int d, float beta) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const T* p = pred + i * d;
+  const float* t = y + i * d;
+  float s = 0.f;
+  for (int col = lane * 4; col < d; col += 256) {
+    const f4v a = load4<T>(p + col), b = load4<float>(t + col);
+#pragma unroll
+    for (int j = 0; j < 4; j++) s += latent_l<MSE>(a[j] - b[j], beta);
+  }
+  s = wave_sum(s);
+  if (lane == 0) rowsum[i] = s;
+}
+
+// one workgroup: rowsum in index order in f64, 256 contiguous runs and then the run sums (grad_norm_finish_k's order)
+__global__ __launch_bounds__(256) void latent_loss_finish_k(const float* rowsum, float* loss, long long n, int d) {
+  __shared__ double runs[256];
+  const long long per = (n + 255) / 256;
+  const long long a = threadIdx.x * per, b = a + per < n ? a + per : n;
+  double t = 0.0;
+  for (long long i = a; i < b; i++) t += (double)rowsum[i];
+  runs[threadIdx.x] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int i = 0; i < 256; i++) s += runs[i];
+    loss[0] = (float)(s / ((double)n * (double)d));
+  }
+}
+
+template <typename T, bool MSE>
+__global__ __launch_bounds__(256) void latent_loss_bwd_k(const T* pred, const float* y, const float* dloss, T* dpred, long long n_live,
+                                                         long long n_all, float coef, float beta) {
+  // n_live, n_all: pieces of four elements inside the first n rows / inside all n_pad rows
+  const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= n_all) return;
+  f4v o = {0.f, 0.f, 0.f, 0.f};
+  if (q < n_live) {
+    const float g = (dloss ? dloss[0] : 1.0f) * coef;
+    const f4v a = load4<T>(pred + q * 4), b = load4<float>(y + q * 4);
+#pragma unroll
+    for (int j = 0; j < 4; j++) o[j] = g * latent_dl<MSE>(a[j] - b[j], beta);
+  }
+  store4<T>(dpred + q * 4, o);
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+extern "C" int pero_ema_update(float* avg, void* avg_bf16, const int64_t* table, int64_t n_segments, int64_t total_tiles, float w,
+                               void* stream) {
+  PERO_REQUIRE(avg && table, "pero_ema_update: null pointer");
+  PERO_REQUIRE(n_segments > 0 && n_segments < (1LL << 31) && total_tiles >= n_segments && total_tiles < (1LL << 31),
+               "pero_ema_update: segment count / tile count (every segment has a tile; fewer than 2^31 tiles)");
+  PERO_REQUIRE(aligned16(avg) && (!avg_bf16 || (((uintptr_t)avg_bf16) & 7) == 0), "pero_ema_update: alignment");
+  hipLaunchKernelGGL(ema_update_k, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, avg, (bf16raw*)avg_bf16,
+                     (const long long*)table, (int)n_segments, w);
+  PERO_CHECK_LAUNCH("pero_ema_update");
+  return PERO_OK;
+}
+
+template <typename T>
+static void launch_targets(int nch, dim3 grid, hipStream_t st, const LatentMats& m, int K, const int64_t* index, float* y, int64_t rows,
+                           int64_t n, int64_t n_pad, int d, float eps, float inv_k) {
+#define LATENT_TARGETS_CASE(N_)                                                                                                      \
+  hipLaunchKernelGGL((latent_targets_k<T, N_>), grid, dim3(256), 0, st, m, K, (const long long*)index, y, (long long)rows, (long long)n, \
+                     (long long)n_pad, d, eps, inv_k)
+  if (nch <= 1) LATENT_TARGETS_CASE(1);
+  else if (nch <= 2) LATENT_TARGETS_CASE(2);
+  else if (nch <= 4) LATENT_TARGETS_CASE(4);
+  else if (nch <= 8) LATENT_TARGETS_CASE(8);
+  else LATENT_TARGETS_CASE(16);
+#undef LATENT_TARGETS_CASE
+}
+
+extern "C" int pero_latent_targets(const void** mats, int64_t K, const int64_t* index, float* y, int64_t rows, int64_t n, int64_t n_pad,
+                                   int64_t d, float eps, int dtype, void* stream) {
+  PERO_REQUIRE(mats && y && (index || n == 0), "pero_latent_targets: null pointer");
+  PERO_REQUIRE(K >= 1 && K <= PERO_LATENT_MAX_K, "pero_latent_targets: 1 <= K <= %d matrices, got %lld", PERO_LATENT_MAX_K, (long long)K);
+  PERO_REQUIRE(dtype == PERO_F32 || dtype == PERO_BF16, "pero_latent_targets: dtype");
+  PERO_REQUIRE(d >= 4 && d % 4 == 0 && d <= PERO_LATENT_MAX_D, "pero_latent_targets: d must be a multiple of 4 in [4, %d], got %lld",
+               PERO_LATENT_MAX_D, (long long)d);
+  PERO_REQUIRE(rows >= 1 && n >= 0 && n_pad >= n && n_pad < (1LL << 32), "pero_latent_targets: rows / n / n_pad");
+  PERO_REQUIRE(aligned16(y), "pero_latent_targets: y must be 16-byte aligned");
+  LatentMats m;
+  for (int k = 0; k < PERO_LATENT_MAX_K; k++) m.p[k] = k < K ? mats[k] : nullptr;
+  for (int k = 0; k < K; k++) PERO_REQUIRE(m.p[k] && aligned16(m.p[k]), "pero_latent_targets: matrix %d is null or not 16-byte aligned", k);
+  if (n_pad == 0) return PERO_OK;
+  const dim3 grid((unsigned)((n_pad + 3) / 4));
+  const int nch = (int)((d + 255) / 256);
+  const float inv_k = (float)(1.0 / (double)K);
+  if (dtype == PERO_F32) launch_targets<float>(nch, grid, (hipStream_t)stream, m, (int)K, index, y, rows, n, n_pad, (int)d, eps, inv_k);
+  else launch_targets<bf16raw>(nch, grid, (hipStream_t)stream, m, (int)K, index, y, rows, n, n_pad, (int)d, eps, inv_k);
+  PERO_CHECK_LAUNCH("pero_latent_targets");
+  return PERO_OK;
+}
+
+#define LATENT_REQUIRE_LOSS(name)                                                                                              \
+  PERO_REQUIRE(dtype == PERO_F32 || dtype == PERO_BF16, name ": dtype");                                                       \
+  PERO_REQUIRE(d >= 4 && d % 4 == 0 && d < (1LL << 31), name ": d must be a multiple of 4, got %lld", (long long)d);            \
+  PERO_REQUIRE(beta >= 0.f, name ": beta must not be negative (0 = MSE)")
+
+extern "C" int pero_latent_loss_fwd(const void* pred, const float* y, float* work, float* loss, int64_t n, int64_t d, float beta, int dtype,
+                                    void* stream) {
+  PERO_REQUIRE(loss && n >= 0 && n < (1LL << 32) && (n == 0 || (pred && y && work)), "pero_latent_loss_fwd: null pointer or row count");
+  LATENT_REQUIRE_LOSS("pero_latent_loss_fwd");
+  PERO_REQUIRE(aligned16(pred) && aligned16(y), "pero_latent_loss_fwd: 16-byte alignment");
+  hipStream_t st = (hipStream_t)stream;
+  if (n > 0) {
+    const dim3 grid((unsigned)((n + 3) / 4));
+    const bool mse = beta == 0.f;
+#define LATENT_ROWS(T_, M_) \
+  hipLaunchKernelGGL((latent_loss_rows_k<T_, M_>), grid, dim3(256), 0, st, (const T_*)pred, y, work, (long long)n, (int)d, beta)
+    if (dtype == PERO_F32) { if (mse) LATENT_ROWS(float, true); else LATENT_ROWS(float, false); }
+    else { if (mse) LATENT_ROWS(bf16raw, true); else LATENT_ROWS(bf16raw, false); }
+#undef LATENT_ROWS
+    PERO_CHECK_LAUNCH("pero_latent_loss_fwd");
+  }
+  hipLaunchKernelGGL(latent_loss_finish_k, dim3(1), dim3(256), 0, st, work, loss, (long long)n, (int)d);
+  PERO_CHECK_LAUNCH("pero_latent_loss_fwd");
+  return PERO_OK;
+}
+
+extern "C" int pero_latent_loss_bwd(const void* pred, const float* y, const float* dloss, void* dpred, int64_t n, int64_t n_pad, int64_t d,
+                                    float beta, int dtype, void* stream) {
+  PERO_REQUIRE(n >= 0 && n_pad >= n && (n_pad == 0 || dpred) && (n == 0 || (pred && y)), "pero_latent_loss_bwd: null pointer or row counts");
+  LATENT_REQUIRE_LOSS("pero_latent_loss_bwd");
+  PERO_REQUIRE(aligned16(pred) && aligned16(y) && aligned16(dpred), "pero_latent_loss_bwd: 16-byte alignment");
+  const long long n_live = n * (d / 4), n_all = n_pad * (d / 4);
+  PERO_REQUIRE((n_all + 255) / 256 < (1LL << 31), "pero_latent_loss_bwd: too many elements for one launch");
+  if (n_all == 0) return PERO_OK;
+  const float coef = n > 0 ? (float)(1.0 / ((double)n * (double)d)) : 0.f;
+  const dim3 grid((unsigned)((n_all + 255) / 256));
+  const bool mse = beta == 0.f;
+#define LATENT_BWD(T_, M_)                                                                                                            \
+  hipLaunchKernelGGL((latent_loss_bwd_k<T_, M_>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)pred, y, dloss, (T_*)dpred, n_live, \
+                     n_all, coef, beta)
+  if (dtype == PERO_F32) { if (mse) LATENT_BWD(float, true); else LATENT_BWD(float, false); }
+  else { if (mse) LATENT_BWD(bf16raw, true); else LATENT_BWD(bf16raw, false); }
+#undef LATENT_BWD
+  PERO_CHECK_LAUNCH("pero_latent_loss_bwd");
+  return PERO_OK;
+}

@@ -450,10 +450,12 @@ def layer_bwd_rows(dtc, index, nrows, L, saved, n, s, h, dtype, side=None, prev=
 # ---------------------------------------------------------------------------------------------
 # whole backbone: front end + L layers
 # ---------------------------------------------------------------------------------------------
-def backbone_fwd(mod, x, mask, offsets, dtype, save, key_ranges=None):
+def backbone_fwd(mod, x, mask, offsets, dtype, save, key_ranges=None, tap=None):
     """x: uint8 (N,H,W,C) line images, or float32 (N,C,H,W) (the reference's model input).
     key_ranges: int32 (N, 2) device tensor or None - every layer's attention takes the keys [k0, k1) of a line only (the backward reads it from the layers' saved state).
-    Returns (tokens (N*S, d) in `dtype`, saved activations or None)."""
+    tap: None, or a list of layer indices (0-based, each in [0, num_blocks)): the output matrices (N*S, d) of those layers - the `t` layer_fwd returns - are
+    returned as well, in the list's order.
+    Returns (tokens (N*S, d) in `dtype`, saved activations or None), with `tap` (tokens, saved, [tapped matrices])."""
     keep = None
     if save and ln_from_out(dtype):
         # per-layer fallback to the input rows (ln_keep_rows), decided before the first launch; a captured step (Trainer(hip_graph=True))
@@ -484,11 +486,16 @@ def backbone_fwd(mod, x, mask, offsets, dtype, save, key_ranges=None):
     pe = mod.position_model.pe_table(x.device)
     t, mean0, rstd0 = ops.layernorm_fwd(y0, mod.intermediate_norm.weight.detach(), mod.intermediate_norm.bias.detach(),
                                         mod.intermediate_norm.eps, pe=pe, offsets=offsets, S=s)
-    layers = []
+    layers, outs = [], {}
     for i, L in enumerate(mod.encoder_layers.layers):
         t, sv = layer_fwd(t, L, n, s, mod.num_heads, dtype, save, force_keep_y=keep is not None and keep[i], key_ranges=key_ranges)
         layers.append(sv)
-    return t, BackboneSaved(a0, y0, mean0, rstd0, layers, n, s) if save else None
+        if tap is not None and i in tap:
+            outs[i] = t
+    saved = BackboneSaved(a0, y0, mean0, rstd0, layers, n, s) if save else None
+    if tap is None:
+        return t, saved
+    return t, saved, [outs[i] for i in tap]
 
 
 def backbone_bwd(mod, saved, dt, dtype, on_layer_done=None, rows=None):

@@ -171,6 +171,25 @@ class TransformerEncoder(ABC, torch.nn.Module):
         offsets = self.position_model.draw_offsets(x.shape[0], w // self.patch_size[1], x.device)
         return _BackboneFn.apply(self, x, mask, offsets, compute_dtype(), self._key_ranges(key_ranges, x.shape[0], x.device), *self._param_list)
 
+    @torch.no_grad()
+    def encode_layers(self, x, layers, key_ranges=None):
+        """No-grad forward that returns the output matrices (N*S, model_dim) of the encoder layers `layers` (indices, negative ones counting
+        from the top: -1 is the last layer, whose matrix is encode_tokens' result), in the order asked for.  No input masking; the
+        positional offsets are drawn or injected exactly as in encode_tokens (one draw per call)."""
+        if not x.is_cuda:
+            raise RuntimeError("pero_pretraining_amd backbones run on the GPU only (HIP kernels, no CPU fallback)")
+        tap = []
+        for i in layers:
+            j = int(i) + self.num_blocks if int(i) < 0 else int(i)
+            if not 0 <= j < self.num_blocks:
+                raise ValueError(f"encode_layers: layer {i} of {self.num_blocks}")
+            tap.append(j)
+        w = x.shape[2] if x.dtype == torch.uint8 else x.shape[3]
+        offsets = self.position_model.draw_offsets(x.shape[0], w // self.patch_size[1], x.device)
+        _, _, outs = F.backbone_fwd(self, x, None, offsets, compute_dtype(), False,
+                                    key_ranges=self._key_ranges(key_ranges, x.shape[0], x.device), tap=tap)
+        return outs
+
     def encode_tokens_views(self, views, key_ranges=None):
         """Several equally shaped image batches (the two views of the joint-embedding step) through ONE pass of 2N lines:
         half the launches and twice the rows per product.  The positional offsets are drawn per view, in view order, with the

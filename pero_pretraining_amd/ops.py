@@ -1257,3 +1257,90 @@ def edit_ops(a, a_len, b, b_len, num_classes=None, separators=None, totals=None,
     call("pero_edit_ops", ptr(a), ptr(a_len), ptr(b), ptr(b_len), ptr(is_sep), ptr(counts), ptr(script), ptr(script_len), ptr(a_spans), ptr(b_spans),
          ptr(totals), ptr(confusion), n, La, Lb, num_classes or 0, stream())
     return counts, script, script_len, a_spans, b_spans
+
+
+# ---- latent-target self-distillation (csrc/latent.hip; formulas and summation orders in include/pero_hip.h) ------------------------------
+LATENT_MAX_K = _lib.DEFINES["PERO_LATENT_MAX_K"]
+LATENT_MAX_D = _lib.DEFINES["PERO_LATENT_MAX_D"]
+
+
+def ema_table(entries, device):
+    """entries: [(source tensor or device address, destination offset, count)] -> (table int64 [n][4] = {source address, destination offset,
+    count, first tile} on `device`, total tiles of LAYER_TILE elements).  The table carries its extent (the largest offset + count) as
+    `_pero_extent`, a host integer, so that ema_update can refuse a flat buffer shorter than its table without reading the device."""
+    rows_, tiles = [], 0
+    for src, off, n in entries:
+        if isinstance(src, torch.Tensor):
+            if src.dtype != torch.float32 or not src.is_contiguous() or not src.is_cuda or src.numel() != n:
+                raise TypeError("ema_table: sources are contiguous f32 device tensors of `count` elements")
+            src = src.data_ptr()
+        if off % 8 or off < 0 or n < 1 or src % 4 or src == 0:
+            raise ValueError(f"ema_table: offsets are multiples of 8 elements, sources 4-byte aligned, segments not empty; got offset {off}, count {n}")
+        rows_.append([src, off, n, tiles])
+        tiles += layer_tiles(n)
+    if not rows_ or tiles >= 1 << 31:
+        raise ValueError(f"ema_table: {len(rows_)} segments, {tiles} tiles")
+    table = torch.tensor(rows_, dtype=torch.int64).to(device)
+    table._pero_extent = max(off + n for _, off, n, _ in rows_)
+    return table, tiles
+
+
+def ema_update(avg, table, tiles, w, avg_bf16=None):
+    """avg <- avg + w * (source - avg) over every segment of `table` in one launch, w = (float)(1 - tau); avg_bf16 (may be None) <- the
+    bf16 copy of the new average."""
+    _req_cuda(avg, table, avg_bf16)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous():
+        raise TypeError("ema_update: table is a contiguous int64 [n][4] device tensor (ops.ema_table)")
+    extent = getattr(table, "_pero_extent", None)
+    if extent is None:
+        raise ValueError("ema_update: the table does not come from ops.ema_table (its extent is unknown)")
+    if avg.dtype != torch.float32 or not avg.is_contiguous() or avg.numel() < extent:
+        raise ValueError(f"ema_update: avg is a contiguous f32 buffer of at least {extent} elements")
+    if avg_bf16 is not None and (avg_bf16.dtype != torch.bfloat16 or not avg_bf16.is_contiguous() or avg_bf16.numel() < extent):
+        raise ValueError(f"ema_update: avg_bf16 is a contiguous bf16 buffer of at least {extent} elements")
+    call("pero_ema_update", ptr(avg), ptr(avg_bf16), ptr(table), table.shape[0], int(tiles), float(w), stream())
+    return avg
+
+
+def latent_targets(mats, index, n_pad=None, eps=1e-5):
+    """y (n_pad, d) f32: row i < n is the mean over the K matrices of the row index[i] normalised to zero mean / unit variance over d
+    (a LayerNorm without weights); rows behind n are zero.  mats: K matrices (rows, d), all f32 or all bf16, contiguous."""
+    mats = list(mats)
+    _req_cuda(index, *mats)
+    rows, d = mats[0].shape
+    if any(m.shape != (rows, d) or m.dtype != mats[0].dtype or not m.is_contiguous() for m in mats):
+        raise TypeError("latent_targets: the matrices have one shape and dtype and are contiguous")
+    if index.dtype != torch.int64 or not index.is_contiguous():
+        raise TypeError("latent_targets: index is a contiguous int64 tensor")
+    n = index.numel()
+    n_pad = n if n_pad is None else int(n_pad)
+    y = torch.empty((n_pad, d), device=mats[0].device, dtype=torch.float32)
+    ptrs = (ctypes.c_void_p * len(mats))(*[m.data_ptr() for m in mats])
+    call("pero_latent_targets", ctypes.cast(ptrs, ctypes.c_void_p), len(mats), ptr(index), ptr(y), rows, n, n_pad, d, float(eps), dt(mats[0]), stream())
+    return y
+
+
+def _latent_loss_args(name, pred, y, n):
+    _req_cuda(pred, y)
+    if pred.dim() != 2 or y.shape != pred.shape or y.dtype != torch.float32 or not pred.is_contiguous() or not y.is_contiguous():
+        raise TypeError(f"{name}: pred (n_pad, d) f32 / bf16 and y (n_pad, d) f32, contiguous")
+    if not 0 <= n <= pred.shape[0]:
+        raise ValueError(f"{name}: n = {n} rows of {pred.shape[0]}")
+    return pred.shape
+
+
+def latent_loss_fwd(pred, y, n, beta):
+    """loss (1,) f32 = mean over the first n rows of smooth_l1(pred - y, beta) (beta == 0: the squared error)."""
+    _, d = _latent_loss_args("latent_loss_fwd", pred, y, n)
+    work = torch.empty(max(n, 1), device=pred.device, dtype=torch.float32)
+    loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+    call("pero_latent_loss_fwd", ptr(pred), ptr(y), ptr(work), ptr(loss), n, d, float(beta), dt(pred), stream())
+    return loss
+
+
+def latent_loss_bwd(pred, y, n, beta, dloss=None):
+    """dpred (n_pad, d) in pred's dtype: dloss * l'(pred - y) / (n d) on the first n rows, zero rows behind; dloss: one f32 on the device."""
+    n_pad, d = _latent_loss_args("latent_loss_bwd", pred, y, n)
+    dpred = torch.empty_like(pred)
+    call("pero_latent_loss_bwd", ptr(pred), ptr(y), ptr(dloss), ptr(dpred), n, n_pad, d, float(beta), dt(pred), stream())
+    return dpred

@@ -19,7 +19,13 @@ FusedLAMB and FusedLARS subclass FusedAdam (the flat buffers, the bf16 and trans
 grad_norm / refresh_lowp and the clip are its own) and replace the step's launch by three per group: the update u and the tile sums of
 p^2 and u^2, the trust ratio r = c |p| / |u| of every parameter tensor, and the step with r (csrc/optim_layerwise.hip; formulas in
 include/pero_hip.h).  layerwise_groups(model, weight_decay) builds their usual pair of groups.
+
+WeightEMA keeps an exponential moving average of a module's parameters in a deep copy of it: one flat f32 buffer with FusedAdam's
+layout, one launch per update however many tensors the module has (pero_ema_update, csrc/latent.hip), the bf16 copy written in the same
+launch.  It is the teacher of latent_pretraining and the weight averaging a recogniser is usually evaluated with.
 """
+import copy
+
 import torch
 
 from . import lowp, ops
@@ -406,3 +412,116 @@ def decay_groups(model, weight_decay):
     params = list(model.parameters())
     return [{"params": [p for p in params if p.dim() >= 2], "weight_decay": weight_decay},
             {"params": [p for p in params if p.dim() < 2], "weight_decay": 0.0}]
+
+
+class WeightEMA:
+    """Exponential moving average of `module`'s parameters: avg <- avg + (1 - tau) * (p - avg) per update.
+
+    `.module` is a deep copy of `module` in eval() with requires_grad_(False); its parameters are views into ONE flat f32 buffer (8-element
+    alignment per tensor, as FusedAdam._flatten) and a flat bf16 copy is registered with lowp.put, so a bf16 forward of `.module` reads what
+    the kernel wrote (the kernel does not bump `_version`: without the registration lowp.get would serve stale weights).  update() is one
+    launch plus a copy_ of the persistent buffers (BatchNorm statistics); it never synchronises with the host.  The decay of update k
+    (0-based), in f64 on the host: tau_k = decay_start + (decay - decay_start) * min(k, ramp_updates) / ramp_updates, or simply `decay` with
+    decay_start None or ramp_updates 0.  The source's addresses are checked at every update: the segment table is rebuilt when a parameter's
+    data_ptr() changed (an optimizer flattened the student).  Not a torch Module: a model that owns one moves it in its own _apply (to())."""
+
+    def __init__(self, module, decay=0.999, decay_start=None, ramp_updates=0):
+        if not 0.0 <= decay <= 1.0 or (decay_start is not None and not 0.0 <= decay_start <= 1.0) or ramp_updates < 0:
+            raise ValueError(f"WeightEMA: invalid decay / decay_start / ramp_updates: {decay}, {decay_start}, {ramp_updates}")
+        self.source = module
+        self.decay, self.decay_start, self.ramp_updates = float(decay), None if decay_start is None else float(decay_start), int(ramp_updates)
+        self.n_updates = 0
+        self.module = copy.deepcopy(module).eval().requires_grad_(False)
+        self._flat = self._flat_bf16 = self._table = None
+        self._tiles, self._ptrs = 0, None
+        self.flatten()
+
+    def decay_at(self, k):
+        """tau of update k (0-based), a Python float (f64)."""
+        if self.decay_start is None or self.ramp_updates == 0:
+            return self.decay
+        return self.decay_start + (self.decay - self.decay_start) * min(int(k), self.ramp_updates) / self.ramp_updates
+
+    def flatten(self):
+        """Move the average's parameters into the flat buffers (again after the module moved to another device).  A module that is not on
+        the GPU yet is left as it is: update() needs the GPU and says so."""
+        ps = list(self.module.parameters())
+        self._flat = self._table = self._ptrs = None
+        if not ps or ps[0].device.type != "cuda":
+            return
+        dev = ps[0].device
+        if any(p.dtype != torch.float32 or p.device != dev for p in ps):
+            raise TypeError("WeightEMA: f32 parameters on one device")
+        self._offsets, total = [], 0
+        for p in ps:
+            self._offsets.append(total)
+            total += ((p.numel() + 7) // 8) * 8   # 16-byte aligned bf16 views
+        fp = ops.zeros((total,), dev, torch.float32)
+        flp = ops.zeros((total,), dev, torch.bfloat16)
+        for p, o in zip(ps, self._offsets):
+            fp[o:o + p.numel()].copy_(p.detach().reshape(-1))
+            p.data = fp[o:o + p.numel()].view(p.shape)
+        ops.cast_to_bf16(fp, flp)
+        for p, o in zip(ps, self._offsets):
+            lowp.put(p, flp[o:o + p.numel()].view(p.shape))
+        self._flat, self._flat_bf16 = fp, flp
+
+    def _pairs(self, module):
+        src, avg = list(module.parameters()), list(self.module.parameters())
+        if len(src) != len(avg) or any(a.shape != b.shape for a, b in zip(src, avg)):
+            raise ValueError("WeightEMA: the module's parameters do not match the average's")
+        return src, avg
+
+    def _buffers(self, module):
+        """(average, source) pairs of the persistent buffers (those a state_dict carries)."""
+        mine = dict(self.module.named_buffers())
+        theirs = dict(module.named_buffers())
+        names = [k for k in self.module.state_dict().keys() if k in mine]
+        return [(mine[k], theirs[k]) for k in names]
+
+    @torch.no_grad()
+    def update(self, module=None):
+        module = self.source if module is None else module
+        if self._flat is None:
+            self.flatten()
+            if self._flat is None:
+                raise RuntimeError("WeightEMA needs the parameters on the GPU (move the model first)")
+        src, _ = self._pairs(module)
+        ptrs = [p.data_ptr() for p in src]
+        if ptrs != self._ptrs:
+            if any(p.dtype != torch.float32 or not p.is_contiguous() or p.device != self._flat.device for p in src):
+                raise TypeError("WeightEMA: the source's parameters are contiguous f32 tensors on the average's device")
+            self._table, self._tiles = ops.ema_table([(a, o, p.numel()) for a, o, p in zip(ptrs, self._offsets, src)], self._flat.device)
+            self._ptrs = ptrs
+        ops.ema_update(self._flat, self._table, self._tiles, 1.0 - self.decay_at(self.n_updates), self._flat_bf16)
+        for mine, theirs in self._buffers(module):
+            mine.copy_(theirs)
+        self.n_updates += 1
+
+    @torch.no_grad()
+    def copy_from(self, module=None):
+        """Reset the average to the module's current parameters and buffers (n_updates, and with it the place on the decay ramp, stays)."""
+        module = self.source if module is None else module
+        src, avg = self._pairs(module)
+        for a, p in zip(avg, src):
+            a.copy_(p.detach())
+        for mine, theirs in self._buffers(module):
+            mine.copy_(theirs)
+        self.refresh_lowp()
+
+    def refresh_lowp(self):
+        """Re-cast the bf16 copy after the average was written from outside (copy_from, load_state_dict)."""
+        if self._flat is not None:
+            ops.cast_to_bf16(self._flat, self._flat_bf16)
+
+    def state_dict(self):
+        return {"module": self.module.state_dict(), "n_updates": self.n_updates, "decay": self.decay, "decay_start": self.decay_start,
+                "ramp_updates": self.ramp_updates}
+
+    def load_state_dict(self, state):
+        self.module.load_state_dict(state["module"])   # copy_ into the flat views
+        self.n_updates = int(state["n_updates"])
+        self.decay = float(state["decay"])
+        self.decay_start = None if state["decay_start"] is None else float(state["decay_start"])
+        self.ramp_updates = int(state["ramp_updates"])
+        self.refresh_lowp()
