@@ -330,7 +330,8 @@ int pero_grad_norm_finish(const float* partials, int64_t count, double scale, fl
  * Layout.  A flat f32 buffer holds n_tensors parameter tensors.  table (DEVICE, int64[n_tensors][3]) = {offset, numel, first tile}:
  * every tensor is cut into ceil(numel / PERO_LAYER_TILE) tiles of PERO_LAYER_TILE elements, tile 0 starting AT the tensor's offset and
  * the last one possibly short, so no tile crosses a tensor; first tile = the number of tiles of the tensors in front; total_tiles = the
- * sum.  Offsets are multiples of 8 elements (16-byte aligned f32 AND bf16 tiles) and numel >= 1; the library cannot read the table on
+ * sum.  In this table, in pero_ema_update's and in pero_transpose_multi's, first tile is the LAST column and never decreases from row to
+ * row: a workgroup finds its row by binary search, the last one whose first tile is <= its index (csrc/flat_tiles.hpp).  Offsets are multiples of 8 elements (16-byte aligned f32 AND bf16 tiles) and numel >= 1; the library cannot read the table on
  * the host, so the caller vouches for it.  The layout is a function of the tensor sizes alone.  One workgroup of 256 lanes takes one
  * tile: lane t holds the four 16-byte pieces at elements (k * 256 + t) * 4, k = 0..3, of the tile.
  *

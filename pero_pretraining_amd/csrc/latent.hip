@@ -1,73 +1,33 @@
 // Latent-target self-distillation: the EMA of a whole model in one launch, the normalised layer-averaged targets at the listed rows, and
 // the regression loss (smooth L1 / MSE) with its gradient.  All HBM-bound, no float atomics, every sum in a fixed order.  Formulas,
 // operation order and layouts: include/pero_hip.h ("latent-target self-distillation").
-#include "common.hpp"
-
-#define LT PERO_LAYER_TILE   // elements of a tile = 256 lanes x 4 pieces of 16 bytes
+#include "flat_tiles.hpp"
 
 // ---------------------------------------------------------------------------------------------
-// EMA.  table[s] = {source address, destination offset, count, first tile}; the segment of tile `bid` is the last one whose first tile is
-// <= bid (binary search, as optim_layerwise.hip).  A tile behind its segment's end has count 0 and touches no element.
+// EMA.  table[s] = {source address, destination offset, count, first tile}.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ema_update_k(float* avg, bf16raw* avg_bf16, const long long* table, int n, float w) {
-  const long long bid = blockIdx.x;
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (table[mid * 4 + 3] <= bid) lo = mid; else hi = mid - 1;
-  }
-  const long long local = bid - table[lo * 4 + 3];
-  const long long left = local >= 0 ? table[lo * 4 + 2] - local * LT : 0;
-  const int count = left >= LT ? LT : (left > 0 ? (int)left : 0);
-  const float* src = (const float*)(uintptr_t)table[lo * 4] + local * LT;
-  float* a = avg + table[lo * 4 + 1] + local * LT;
-  bf16raw* ab = avg_bf16 ? avg_bf16 + table[lo * 4 + 1] + local * LT : nullptr;
+  const TileSeg s = tile_segment<4>(table, n, blockIdx.x);
+  const int count = tile_count(table[s.seg * 4 + 2], s.local);
+  const float* src = (const float*)(uintptr_t)table[s.seg * 4] + s.local * LT;
+  float* a = avg + table[s.seg * 4 + 1] + s.local * LT;
+  bf16raw* ab = avg_bf16 ? avg_bf16 + table[s.seg * 4 + 1] + s.local * LT : nullptr;
   const bool vec = (((uintptr_t)src) & 15) == 0;   // uniform over the workgroup: a source that is not 16-byte aligned takes scalar loads
   f4v pp[4], aa[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const int e = (k * 256 + threadIdx.x) * 4;
-    pp[k] = (f4v){0.f, 0.f, 0.f, 0.f};
-    aa[k] = (f4v){0.f, 0.f, 0.f, 0.f};
-    if (e + 4 <= count) {
-      aa[k] = *(const f4v*)(a + e);
-      if (vec) pp[k] = *(const f4v*)(src + e);
-      else { pp[k][0] = src[e]; pp[k][1] = src[e + 1]; pp[k][2] = src[e + 2]; pp[k][3] = src[e + 3]; }
-    } else {
-      for (int j = 0; j < 4; j++)
-        if (e + j < count) { aa[k][j] = a[e + j]; pp[k][j] = src[e + j]; }
-    }
+    aa[k] = load4_tail(a, e, count);
+    pp[k] = load4_tail(src, e, count, vec);
   }
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const int e = (k * 256 + threadIdx.x) * 4;
 #pragma unroll
     for (int j = 0; j < 4; j++) aa[k][j] = aa[k][j] + w * (pp[k][j] - aa[k][j]);
-    if (e + 4 <= count) {
-      *(f4v*)(a + e) = aa[k];
-      if (ab) { uint2 o; o.x = pack2bf(aa[k][0], aa[k][1]); o.y = pack2bf(aa[k][2], aa[k][3]); *(uint2*)(ab + e) = o; }
-    } else {
-      for (int j = 0; j < 4; j++)
-        if (e + j < count) { a[e + j] = aa[k][j]; if (ab) ab[e + j] = f2bf(aa[k][j]); }
-    }
+    store4_tail(a, e, count, aa[k]);
+    if (ab) store4_tail(ab, e, count, aa[k]);
   }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Four consecutive elements as one 16-byte (f32) or 8-byte (bf16) access
-// ---------------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ f4v load4(const T* p);
-template <> __device__ __forceinline__ f4v load4<float>(const float* p) { return *(const f4v*)p; }
-template <> __device__ __forceinline__ f4v load4<bf16raw>(const bf16raw* p) {
-  const uint2 r = *(const uint2*)p;
-  return (f4v){__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
-}
-template <typename T> __device__ __forceinline__ void store4(T* p, f4v v);
-template <> __device__ __forceinline__ void store4<float>(float* p, f4v v) { *(f4v*)p = v; }
-template <> __device__ __forceinline__ void store4<bf16raw>(bf16raw* p, f4v v) {
-  uint2 o;
-  o.x = pack2bf(v[0], v[1]); o.y = pack2bf(v[2], v[3]);
-  *(uint2*)p = o;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -163,20 +123,11 @@ __global__ __launch_bounds__(256) void latent_loss_rows_k(const T* pred, const f
   if (lane == 0) rowsum[i] = s;
 }
 
-// one workgroup: rowsum in index order in f64, 256 contiguous runs and then the run sums (grad_norm_finish_k's order)
+// one workgroup: the row sums in f64 (run_sum_f64)
 __global__ __launch_bounds__(256) void latent_loss_finish_k(const float* rowsum, float* loss, long long n, int d) {
-  __shared__ double runs[256];
-  const long long per = (n + 255) / 256;
-  const long long a = threadIdx.x * per, b = a + per < n ? a + per : n;
-  double t = 0.0;
-  for (long long i = a; i < b; i++) t += (double)rowsum[i];
-  runs[threadIdx.x] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int i = 0; i < 256; i++) s += runs[i];
-    loss[0] = (float)(s / ((double)n * (double)d));
-  }
+  double s[1];
+  run_sum_f64<1, 1>(rowsum, n, s);
+  if (threadIdx.x == 0) loss[0] = (float)(s[0] / ((double)n * (double)d));
 }
 
 template <typename T, bool MSE>

@@ -1,5 +1,5 @@
 // Front end (u8 line images -> patch rows), casts, Adam, row gather / scatter.  All HBM-bound.
-#include "common.hpp"
+#include "flat_tiles.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // patch rows from u8 NHWC line images.  One block = one line x 16 consecutive patches: the
@@ -418,15 +418,14 @@ extern "C" int pero_rowdot_blocks(const void* x, const void* y, float* out, int6
 // Transposed bf16 weight copies, every matrix of a flat buffer in ONE launch.  The input gradient dX = dY W reads W
 // K-contiguous from such a copy ([in][out]) instead of k-major from W itself - the 256x256x64 tile kernels run 10-20 %
 // faster on K-contiguous operands.  table[t] = {src offset, dst offset, rows, cols, first tile}
-// (elements / tiles of 64 x 64); a workgroup finds its matrix by scanning the <= a-few-dozen entries.
+// (elements / tiles of 64 x 64); a workgroup finds its matrix with tile_segment (flat_tiles.hpp).
 // --------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void transpose_multi_k(const bf16raw* src, bf16raw* dst, const long long* table, int n) {
   __shared__ bf16raw tile[64][66];  // pitch 33 dwords: a column walk touches 32 different banks
-  const long long bid = blockIdx.x;
-  int t = 0;
-  while (t + 1 < n && table[(t + 1) * 5 + 4] <= bid) t++;
+  const TileSeg seg = tile_segment<5>(table, n, blockIdx.x);
+  const int t = seg.seg;
   const long long so = table[t * 5], dof = table[t * 5 + 1], rows = table[t * 5 + 2], cols = table[t * 5 + 3];
-  const long long local = bid - table[t * 5 + 4];
+  const long long local = seg.local;
   const long long tiles_c = (cols + 63) / 64;
   const long long r0 = (local / tiles_c) * 64, c0 = (local % tiles_c) * 64;
   const bf16raw* s = src + so;

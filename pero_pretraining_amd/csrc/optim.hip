@@ -1,6 +1,7 @@
 // Adam with torch.optim.Adam's remaining arguments (weight decay coupled / decoupled, amsgrad, maximize) and a fused global-norm
-// clip, plus the two launches that produce that norm on the device.  All HBM-bound; pero_adam_step (misc.hip) stays as it is.
-#include "common.hpp"
+// clip, plus the two launches that produce that norm on the device.  All HBM-bound.  pero_adam_step (misc.hip) is the plain
+// kernel without these arguments: the benchmark times it, and the tests hold adam_ex_k with every flag off to its bits.
+#include "flat_tiles.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // One element, in torch's order (torch/optim/adam.py _single_tensor_adam; clip_grad_norm_ in front of it).  `g` arrives as
@@ -116,16 +117,7 @@ static long long sumsq_blocks(long long n) {
   if (b > SUMSQ_MAX_BLOCKS) b = SUMSQ_MAX_BLOCKS;
   return b < 1 ? 1 : b;
 }
-__device__ __forceinline__ f4v sumsq_piece(const float* x, long long i, long long n) {
-  const long long e = i * 4;
-  if (e + 4 <= n) return *(const f4v*)(x + e);
-  f4v r = {0.f, 0.f, 0.f, 0.f};
-  for (int k = 0; k < 4; k++)
-    if (e + k < n) r[k] = x[e + k];
-  return r;
-}
 __global__ __launch_bounds__(256) void sumsq_partials_k(const float* x, long long n, float* partials) {
-  __shared__ float waves[4];
   const long long nv = (n + 3) >> 2;
   const long long stride = (long long)gridDim.x * 256;
   f4v acc = {0.f, 0.f, 0.f, 0.f};
@@ -135,30 +127,17 @@ __global__ __launch_bounds__(256) void sumsq_partials_k(const float* x, long lon
     for (int k = 0; k < 4; k++) {
       const long long idx = i + k * stride;
       a[k] = (f4v){0.f, 0.f, 0.f, 0.f};
-      if (idx < nv) a[k] = sumsq_piece(x, idx, n);
+      if (idx < nv) a[k] = load4_tail(x, idx * 4, n);
     }
 #pragma unroll
     for (int k = 0; k < 4; k++) acc = acc + a[k] * a[k];
   }
-  float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = ((waves[0] + waves[1]) + waves[2]) + waves[3];
+  block_fold<1>({acc}, partials + blockIdx.x);
 }
 __global__ __launch_bounds__(256) void grad_norm_finish_k(const float* partials, long long count, double scale, float* norm) {
-  __shared__ double runs[256];
-  const long long per = (count + 255) / 256;
-  const long long a = threadIdx.x * per, b = a + per < count ? a + per : count;
-  double t = 0.0;
-  for (long long i = a; i < b; i++) t += (double)partials[i];
-  runs[threadIdx.x] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double total = 0.0;
-    for (int i = 0; i < 256; i++) total += runs[i];
-    norm[0] = (float)(scale * sqrt(total));
-  }
+  double total[1];
+  run_sum_f64<1, 1>(partials, count, total);
+  if (threadIdx.x == 0) norm[0] = (float)(scale * sqrt(total[0]));
 }
 
 extern "C" int pero_sumsq_num_partials(int64_t n) { return n > 0 ? (int)sumsq_blocks(n) : 0; }

@@ -2,14 +2,10 @@
 // group and step without float atomics, without waiting between workgroups and without a buffer for the update u (stage 2 computes it again
 // from the same operands with the same operations: -ffp-contract=off, the same bits).  All HBM-bound.  Formulas, operation order and the
 // tile / partial layout: include/pero_hip.h ("layer-wise optimizers").
-#include "common.hpp"
-
-#define LT PERO_LAYER_TILE   // elements of a tile = 256 lanes x 4 pieces of 16 bytes
+#include "flat_tiles.hpp"
 
 // ---------------------------------------------------------------------------------------------
-// Workgroup -> tile.  table[t] = {offset, numel, first tile}; the tensor of tile `bid` is the last one whose first tile is <= bid (binary
-// search: a model has a few hundred tensors).  A tile that lies behind its tensor's end (a table and a tile count that do not belong
-// together) has count 0 and touches no element.
+// Workgroup -> tile.  table[t] = {offset, numel, first tile}.  Piece k of lane t holds the elements (k * 256 + t) * 4 .. + 3 of the tile.
 // ---------------------------------------------------------------------------------------------
 struct LayerTile {
   long long start;   // first element in the flat buffer
@@ -17,51 +13,12 @@ struct LayerTile {
   int tensor;
 };
 __device__ __forceinline__ LayerTile layer_tile(const long long* table, int n, long long bid) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (table[mid * 3 + 2] <= bid) lo = mid; else hi = mid - 1;
-  }
-  const long long local = bid - table[lo * 3 + 2];
-  const long long left = local >= 0 ? table[lo * 3 + 1] - local * LT : 0;
+  const TileSeg s = tile_segment<3>(table, n, bid);
   LayerTile r;
-  r.tensor = lo;
-  r.start = table[lo * 3] + local * LT;
-  r.count = left >= LT ? LT : (left > 0 ? (int)left : 0);
+  r.tensor = s.seg;
+  r.start = table[s.seg * 3] + s.local * LT;
+  r.count = tile_count(table[s.seg * 3 + 1], s.local);
   return r;
-}
-// piece k of lane t holds the elements (k * 256 + t) * 4 .. + 3 of the tile; only a tensor's last tile has a piece cut short (scalar tail)
-__device__ __forceinline__ f4v tile_load(const float* x, int e, int count) {
-  if (e + 4 <= count) return *(const f4v*)(x + e);
-  f4v r = {0.f, 0.f, 0.f, 0.f};
-  for (int j = 0; j < 4; j++)
-    if (e + j < count) r[j] = x[e + j];
-  return r;
-}
-__device__ __forceinline__ void tile_store(float* x, int e, int count, f4v val) {
-  if (e + 4 <= count) { *(f4v*)(x + e) = val; return; }
-  for (int j = 0; j < 4; j++)
-    if (e + j < count) x[e + j] = val[j];
-}
-__device__ __forceinline__ void tile_store_bf16(bf16raw* x, int e, int count, f4v val) {
-  if (e + 4 <= count) { uint2 o; o.x = pack2bf(val[0], val[1]); o.y = pack2bf(val[2], val[3]); *(uint2*)(x + e) = o; return; }
-  for (int j = 0; j < 4; j++)
-    if (e + j < count) x[e + j] = f2bf(val[j]);
-}
-// the two sums of a tile: the lane's four running sums folded ((a0+a1)+(a2+a3)), the wave butterfly, the four waves in order - the fixed
-// places of sumsq_partials_k (optim.hip)
-__device__ __forceinline__ void tile_sums(f4v ap, f4v au, float* out) {
-  __shared__ float waves[2][4];
-  float sp = (ap[0] + ap[1]) + (ap[2] + ap[3]);
-  float su = (au[0] + au[1]) + (au[2] + au[3]);
-  sp = wave_sum(sp);
-  su = wave_sum(su);
-  if ((threadIdx.x & 63) == 0) { waves[0][threadIdx.x >> 6] = sp; waves[1][threadIdx.x >> 6] = su; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    out[0] = ((waves[0][0] + waves[0][1]) + waves[0][2]) + waves[0][3];
-    out[1] = ((waves[1][0] + waves[1][1]) + waves[1][2]) + waves[1][3];
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -93,8 +50,8 @@ __global__ __launch_bounds__(256) void lamb_stage1_k(const float* p, const float
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const int e = (k * 256 + threadIdx.x) * 4;
-    pp[k] = tile_load(p + T.start, e, T.count); gg[k] = tile_load(g + T.start, e, T.count);
-    mm[k] = tile_load(m + T.start, e, T.count); vv[k] = tile_load(v + T.start, e, T.count);
+    pp[k] = load4_tail(p + T.start, e, T.count); gg[k] = load4_tail(g + T.start, e, T.count);
+    mm[k] = load4_tail(m + T.start, e, T.count); vv[k] = load4_tail(v + T.start, e, T.count);
   }
   f4v ap = {0.f, 0.f, 0.f, 0.f}, au = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -112,10 +69,10 @@ __global__ __launch_bounds__(256) void lamb_stage1_k(const float* p, const float
       au[j] = au[j] + (live ? u * u : 0.f);
       mm[k][j] = me; vv[k][j] = ve;
     }
-    tile_store(m + T.start, e, T.count, mm[k]);
-    tile_store(v + T.start, e, T.count, vv[k]);
+    store4_tail(m + T.start, e, T.count, mm[k]);
+    store4_tail(v + T.start, e, T.count, vv[k]);
   }
-  tile_sums(ap, au, partials + 2 * (long long)blockIdx.x);
+  block_fold<2>({ap, au}, partials + 2 * (long long)blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void lamb_stage2_k(float* p, const float* m, const float* v, bf16raw* pb, const long long* table, int n,
@@ -126,15 +83,15 @@ __global__ __launch_bounds__(256) void lamb_stage2_k(float* p, const float* m, c
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const int e = (k * 256 + threadIdx.x) * 4;
-    pp[k] = tile_load(p + T.start, e, T.count); mm[k] = tile_load(m + T.start, e, T.count); vv[k] = tile_load(v + T.start, e, T.count);
+    pp[k] = load4_tail(p + T.start, e, T.count); mm[k] = load4_tail(m + T.start, e, T.count); vv[k] = load4_tail(v + T.start, e, T.count);
   }
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const int e = (k * 256 + threadIdx.x) * 4;
 #pragma unroll
     for (int j = 0; j < 4; j++) pp[k][j] = pp[k][j] - step * lamb_update(pp[k][j], mm[k][j], vv[k][j], rbc1, rsb2, eps, wd);
-    tile_store(p + T.start, e, T.count, pp[k]);
-    if (pb) tile_store_bf16(pb + T.start, e, T.count, pp[k]);
+    store4_tail(p + T.start, e, T.count, pp[k]);
+    if (pb) store4_tail(pb + T.start, e, T.count, pp[k]);
   }
 }
 
@@ -147,7 +104,7 @@ __global__ __launch_bounds__(256) void lars_stage1_k(const float* p, const float
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const int e = (k * 256 + threadIdx.x) * 4;
-    pp[k] = tile_load(p + T.start, e, T.count); gg[k] = tile_load(g + T.start, e, T.count);
+    pp[k] = load4_tail(p + T.start, e, T.count); gg[k] = load4_tail(g + T.start, e, T.count);
   }
   f4v ap = {0.f, 0.f, 0.f, 0.f}, au = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -162,7 +119,7 @@ __global__ __launch_bounds__(256) void lars_stage1_k(const float* p, const float
       au[j] = au[j] + (live ? u * u : 0.f);
     }
   }
-  tile_sums(ap, au, partials + 2 * (long long)blockIdx.x);
+  block_fold<2>({ap, au}, partials + 2 * (long long)blockIdx.x);
 }
 
 template <bool MAXI, bool CLIP>
@@ -176,7 +133,7 @@ __global__ __launch_bounds__(256) void lars_stage2_k(float* p, const float* g, f
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const int e = (k * 256 + threadIdx.x) * 4;
-    pp[k] = tile_load(p + T.start, e, T.count); gg[k] = tile_load(g + T.start, e, T.count); bb[k] = tile_load(buf + T.start, e, T.count);
+    pp[k] = load4_tail(p + T.start, e, T.count); gg[k] = load4_tail(g + T.start, e, T.count); bb[k] = load4_tail(buf + T.start, e, T.count);
   }
 #pragma unroll
   for (int k = 0; k < 4; k++) {
@@ -187,27 +144,20 @@ __global__ __launch_bounds__(256) void lars_stage2_k(float* p, const float* g, f
       bb[k][j] = mu * bb[k][j] + r * u;
       pp[k][j] = pp[k][j] - lr * bb[k][j];
     }
-    tile_store(buf + T.start, e, T.count, bb[k]);
-    tile_store(p + T.start, e, T.count, pp[k]);
-    if (pb) tile_store_bf16(pb + T.start, e, T.count, pp[k]);
+    store4_tail(buf + T.start, e, T.count, bb[k]);
+    store4_tail(p + T.start, e, T.count, pp[k]);
+    if (pb) store4_tail(pb + T.start, e, T.count, pp[k]);
   }
 }
 
-// One workgroup per tensor: its tiles' partials in index order in f64, contiguous runs per lane and then the run sums (grad_norm_finish_k).
+// One workgroup per tensor: the two sums of its tiles' partials in f64 (run_sum_f64).
 __global__ __launch_bounds__(256) void layer_ratio_finish_k(const float* partials, const long long* table, float c, int adapt, float* stats) {
-  __shared__ double runs[2][256];
   const long long t = blockIdx.x;
   const long long first = table[t * 3 + 2], count = (table[t * 3 + 1] + LT - 1) / LT;
-  const long long per = (count + 255) / 256;
-  const long long a = threadIdx.x * per, b = a + per < count ? a + per : count;
-  double tp = 0.0, tu = 0.0;
-  for (long long i = a; i < b; i++) { tp += (double)partials[2 * (first + i)]; tu += (double)partials[2 * (first + i) + 1]; }
-  runs[0][threadIdx.x] = tp; runs[1][threadIdx.x] = tu;
-  __syncthreads();
+  double s[2];   // sum p^2, sum u^2
+  run_sum_f64<2, 2>(partials + 2 * first, count, s);
   if (threadIdx.x == 0) {
-    double sp = 0.0, su = 0.0;
-    for (int i = 0; i < 256; i++) { sp += runs[0][i]; su += runs[1][i]; }
-    const float pn = (float)sqrt(sp), un = (float)sqrt(su);
+    const float pn = (float)sqrt(s[0]), un = (float)sqrt(s[1]);
     float r = 1.0f;
     if (adapt && pn > 0.f && un > 0.f) r = (c * pn) / un;   // a NaN norm fails both comparisons: r = 1, the NaN reaches p through u
     stats[t * 3] = pn; stats[t * 3 + 1] = un; stats[t * 3 + 2] = r;

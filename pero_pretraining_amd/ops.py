@@ -429,13 +429,41 @@ def colsum(x, out):
     return out
 
 
+def _tile_table(rows, tiles_of, extent_of, device, refuse=None):
+    """The device table of a kernel that walks segments in tiles (csrc/flat_tiles.hpp): `rows` with the running first tile appended as
+    the last column -> (int64 table on `device`, total tiles).  tiles_of(row) and extent_of(row) give a row's tile count and the end of the
+    elements it addresses; the largest end is the table's `_pero_extent`, a host integer, so that a wrapper can refuse a flat buffer shorter
+    than its table without reading the device.  refuse: (function name, noun) of the ValueError for an empty table or one of 2^31 tiles or
+    more (None: the launch refuses it)."""
+    table, tiles = [], 0
+    for row in rows:
+        table.append([*row, tiles])
+        tiles += tiles_of(row)
+    if refuse is not None and (not table or tiles >= 1 << 31):
+        raise ValueError(f"{refuse[0]}: {len(table)} {refuse[1]}, {tiles} tiles")
+    extent = max((extent_of(row) for row in rows), default=0)
+    table = torch.tensor(table, dtype=torch.int64).to(device)
+    table._pero_extent = extent
+    return table, tiles
+
+
+def _table_check(name, table, columns, made_by, flat=()):
+    """A table of _tile_table with `columns` columns; flat: the buffers it indexes (None allowed).  Returns the extent."""
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != columns or not table.is_contiguous():
+        raise TypeError(f"{name}: table is a contiguous int64 [n][{columns}] device tensor (ops.{made_by})")
+    extent = getattr(table, "_pero_extent", None)
+    if extent is None:
+        raise ValueError(f"{name}: the table does not come from ops.{made_by} (its extent is unknown)")
+    for t in flat:
+        if t is not None and t.numel() < extent:
+            raise ValueError(f"{name}: a flat buffer of {t.numel()} elements is shorter than the table's extent {extent}")
+    return extent
+
+
 def transpose_table(entries, device):
     """entries: [(src offset, dst offset, rows, cols)] -> (device table for transpose_multi, total 64x64 tiles)."""
-    rows_, tiles = [], 0
-    for so, do, r, c in entries:
-        rows_.append([so, do, r, c, tiles])
-        tiles += ((r + 63) // 64) * ((c + 63) // 64)
-    return torch.tensor(rows_, dtype=torch.int64).to(device), tiles
+    return _tile_table([list(e) for e in entries], lambda e: ((e[2] + 63) // 64) * ((e[3] + 63) // 64),
+                       lambda e: max(e[0], e[1]) + e[2] * e[3], device)
 
 
 def transpose_multi(src, dst, table, tiles):
@@ -563,35 +591,23 @@ def layer_table(entries, device):
     """entries: [(offset, numel)] of the tensors of a flat buffer -> (table int64 [n][3] = {offset, numel, first tile} on `device`,
     total tiles).  A function of the sizes alone.  The table carries its extent (the largest offset + numel) as `_pero_extent`, a host
     integer, so that the wrappers below can refuse a flat buffer that is shorter than its table without reading the device."""
-    rows_, tiles = [], 0
+    rows_ = []
     for off, n in entries:
         if off % 8 or off < 0 or n < 1:
             raise ValueError(f"layer_table: offsets are multiples of 8 elements and tensors are not empty, got offset {off}, numel {n}")
-        rows_.append([off, n, tiles])
-        tiles += layer_tiles(n)
-    if not rows_ or tiles >= 1 << 31:
-        raise ValueError(f"layer_table: {len(rows_)} tensors, {tiles} tiles")
-    table = torch.tensor(rows_, dtype=torch.int64).to(device)
-    table._pero_extent = max(off + n for off, n, _ in rows_)
-    return table, tiles
+        rows_.append([off, n])
+    return _tile_table(rows_, lambda r: layer_tiles(r[1]), lambda r: r[0] + r[1], device, refuse=("layer_table", "tensors"))
 
 
 def _layer_check(name, table, tiles, f32, flat=(), **sized):
     """f32: every f32 argument (None allowed); flat: those of them, and the bf16 copy, that the table indexes."""
     _req_cuda(table, *f32, *flat)
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or not table.is_contiguous():
-        raise TypeError(f"{name}: table is a contiguous int64 [n][3] device tensor (ops.layer_table)")
+    _table_check(name, table, 3, "layer_table", flat)
     if any(t is not None and (t.dtype != torch.float32 or not t.is_contiguous()) for t in f32):
         raise TypeError(f"{name}: contiguous f32 tensors")
     for what, (t, need) in sized.items():
         if t.numel() != need:
             raise ValueError(f"{name}: {what} holds {t.numel()} elements, the table needs {need}")
-    extent = getattr(table, "_pero_extent", None)
-    if extent is None:
-        raise ValueError(f"{name}: the table does not come from ops.layer_table (its extent is unknown)")
-    for t in flat:
-        if t is not None and t.numel() < extent:
-            raise ValueError(f"{name}: a flat buffer of {t.numel()} elements is shorter than the table's extent {extent}")
     return table.shape[0], int(tiles)
 
 
@@ -1268,7 +1284,7 @@ def ema_table(entries, device):
     """entries: [(source tensor or device address, destination offset, count)] -> (table int64 [n][4] = {source address, destination offset,
     count, first tile} on `device`, total tiles of LAYER_TILE elements).  The table carries its extent (the largest offset + count) as
     `_pero_extent`, a host integer, so that ema_update can refuse a flat buffer shorter than its table without reading the device."""
-    rows_, tiles = [], 0
+    rows_ = []
     for src, off, n in entries:
         if isinstance(src, torch.Tensor):
             if src.dtype != torch.float32 or not src.is_contiguous() or not src.is_cuda or src.numel() != n:
@@ -1276,24 +1292,15 @@ def ema_table(entries, device):
             src = src.data_ptr()
         if off % 8 or off < 0 or n < 1 or src % 4 or src == 0:
             raise ValueError(f"ema_table: offsets are multiples of 8 elements, sources 4-byte aligned, segments not empty; got offset {off}, count {n}")
-        rows_.append([src, off, n, tiles])
-        tiles += layer_tiles(n)
-    if not rows_ or tiles >= 1 << 31:
-        raise ValueError(f"ema_table: {len(rows_)} segments, {tiles} tiles")
-    table = torch.tensor(rows_, dtype=torch.int64).to(device)
-    table._pero_extent = max(off + n for _, off, n, _ in rows_)
-    return table, tiles
+        rows_.append([src, off, n])
+    return _tile_table(rows_, lambda r: layer_tiles(r[2]), lambda r: r[1] + r[2], device, refuse=("ema_table", "segments"))
 
 
 def ema_update(avg, table, tiles, w, avg_bf16=None):
     """avg <- avg + w * (source - avg) over every segment of `table` in one launch, w = (float)(1 - tau); avg_bf16 (may be None) <- the
     bf16 copy of the new average."""
     _req_cuda(avg, table, avg_bf16)
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous():
-        raise TypeError("ema_update: table is a contiguous int64 [n][4] device tensor (ops.ema_table)")
-    extent = getattr(table, "_pero_extent", None)
-    if extent is None:
-        raise ValueError("ema_update: the table does not come from ops.ema_table (its extent is unknown)")
+    extent = _table_check("ema_update", table, 4, "ema_table")
     if avg.dtype != torch.float32 or not avg.is_contiguous() or avg.numel() < extent:
         raise ValueError(f"ema_update: avg is a contiguous f32 buffer of at least {extent} elements")
     if avg_bf16 is not None and (avg_bf16.dtype != torch.bfloat16 or not avg_bf16.is_contiguous() or avg_bf16.numel() < extent):

@@ -31,6 +31,25 @@ import torch
 from . import lowp, ops
 
 
+def _flat_storage(ps, dev):
+    """The parameters `ps` moved into ONE flat f32 buffer on `dev`, every tensor at an offset rounded up to 8 elements (16-byte aligned bf16
+    views), and its bf16 copy registered view by view with lowp.put.  Both buffers are zero-filled (the library's linear fill: torch's
+    elementwise one runs at a third of its rate), so the pads between the tensors are zeros.  Returns (offsets, total, f32, bf16)."""
+    offs, total = [], 0
+    for p in ps:
+        offs.append(total)
+        total += ((p.numel() + 7) // 8) * 8
+    fp = ops.zeros((total,), dev, torch.float32)
+    flp = ops.zeros((total,), dev, torch.bfloat16)
+    for p, o in zip(ps, offs):
+        fp[o:o + p.numel()].copy_(p.detach().reshape(-1))
+        p.data = fp[o:o + p.numel()].view(p.shape)
+    ops.cast_to_bf16(fp, flp)
+    for p, o in zip(ps, offs):
+        lowp.put(p, flp[o:o + p.numel()].view(p.shape))
+    return offs, total, fp, flp
+
+
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False, *,
                  decoupled_weight_decay=False, max_grad_norm=None):
@@ -54,9 +73,8 @@ class FusedAdam(torch.optim.Optimizer):
 
     @staticmethod
     def _moments(total, dev, group):
-        """The state buffers of one group beside p and g.  A subclass with other state allocates its own here and must then override
-        whatever reads the ones it leaves None: FusedLARS keeps v = None, and state_dict, load_state_dict and _vmax of this class would
-        fail on such an entry - it overrides the first two and never has amsgrad."""
+        """The state buffers of one group beside p and g.  A subclass with other state allocates its own here and names it in _STATE:
+        FusedLARS keeps v = None, which its map never reads, and never has amsgrad (_vmax)."""
         return dict(m=ops.zeros((total,), dev, torch.float32), v=ops.zeros((total,), dev, torch.float32),
                     vmax=ops.zeros((total,), dev, torch.float32) if group["amsgrad"] else None)
 
@@ -70,23 +88,13 @@ class FusedAdam(torch.optim.Optimizer):
             dev = ps[0].device
             if dev.type != "cuda":
                 raise RuntimeError("FusedAdam needs the parameters on the GPU (move the model first)")
-            offs, total = [], 0
-            for p in ps:
-                offs.append(total)
-                total += ((p.numel() + 7) // 8) * 8  # 16-byte aligned bf16 views
-            fp = ops.zeros((total,), dev, torch.float32)   # (the library's linear fill: torch's elementwise one runs at a third of its rate)
+            offs, total, fp, flp = _flat_storage(ps, dev)
             fg = ops.zeros((total,), dev, torch.float32)
-            flp = torch.empty(total, device=dev, dtype=torch.bfloat16)
             for p, o in zip(ps, offs):
                 n = p.numel()
-                fp[o:o + n].copy_(p.detach().reshape(-1))
                 if p.grad is not None:
                     fg[o:o + n].copy_(p.grad.reshape(-1))
-                p.data = fp[o:o + n].view(p.shape)
                 p.grad = fg[o:o + n].view(p.shape)
-            ops.cast_to_bf16(fp, flp)
-            for p, o in zip(ps, offs):
-                lowp.put(p, flp[o:o + p.numel()].view(p.shape))
             # transposed bf16 copies of the matrices (lowp.weight_t: the input-gradient products read them), same offsets
             mats = [(o, o, p.shape[0], p.numel() // p.shape[0]) for p, o in zip(ps, offs) if p.dim() >= 2]
             flpt, ttable, ttiles = None, None, 0
@@ -139,6 +147,17 @@ class FusedAdam(torch.optim.Optimizer):
     # group, 'max_exp_avg_sq'; the group keys carry the real hyper-parameters), so optimizer state moves between this class and
     # torch.optim.Adam / AdamW (the reference's optimizer, masked_pretraining/train.py:146) in both directions.  The reference itself
     # never saves it.
+    # state-dict key -> flat-buffer key (a subclass with other state replaces the maps); _STATE_STEP: the entries carry a 'step'
+    _STATE = {"exp_avg": "m", "exp_avg_sq": "v"}
+    _STATE_AMSGRAD = {"max_exp_avg_sq": "vmax"}
+    _STATE_STEP = True
+
+    def _state_keys(self, group, f):
+        if not group.get("amsgrad"):
+            return self._STATE
+        self._vmax(f)
+        return {**self._STATE, **self._STATE_AMSGRAD}
+
     def state_dict(self):
         state, groups, idx = {}, [], 0
         for group, f in zip(self.param_groups, self._flat):
@@ -147,11 +166,9 @@ class FusedAdam(torch.optim.Optimizer):
             for p in group["params"]:
                 if id(p) in offs and f["step"] > 0:
                     o, n = offs[id(p)], p.numel()
-                    state[idx] = {"step": torch.tensor(float(f["step"])),
-                                  "exp_avg": f["m"][o:o + n].view(p.shape).clone(),
-                                  "exp_avg_sq": f["v"][o:o + n].view(p.shape).clone()}
-                    if group["amsgrad"]:
-                        state[idx]["max_exp_avg_sq"] = self._vmax(f)[o:o + n].view(p.shape).clone()
+                    state[idx] = {"step": torch.tensor(float(f["step"]))} if self._STATE_STEP else {}
+                    for key, buf in self._state_keys(group, f).items():
+                        state[idx][key] = f[buf][o:o + n].view(p.shape).clone()
                 ids.append(idx)
                 idx += 1
             g = {k: v for k, v in group.items() if k != "params"}
@@ -172,25 +189,34 @@ class FusedAdam(torch.optim.Optimizer):
             if f is None:
                 continue
             offs = {id(p): o for p, o in zip(f["params"], f["offsets"])}
-            f["m"].zero_(); f["v"].zero_()
-            if group["amsgrad"]:
-                self._vmax(f).zero_()
-            else:
+            if not group.get("amsgrad"):
                 f["vmax"] = None
-            steps = set()
+            keys = self._state_keys(group, f)
+            for buf in keys.values():
+                f[buf].zero_()
+            steps, loaded = set(), False
             for p, idx in zip(group["params"], saved["params"]):
                 st = state_dict["state"].get(idx)
                 if st is None or id(p) not in offs:
                     continue
                 o, n = offs[id(p)], p.numel()
-                f["m"][o:o + n].copy_(st["exp_avg"].reshape(-1))
-                f["v"][o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
-                if group["amsgrad"]:  # a state saved without amsgrad starts its running maximum at v, where the next step's max() puts it anyway
-                    f["vmax"][o:o + n].copy_(st.get("max_exp_avg_sq", st["exp_avg_sq"]).reshape(-1))
-                steps.add(int(float(st["step"])))
-            if len(steps) > 1:
-                raise ValueError(f"FusedAdam keeps one step counter per group, got {sorted(steps)}")
-            f["step"] = steps.pop() if steps else 0
+                for key, buf in keys.items():
+                    if key in self._STATE_AMSGRAD:   # a state saved without amsgrad starts its running maximum at v, where the next step's max() puts it anyway
+                        val = st.get(key, st["exp_avg_sq"])
+                    else:                            # torch.optim.Adam's entries are complete; SGD's may be empty, or hold None before the first step
+                        val = st[key] if self._STATE_STEP else st.get(key)
+                    if val is not None:
+                        f[buf][o:o + n].copy_(val.reshape(-1))
+                        loaded = True
+                if self._STATE_STEP:
+                    steps.add(int(float(st["step"])))
+            f["step"] = self._step_after_load(steps, loaded)
+
+    @staticmethod
+    def _step_after_load(steps, loaded):
+        if len(steps) > 1:
+            raise ValueError(f"FusedAdam keeps one step counter per group, got {sorted(steps)}")
+        return steps.pop() if steps else 0
 
     @staticmethod
     def _vmax(f):
@@ -360,43 +386,13 @@ class FusedLARS(_LayerWise):
         ops.lars_stage2(f["p"], f["g"], f["m"], f["lp"], f["ltable"], f["ltiles"], f["stats"], group["lr"], group["momentum"], **clip)
 
     # ---- checkpointing: torch.optim.SGD's layout (per-parameter 'momentum_buffer', no step counter)
-    def state_dict(self):
-        state, groups, idx = {}, [], 0
-        for group, f in zip(self.param_groups, self._flat):
-            offs = {id(p): o for p, o in zip(f["params"], f["offsets"])} if f is not None else {}
-            ids = []
-            for p in group["params"]:
-                if id(p) in offs and f["step"] > 0:
-                    o, n = offs[id(p)], p.numel()
-                    state[idx] = {"momentum_buffer": f["m"][o:o + n].view(p.shape).clone()}
-                ids.append(idx)
-                idx += 1
-            g = {k: v for k, v in group.items() if k != "params"}
-            g["params"] = ids
-            groups.append(g)
-        return {"state": state, "param_groups": groups}
+    _STATE = {"momentum_buffer": "m"}
+    _STATE_AMSGRAD = {}
+    _STATE_STEP = False
 
-    def load_state_dict(self, state_dict):
-        groups = state_dict["param_groups"]
-        if len(groups) != len(self.param_groups):
-            raise ValueError("loaded state dict has a different number of parameter groups")
-        for group, saved, f in zip(self.param_groups, groups, self._flat):
-            if len(saved["params"]) != len(group["params"]):
-                raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
-            for k, v in saved.items():
-                if k != "params":
-                    group[k] = v
-            if f is None:
-                continue
-            offs = {id(p): o for p, o in zip(f["params"], f["offsets"])}
-            f["m"].zero_()
-            f["step"] = 0   # counts this object's steps only: the update does not depend on it
-            for p, idx in zip(group["params"], saved["params"]):
-                buf = (state_dict["state"].get(idx) or {}).get("momentum_buffer")
-                if buf is not None and id(p) in offs:
-                    o = offs[id(p)]
-                    f["m"][o:o + p.numel()].copy_(buf.reshape(-1))
-                    f["step"] = 1
+    @staticmethod
+    def _step_after_load(steps, loaded):
+        return int(loaded)   # counts this object's steps only: the update does not depend on it
 
 
 def layerwise_groups(model, weight_decay):
@@ -418,7 +414,7 @@ class WeightEMA:
     """Exponential moving average of `module`'s parameters: avg <- avg + (1 - tau) * (p - avg) per update.
 
     `.module` is a deep copy of `module` in eval() with requires_grad_(False); its parameters are views into ONE flat f32 buffer (8-element
-    alignment per tensor, as FusedAdam._flatten) and a flat bf16 copy is registered with lowp.put, so a bf16 forward of `.module` reads what
+    alignment per tensor, FusedAdam's layout) and a flat bf16 copy is registered with lowp.put, so a bf16 forward of `.module` reads what
     the kernel wrote (the kernel does not bump `_version`: without the registration lowp.get would serve stale weights).  update() is one
     launch plus a copy_ of the persistent buffers (BatchNorm statistics); it never synchronises with the host.  The decay of update k
     (0-based), in f64 on the host: tau_k = decay_start + (decay - decay_start) * min(k, ramp_updates) / ramp_updates, or simply `decay` with
@@ -452,19 +448,7 @@ class WeightEMA:
         dev = ps[0].device
         if any(p.dtype != torch.float32 or p.device != dev for p in ps):
             raise TypeError("WeightEMA: f32 parameters on one device")
-        self._offsets, total = [], 0
-        for p in ps:
-            self._offsets.append(total)
-            total += ((p.numel() + 7) // 8) * 8   # 16-byte aligned bf16 views
-        fp = ops.zeros((total,), dev, torch.float32)
-        flp = ops.zeros((total,), dev, torch.bfloat16)
-        for p, o in zip(ps, self._offsets):
-            fp[o:o + p.numel()].copy_(p.detach().reshape(-1))
-            p.data = fp[o:o + p.numel()].view(p.shape)
-        ops.cast_to_bf16(fp, flp)
-        for p, o in zip(ps, self._offsets):
-            lowp.put(p, flp[o:o + p.numel()].view(p.shape))
-        self._flat, self._flat_bf16 = fp, flp
+        self._offsets, _, self._flat, self._flat_bf16 = _flat_storage(ps, dev)
 
     def _pairs(self, module):
         src, avg = list(module.parameters()), list(self.module.parameters())

@@ -82,6 +82,29 @@ def test_ema_update_is_bit_equal_to_the_f32_formula(ops):
     print(f"\npero_ema_update: max |got - numpy f32| = 0 over {total} elements, {tiles} tiles (bound: bit equality)")
 
 
+@pytest.mark.parametrize("sizes", [[4097], [4097, 7], [4097, 7, 4096]], ids=lambda s: f"{len(s)}seg")
+def test_ema_update_finds_the_segment_in_tables_of_one_two_and_three(ops, sizes):
+    """Tables of 1, 2 and 3 segments (first tiles 0 / 0, 2 / 0, 2, 3) are where a wrong midpoint of the segment search first shows:
+    every segment against the f32 formula, bit for bit, and zero pads."""
+    g = gen(4, len(sizes))
+    offs = [sum(((m + 7) // 8) * 8 for m in sizes[:i]) for i in range(len(sizes))]
+    total = offs[-1] + ((sizes[-1] + 7) // 8) * 8
+    srcs = [torch.randn(n, generator=g).cuda() for n in sizes]
+    avg0 = torch.zeros(total)
+    for o, n in zip(offs, sizes):
+        avg0[o:o + n] = torch.randn(n, generator=g)
+    table, tiles = ops.ema_table([(s, o, s.numel()) for s, o in zip(srcs, offs)], torch.device("cuda"))
+    assert tiles == sum((n + 4095) // 4096 for n in sizes)
+    avg, lp = avg0.cuda(), torch.zeros(total, device="cuda", dtype=BF16)
+    w = f32r(1.0 - 0.99)
+    ops.ema_update(avg, table, tiles, w, lp)
+    ref = avg0.numpy().copy()
+    for s, o in zip(srcs, offs):
+        ref[o:o + s.numel()] = LR.ema_update_f32(ref[o:o + s.numel()], s.cpu().numpy(), w)   # the pads of avg0 are zeros and stay untouched
+    assert torch.equal(avg.cpu(), torch.from_numpy(ref))
+    assert torch.equal(lp.cpu(), torch.from_numpy(ref).to(BF16))
+
+
 # ------------------------------------------------------------------------------------------------ pero_latent_targets
 def _targets_case(d, K, n, dtype):
     g = gen(d, K, n, dtype == F32)

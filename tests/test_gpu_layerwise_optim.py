@@ -268,6 +268,23 @@ def test_same_bits_twice_and_alone(ops, inputs, kind):
         assert torch.equal(alone.get(alone.m)[0], together.get(together.m)[t]), n
 
 
+@pytest.mark.parametrize("kind", ["lamb", "lars"])
+def test_tables_of_one_two_and_three_tensors_give_the_bits_of_the_eight(ops, inputs, kind):
+    """Tables of 1, 2 and 3 tensors (4097 / 4097, 7 / 4097, 7, 4096 elements: first tiles 0 / 0, 2 / 0, 2, 3) are where a wrong midpoint
+    of the tile search first shows: every tensor's p, m and stats row are those of the same tensor in the run over all eight."""
+    params, grads = inputs
+    together = Flat(ops, SIZES, params)
+    stats = together.step(kind, grads[0], 1, lr_of(kind, 1), wd=0.01, maximize=False, clip=False)
+    all_p, all_m = together.get(together.p), together.get(together.m)
+    for sizes in ([4097], [4097, 7], [4097, 7, 4096]):
+        which = [SIZES.index(n) for n in sizes]
+        few = Flat(ops, sizes, [params[t] for t in which])
+        st = few.step(kind, [grads[0][t] for t in which], 1, lr_of(kind, 1), wd=0.01, maximize=False, clip=False)
+        for i, (t, p, m) in enumerate(zip(which, few.get(few.p), few.get(few.m))):
+            assert torch.equal(st[i], stats[t]), (sizes, i, st[i].tolist(), stats[t].tolist())
+            assert torch.equal(p, all_p[t]) and torch.equal(m, all_m[t]), (sizes, i)
+
+
 # ---- 4.-6. the optimizer classes -------------------------------------------------------------------------------------------------------
 SHAPES = [(24, 32), (24,), (7, 5, 3), (1,), (64, 65)]
 
