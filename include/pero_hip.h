@@ -838,6 +838,37 @@ int pero_latent_loss_fwd(const void* pred, const float* y, float* work, float* l
 int pero_latent_loss_bwd(const void* pred, const float* y, const float* dloss, void* dpred, int64_t n, int64_t n_pad, int64_t d, float beta,
                          int dtype, void* stream);
 
+/* ---- Barlow Twins loss (csrc/barlow.hip; BarlowTwinsLoss) -----------------------------------------------
+ * z1[r] = x[ix[r]], z2[r] = y[iy[r]], r < n: the n paired rows of the two views (x, y: rows of d values of `dtype`; ix, iy: DEVICE int64
+ * lists, unique within a list).  Per view and column j: mu_j = mean_r z[r][j], var_j = mean_r (z[r][j] - mu_j)^2 (biased),
+ * rstd_j = 1 / sqrt(var_j + eps), zh[r][j] = (z[r][j] - mu_j) * rstd_j.  With c = zh1^T zh2 / n (the caller's pero_gemm):
+ *   on = sum_i (c_ii - 1)^2,  off = sum_{i != j} c_ij^2,  loss = on + lambda * off,  G_ii = 2 (c_ii - 1) / n,  G_ij = 2 lambda c_ij / n,
+ * d zh1 = zh2 G^T, d zh2 = zh1 G (pero_gemm again), and per view with a_j = sum_r dzh[r][j], b_j = sum_r dzh[r][j] zh[r][j]:
+ *   dz[r][j] = g * rstd_j * (dzh[r][j] - a_j / n - zh[r][j] * b_j / n).
+ * Every per-view array holds view 1 then view 2: mean, rstd, a, b are f32 [2][d]; zh, dzh are `dtype` [2][n_pad][d], n_pad >= n.
+ * No atomics: the column reductions leave one partial per column and tile of PERO_BARLOW_TILE_ROWS rows, merged in tile order in
+ * f64 ((count, mean, M2) partials and the parallel-variance formula for the statistics), so a second call gives the same bits.
+ * part: f32 workspace of PERO_BARLOW_PART(n, d) values.  16-byte accesses when d % 8 == 0 and every row is 16-byte aligned, element
+ * by element otherwise; 1 <= d <= 65535 * 256.
+ *
+ * pero_barlow_stats           mean, rstd of both views in one pass over the gathered rows
+ * pero_barlow_standardize     zh, rows n <= r < n_pad explicit zeros (every element of zh is written)
+ * pero_barlow_corr            one read of c (f32 d x d): out = {loss, on, off} and G (`dtype`, d x d); rowpart: f32 [2][d] scratch
+ * pero_barlow_bwd_stats       a, b of both views in one pass over dzh and zh
+ * pero_barlow_standardize_bwd dz STORED to dx[ix[r]] / dy[iy[r]] (other rows untouched); g: DEVICE pointer to one f32 (null = 1) */
+#define PERO_BARLOW_TILE_ROWS 1024
+#define PERO_BARLOW_PART(n, d) (4 * (((n) + PERO_BARLOW_TILE_ROWS - 1) / PERO_BARLOW_TILE_ROWS) * (d))
+int pero_barlow_stats(const void* x, const int64_t* ix, const void* y, const int64_t* iy, float* part, float* mean, float* rstd,
+                      int64_t n, int64_t d, float eps, int dtype, void* stream);
+int pero_barlow_standardize(const void* x, const int64_t* ix, const void* y, const int64_t* iy, const float* mean, const float* rstd,
+                            void* zh, int64_t n, int64_t n_pad, int64_t d, int dtype, void* stream);
+int pero_barlow_corr(const float* c, void* G, float* rowpart, float* out, int64_t d, int64_t n, float lambda, int dtype, void* stream);
+int pero_barlow_bwd_stats(const void* dzh, const void* zh, float* part, float* a, float* b, int64_t n, int64_t n_pad, int64_t d,
+                          int dtype, void* stream);
+int pero_barlow_standardize_bwd(const void* dzh, const void* zh, const float* rstd, const float* a, const float* b, const int64_t* ix,
+                                const int64_t* iy, void* dx, void* dy, const float* g, int64_t n, int64_t n_pad, int64_t d, int dtype,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """VICRegLoss and NTXentLoss with the interface of the reference's joint_embedding_pretraining/losses.py,
 computed by HIP kernels: boolean-mask row selections become index gathers, the covariance (a D x D SYRK)
-and the per-line similarity matrices run on pero_gemm, the statistics are f32 reductions."""
+and the per-line similarity matrices run on pero_gemm, the statistics are f32 reductions.  BarlowTwinsLoss (no
+reference counterpart) takes the same inputs: csrc/barlow.hip around three pero_gemm products."""
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -168,6 +169,93 @@ class VICRegLoss(torch.nn.Module):
         if not (dist.is_available() and dist.is_initialized()):
             raise RuntimeError("VICRegLoss(global_statistics=True) needs an initialised torch.distributed process group")
         return self.process_group if self.process_group is not None else dist.group.WORLD
+
+
+class _BarlowFn(torch.autograd.Function):
+    """Barlow Twins as one autograd node (csrc/barlow.hip): two passes over the paired rows (statistics; gather +
+    standardise), the D x D cross-correlation on pero_gemm, one pass over it (loss parts and the backward operand G); backward: two products,
+    one pass for the column sums a, b of both views, one pass that stores the input gradients.  Saved: zh, rstd, G and the index lists."""
+
+    @staticmethod
+    def forward(ctx, x, y, ix, iy, lam, eps, dtype):
+        D = x.shape[-1]
+        stacked = y is None   # x = both views stacked along dim 0: one tensor, ONE gradient (as in _VICRegFn)
+        if stacked:
+            xy = _rows(x, dtype)
+            x2, y2 = xy[:xy.shape[0] // 2], xy[xy.shape[0] // 2:]
+        else:
+            x2, y2 = _rows(x, dtype), _rows(y, dtype)
+        if ix.numel() != iy.numel():
+            raise RuntimeError(f"The size of tensor a ({ix.numel()}) must match the size of tensor b ({iy.numel()}) "
+                               "at non-singleton dimension 0")  # the text of VICRegLoss for the same masks
+        n = ix.numel()
+        if n == 0:
+            raise ValueError("BarlowTwinsLoss: the shift masks select no pair of positions (no position with shift mask == 1)")
+        n_pad = ((n + 63) // 64) * 64
+        mean, rstd = ops.barlow_stats(x2, ix, y2, iy, eps)
+        zh = ops.barlow_standardize(x2, ix, y2, iy, mean, rstd, n_pad)
+        # c = zh1^T zh2 / n: kept apart from the statistics, so that an exchange over ranks can be put between them later
+        if dtype == torch.bfloat16:
+            c = ops.zeros((D, D), x2.device, torch.float32)   # split-K into a zeroed f32 matrix, as VICReg's SYRK
+            ops.gemm(zh[0], zh[1], out=c, trans_a=True, trans_b=True, alpha=1.0 / n, atomic=True, k_split=0)
+        else:
+            c = ops.gemm(zh[0], zh[1], trans_a=True, trans_b=True, alpha=1.0 / n, out_dtype=torch.float32)
+        out, G = ops.barlow_corr(c, n, lam, dtype)
+        ctx.save_for_backward(zh, rstd, G, ix, iy)
+        ctx.meta = (x.shape, None if stacked else y.shape, x2.shape, y2.shape, n)
+        loss, on, off = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(on, off)
+        return loss, on, off
+
+    @staticmethod
+    def backward(ctx, g, _gon, _goff):
+        zh, rstd, G, ix, iy = ctx.saved_tensors
+        xs, ys, rows_shape, rows_shape_y, n = ctx.meta
+        gdev = g.detach().reshape(1).to(torch.float32)
+        dzh = torch.empty_like(zh)
+        ops.gemm(zh[1], G, out=dzh[0])                 # d zh1 = zh2 G^T
+        ops.gemm(zh[0], G, out=dzh[1], trans_b=True)   # d zh2 = zh1 G
+        a, b = ops.barlow_bwd_stats(dzh, zh, n)
+        if ys is None:   # stacked views: one gradient buffer, the two halves are the views' gradients
+            dxy = ops.zeros((2 * rows_shape[0], rows_shape[1]), zh.device, zh.dtype)
+            dx, dy = dxy[:rows_shape[0]], dxy[rows_shape[0]:]
+        else:
+            dx = ops.zeros(rows_shape, zh.device, zh.dtype)
+            dy = ops.zeros(rows_shape_y, zh.device, zh.dtype)
+        ops.barlow_standardize_bwd(dzh, zh, rstd, a, b, ix, iy, dx, dy, gdev)
+        if ys is None:
+            return (dxy.view(xs), None) + (None,) * 5
+        return (dx.view(xs), dy.view(ys)) + (None,) * 5
+
+
+class BarlowTwinsLoss(torch.nn.Module):
+    """Barlow Twins (Zbontar et al., 2021; no reference counterpart) on the pairs of VICReg's invariance term: the k-th position with
+    shift_masks1 == 1 pairs with the k-th position with shift_masks2 == 1 (2 in a shift mask stays out), n pairs z1, z2 of shape (n, D).
+    Each view is standardised along the rows like BatchNorm1d without affine (biased variance, eps inside the root):
+        zh = (z - mean_r z) / sqrt(var_r z + eps),   c = zh1^T zh2 / n   (D x D),
+        loss = sum_i (c_ii - 1)^2 + lambda_offdiag * sum_{i != j} c_ij^2.
+    Returns {"loss", "loss.on_diagonal", "loss.off_diagonal"}; the two parts are unweighted, detached and not differentiable.
+
+    The image masks are accepted for the interface of the other losses and are NOT used.  Unequal pair counts raise VICRegLoss's
+    RuntimeError, no pair at all raises ValueError; both are decided from the lengths of the index lists, which the host knows.
+    Positions outside the pairs receive exact zero gradients.  The statistics and c are those of the rows THIS process sees: under
+    data-parallel training they are per rank, like VICRegLoss's default (no counterpart of its global_statistics)."""
+
+    def __init__(self, lambda_offdiag=0.0051, eps=1e-5):
+        super().__init__()
+        self.lambda_offdiag = lambda_offdiag
+        self.eps = eps
+
+    def forward(self, x, y, image_masks1, image_masks2, shift_masks1, shift_masks2):
+        if not x.is_cuda:
+            raise RuntimeError("pero_pretraining_amd losses run on the GPU only (HIP kernels, no CPU fallback)")
+        ix, iy = _nz(shift_masks1, x.device), _nz(shift_masks2, x.device)
+        loss, on, off = _BarlowFn.apply(x, y, ix, iy, float(self.lambda_offdiag), float(self.eps), compute_dtype())
+        return {"loss": loss, "loss.on_diagonal": on, "loss.off_diagonal": off}
+
+    def forward_stacked(self, xy, image_masks1, image_masks2, shift_masks1, shift_masks2):
+        """forward(xy[:n], xy[n:], ...) for the two views stacked along dim 0: same values, ONE gradient tensor for xy (see VICRegLoss)."""
+        return self.forward(xy, None, image_masks1, image_masks2, shift_masks1, shift_masks2)
 
 
 def ntxent_slots_host(image_masks1, image_masks2, shift_masks1, shift_masks2):

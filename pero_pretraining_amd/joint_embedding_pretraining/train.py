@@ -8,15 +8,16 @@ from ..common.lr_scheduler import WarmupSchleduler
 from ..masked_pretraining.train import resume, save_model  # noqa: F401  (same semantics)
 from ..optim import FusedAdam, FusedAdamW, FusedLAMB, FusedLARS, decay_groups, layerwise_groups
 from .batch_operator import BatchOperator
-from .losses import NTXentLoss, VICRegLoss
+from .losses import BarlowTwinsLoss, NTXentLoss, VICRegLoss
 from .model import JointEmbeddingTransformerEncoder, init_backbone, init_head
 from .tester import Tester
 from .trainer import Trainer
 
 
 def init_model(device, backbone_definition, head_definition, loss_type="vicreg", path=None, global_statistics=False,
-               ntxent_apply_masks=False):
-    """train.py:54-72.  ntxent_apply_masks: NTXentLoss(apply_masks=True), the form of NT-Xent that takes collated batches (losses.py)."""
+               ntxent_apply_masks=False, barlow_lambda=0.0051):
+    """train.py:54-72.  ntxent_apply_masks: NTXentLoss(apply_masks=True), the form of NT-Xent that takes collated batches (losses.py).
+    loss_type="barlow" (no reference counterpart): BarlowTwinsLoss(lambda_offdiag=barlow_lambda)."""
     backbone = init_backbone(backbone_definition)
     head = init_head(head_definition)
     if loss_type == "vicreg":
@@ -24,6 +25,8 @@ def init_model(device, backbone_definition, head_definition, loss_type="vicreg",
         loss = VICRegLoss(global_statistics=global_statistics)
     elif loss_type == "ntxent":
         loss = NTXentLoss(apply_masks=ntxent_apply_masks)
+    elif loss_type == "barlow":
+        loss = BarlowTwinsLoss(lambda_offdiag=barlow_lambda)
     else:
         raise ValueError(f"Unknown loss type: {loss_type}")
     model = JointEmbeddingTransformerEncoder(backbone, head, loss)

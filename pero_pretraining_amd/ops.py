@@ -786,6 +786,59 @@ def vicreg_cov(cov, cvar, m, wv, wc, dtype):
     return G, loss
 
 
+BARLOW_TILE_ROWS = _lib.DEFINES["PERO_BARLOW_TILE_ROWS"]
+
+
+def barlow_part_elems(n, d):
+    """f32 elements of the Barlow Twins column reductions' workspace: the header's PERO_BARLOW_PART(n, d)."""
+    return 4 * ((n + BARLOW_TILE_ROWS - 1) // BARLOW_TILE_ROWS) * d
+
+
+def barlow_stats(x, ix, y, iy, eps):
+    """(mean, rstd), f32 (2, d): the column statistics of the rows x[ix] (view 1) and y[iy] (view 2), biased variance."""
+    n, d = ix.numel(), x.shape[-1]
+    part = torch.empty(barlow_part_elems(n, d), device=x.device, dtype=torch.float32)
+    mean = torch.empty((2, d), device=x.device, dtype=torch.float32)
+    rstd = torch.empty((2, d), device=x.device, dtype=torch.float32)
+    call("pero_barlow_stats", ptr(x), ptr(ix), ptr(y), ptr(iy), ptr(part), ptr(mean), ptr(rstd), n, d, float(eps), dt(x), stream())
+    return mean, rstd
+
+
+def barlow_standardize(x, ix, y, iy, mean, rstd, n_pad):
+    """zh (2, n_pad, d): the standardised rows of both views, rows behind ix.numel() zero."""
+    n, d = ix.numel(), x.shape[-1]
+    zh = torch.empty((2, n_pad, d), device=x.device, dtype=x.dtype)
+    call("pero_barlow_standardize", ptr(x), ptr(ix), ptr(y), ptr(iy), ptr(mean), ptr(rstd), ptr(zh), n, n_pad, d, dt(x), stream())
+    return zh
+
+
+def barlow_corr(c, n, lambda_offdiag, dtype):
+    """(out, G): out f32 (3,) = loss, on-diagonal part, off-diagonal part of the cross-correlation c (d, d) f32; G (d, d) of `dtype`."""
+    d = c.shape[0]
+    G = torch.empty((d, d), device=c.device, dtype=dtype)
+    rowpart = torch.empty(2 * d, device=c.device, dtype=torch.float32)
+    out = torch.empty(3, device=c.device, dtype=torch.float32)
+    call("pero_barlow_corr", ptr(c), ptr(G), ptr(rowpart), ptr(out), d, n, float(lambda_offdiag), dt(dtype), stream())
+    return out, G
+
+
+def barlow_bwd_stats(dzh, zh, n):
+    """(a, b), f32 (2, d): column sums of dzh and of dzh * zh over the first n rows of each view."""
+    _, n_pad, d = zh.shape
+    part = torch.empty(barlow_part_elems(n, d), device=zh.device, dtype=torch.float32)
+    a = torch.empty((2, d), device=zh.device, dtype=torch.float32)
+    b = torch.empty((2, d), device=zh.device, dtype=torch.float32)
+    call("pero_barlow_bwd_stats", ptr(dzh), ptr(zh), ptr(part), ptr(a), ptr(b), n, n_pad, d, dt(zh), stream())
+    return a, b
+
+
+def barlow_standardize_bwd(dzh, zh, rstd, a, b, ix, iy, dx, dy, g):
+    """dx[ix[r]], dy[iy[r]] = the gradient rows of the standardisation (stored; the other rows of dx, dy are left as they are)."""
+    _, n_pad, d = zh.shape
+    call("pero_barlow_standardize_bwd", ptr(dzh), ptr(zh), ptr(rstd), ptr(a), ptr(b), ptr(ix), ptr(iy), ptr(dx), ptr(dy), ptr(g),
+         ix.numel(), n_pad, d, dt(zh), stream())
+
+
 def scatter_add_rows_scaled(src, index, dst, g):
     if index.numel():
         call("pero_scatter_add_rows_scaled", ptr(src), ptr(index), ptr(dst), ptr(g), index.numel(), dst.shape[-1], dt(src), stream())
