@@ -869,6 +869,43 @@ int pero_barlow_standardize_bwd(const void* dzh, const void* zh, const float* rs
                                 const int64_t* iy, void* dx, void* dy, const float* g, int64_t n, int64_t n_pad, int64_t d, int dtype,
                                 void* stream);
 
+/* ---- VGG tokenizer front end (csrc/conv.hip; models/autoencoders.py VGGEncoder) ---------------------------
+ * Halo layout: an activation of N images, H x W pixels, C channels is stored NHWC with a one-pixel border, (N, H + 2, W + 2, C) values
+ * of `dtype`, and read as R = N (H + 2)(W + 2) rows of C.  Border ("halo") pixels hold zeros: they are the convolution's padding.
+ * Every entry point below WRITES the zeros of its output's halo; none reads or writes outside the N (H + 2)(W + 2) C values of a
+ * buffer: loads are guarded, so PERO_CONV_SLACK_ROWS, the spare rows a caller has to leave in front of and behind a buffer, is 0.
+ *
+ * pero_conv3x3       Conv2d(Cin -> Cout, kernel 3, stride 1, padding 1) + bias + activation.  x: halo layout with Cin channels;
+ *                    w: the weight REPACKED to [Cout][ky][kx][Cin] (`dtype`); bias: f32 [Cout] or null; y: halo layout with Cout channels:
+ *                      y[r][co] = act(sum_{ky, kx, ci} x[r + (ky - 1)(W + 2) + (kx - 1)][ci] * w[co][ky][kx][ci] + bias[co])   interior rows r
+ *                      y[r][co] = 0                                                                                        halo rows r
+ *                    act: PERO_CONV_ACT_NONE, _RELU (max(v, 0)), _LEAKY_RELU (v > 0 ? v : v * slope).  f32 accumulation in a fixed order,
+ *                    one rounding of the output.  128-row tiles on the matrix pipe when Cin is a multiple of 8 (PERO_BF16:
+ *                    v_mfma_f32_32x32x16_bf16) or of 4 (PERO_F32: v_mfma_f32_32x32x2_f32, exact f32 products and sums, no sum of more than
+ *                    a tap's terms in one chain); other channel counts take a plain FMA kernel (exact f32 as well, no speed target) - so
+ *                    the caller pads the first layer's 3 channels with zeros (pero_image_to_halo's C_pad; zero weights behind them).
+ *                    Any N, H, W, Cin, Cout >= 1.  x, w, y 16-byte aligned, y != x.  The im2col matrix is never formed.
+ * pero_image_to_halo src -> dst (halo layout, C_pad >= C channels, the channels C .. C_pad - 1 zeros).  PERO_IMAGE_U8_NHWC: uint8
+ *                    (N, H, W, C), dst = value / 255 (the f64 quotient rounded once to f32, then to `dtype`).  PERO_IMAGE_F32_NCHW:
+ *                    f32 (N, C, H, W), dst = value.  One 16-byte store per pixel when C_pad values are 16 bytes.
+ * pero_maxpool_nhwc  MaxPool2d(kernel = stride = (ph, pw)), ph, pw in {1, 2}, H % ph == 0, W % pw == 0, over the interior of x (halo
+ *                    layout, C channels), then, where a and b (f32 [C]) are given, y = max * a[c] + b[c] (an eval-mode BatchNorm2d; a may be
+ *                    negative, so it is applied after the maximum).  token_rows 0: y in halo layout (N, H / ph + 2, W / pw + 2, C).
+ *                    token_rows 1: y (N * W / pw, (H / ph) * C): row n * (W / pw) + xo holds that column's H / ph pixels top to bottom - the A
+ *                    operand of the (h, 1) aggregation convolution as one pero_gemm with K = h * C.  16-byte accesses when C % 8 == 0. */
+#define PERO_CONV_SLACK_ROWS 0
+#define PERO_CONV_ACT_NONE 0
+#define PERO_CONV_ACT_RELU 1
+#define PERO_CONV_ACT_LEAKY_RELU 2
+#define PERO_IMAGE_U8_NHWC 0
+#define PERO_IMAGE_F32_NCHW 1
+int pero_conv3x3(const void* x, const void* w, const float* bias, void* y, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
+                 int act, float slope, int dtype, void* stream);
+int pero_image_to_halo(const void* src, void* dst, int64_t N, int64_t H, int64_t W, int64_t C, int64_t C_pad, int src_kind, int dtype,
+                       void* stream);
+int pero_maxpool_nhwc(const void* x, void* y, const float* a, const float* b, int64_t N, int64_t H, int64_t W, int64_t C, int ph, int pw,
+                      int token_rows, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1404,3 +1404,117 @@ def latent_loss_bwd(pred, y, n, beta, dloss=None):
     dpred = torch.empty_like(pred)
     call("pero_latent_loss_bwd", ptr(pred), ptr(y), ptr(dloss), ptr(dpred), n, n_pad, d, float(beta), dt(pred), stream())
     return dpred
+
+
+# ---- VGG tokenizer front end (csrc/conv.hip): activations in halo layout (N, H + 2, W + 2, C) --------------------------
+CONV_SLACK_ROWS = _lib.DEFINES["PERO_CONV_SLACK_ROWS"]
+CONV_ACTIVATIONS = {"none": _lib.DEFINES["PERO_CONV_ACT_NONE"], "relu": _lib.DEFINES["PERO_CONV_ACT_RELU"],
+                    "leaky_relu": _lib.DEFINES["PERO_CONV_ACT_LEAKY_RELU"]}
+
+
+def halo_buffer(n, h, w, c, dtype, device):
+    """Uninitialised activation buffer in halo layout, (n, h + 2, w + 2, c), 16-byte aligned, with the header's PERO_CONV_SLACK_ROWS spare
+    rows of c values in front of it and behind it (the kernels guard their loads, so that is 0 rows today)."""
+    if min(n, h, w, c) < 1:
+        raise ValueError(f"halo_buffer: n, h, w, c = {n}, {h}, {w}, {c} must all be >= 1")
+    rows, slack = n * (h + 2) * (w + 2), CONV_SLACK_ROWS * (w + 3)
+    esz = torch.empty((), dtype=dtype).element_size()
+    front = -(-slack * c * esz // 16) * 16 // esz           # whole 16-byte units, so the first row stays aligned
+    flat = torch.empty(front + (rows + slack) * c, device=device, dtype=dtype)
+    return flat[front:front + rows * c].view(n, h + 2, w + 2, c)
+
+
+def _halo_check(name, x, what="x"):
+    _req_cuda(x)
+    if x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3 or not x.is_contiguous() or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{name}: {what} must be a contiguous f32 / bf16 halo-layout tensor (N, H + 2, W + 2, C), got {tuple(x.shape)} {x.dtype}")
+    n, hp, wp, c = x.shape
+    return n, hp - 2, wp - 2, c
+
+
+def conv3x3_pack_weight(weight, dtype, cin_pad=None):
+    """Conv2d weight (Cout, Cin, 3, 3) -> the kernels' layout (Cout, 3, 3, cin_pad or Cin) in `dtype`, contiguous, zeros behind Cin (done
+    once per checkpoint load).  `cin_pad`: the channel count of an input padded with zero channels (conv_channel_pad)."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError(f"conv3x3_pack_weight: weight must be (Cout, Cin, 3, 3), got {tuple(weight.shape)}")
+    packed = weight.detach().permute(0, 2, 3, 1).to(dtype)
+    if cin_pad is not None:
+        if cin_pad < weight.shape[1]:
+            raise ValueError(f"conv3x3_pack_weight: cin_pad = {cin_pad} is below Cin = {weight.shape[1]}")
+        packed = torch.nn.functional.pad(packed, (0, cin_pad - weight.shape[1]))
+    return packed.contiguous()
+
+
+def conv_channel_pad(c, dtype):
+    """Channel count to pad a layer's input to so that pero_conv3x3 takes its tile kernel: the next multiple of 8 (bf16) or 4 (f32)."""
+    unit = 8 if dtype == torch.bfloat16 else 4
+    return -(-c // unit) * unit
+
+
+def conv3x3(x, w, bias=None, activation="none", slope=0.01, out=None):
+    """y = act(conv3x3(x) + bias), stride 1, padding 1.  x: halo layout (N, H + 2, W + 2, Cin); w: packed weight (Cout, 3, 3, Cin) of x's
+    dtype (conv3x3_pack_weight); bias: f32 (Cout,) or None; activation: "none", "relu" or "leaky_relu" (with `slope`).  Returns the
+    halo-layout output (N, H + 2, W + 2, Cout), halo pixels zero."""
+    n, h, wd, cin = _halo_check("conv3x3", x)
+    _req_cuda(w, bias)
+    if w.dim() != 4 or tuple(w.shape[1:]) != (3, 3, cin) or w.dtype != x.dtype or not w.is_contiguous():
+        raise ValueError(f"conv3x3: w must be a contiguous packed weight (Cout, 3, 3, {cin}) of {x.dtype}, got {tuple(w.shape)} {w.dtype}")
+    cout = w.shape[0]
+    if bias is not None and (tuple(bias.shape) != (cout,) or bias.dtype != torch.float32 or not bias.is_contiguous()):
+        raise ValueError(f"conv3x3: bias must be f32 ({cout},), got {tuple(bias.shape)} {bias.dtype}")
+    if activation not in CONV_ACTIVATIONS:
+        raise ValueError(f"conv3x3: activation {activation!r} is not one of {sorted(CONV_ACTIVATIONS)}")
+    if out is None:
+        out = halo_buffer(n, h, wd, cout, x.dtype, x.device)
+    elif tuple(out.shape) != (n, h + 2, wd + 2, cout) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError(f"conv3x3: out must be contiguous {(n, h + 2, wd + 2, cout)} of {x.dtype}, got {tuple(out.shape)} {out.dtype}")
+    call("pero_conv3x3", ptr(x), ptr(w), ptr(bias), ptr(out), n, h, wd, cin, cout, CONV_ACTIVATIONS[activation], float(slope), dt(x), stream())
+    return out
+
+
+def image_to_halo(images, dtype, channels=None, out=None):
+    """Line images -> the first layer's input, halo layout (N, H + 2, W + 2, channels or C) of `dtype`, the channels behind C zeros.
+    uint8 (N, H, W, C) as BatchCreator delivers it is divided by 255 (autoencoders/batch_operator.py:14); float32 (N, C, H, W), as that
+    batch operator builds it, is taken as it is."""
+    _req_cuda(images)
+    if images.dim() != 4 or not images.is_contiguous() or images.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"image_to_halo: images must be contiguous uint8 (N, H, W, C) or float32 (N, C, H, W), got {tuple(images.shape)} {images.dtype}")
+    if images.dtype == torch.uint8:
+        (n, h, w, c), kind = images.shape, _lib.DEFINES["PERO_IMAGE_U8_NHWC"]
+    else:
+        (n, c, h, w), kind = images.shape, _lib.DEFINES["PERO_IMAGE_F32_NCHW"]
+    cp = c if channels is None else int(channels)
+    if cp < c:
+        raise ValueError(f"image_to_halo: channels = {cp} is below the images' {c}")
+    if out is None:
+        out = halo_buffer(n, h, w, cp, dtype, images.device)
+    elif tuple(out.shape) != (n, h + 2, w + 2, cp) or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError(f"image_to_halo: out must be contiguous {(n, h + 2, w + 2, cp)} of {dtype}, got {tuple(out.shape)} {out.dtype}")
+    call("pero_image_to_halo", ptr(images), ptr(out), n, h, w, c, cp, kind, dt(dtype), stream())
+    return out
+
+
+def maxpool_nhwc(x, pool, a=None, b=None, token_rows=False, out=None):
+    """MaxPool2d(kernel = stride = pool) of the halo-layout x (N, H + 2, W + 2, C), pool in {(2, 2), (2, 1), (1, 2), (1, 1)}, then
+    y = max * a[c] + b[c] where a, b (f32 (C,)) are given.  Returns halo layout (N, H / ph + 2, W / pw + 2, C) or, with token_rows, the
+    matrix (N * W / pw, (H / ph) * C) whose row n * (W / pw) + t holds column t's pixels top to bottom."""
+    n, h, w, c = _halo_check("maxpool_nhwc", x)
+    ph, pw = (int(p) for p in pool)
+    if ph not in (1, 2) or pw not in (1, 2):
+        raise ValueError(f"maxpool_nhwc: pool {tuple(pool)} is not one of (2, 2), (2, 1), (1, 2), (1, 1)")
+    if h % ph or w % pw:
+        raise ValueError(f"maxpool_nhwc: H = {h}, W = {w} are not divisible by the pool {(ph, pw)}")
+    if (a is None) != (b is None):
+        raise ValueError("maxpool_nhwc: the affine needs both a and b")
+    for name, t in (("a", a), ("b", b)):
+        _req_cuda(t)
+        if t is not None and (tuple(t.shape) != (c,) or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"maxpool_nhwc: {name} must be f32 ({c},), got {tuple(t.shape)} {t.dtype}")
+    ho, wo = h // ph, w // pw
+    shape = (n * wo, ho * c) if token_rows else (n, ho + 2, wo + 2, c)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=x.dtype) if token_rows else halo_buffer(n, ho, wo, c, x.dtype, x.device)
+    elif tuple(out.shape) != shape or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError(f"maxpool_nhwc: out must be contiguous {shape} of {x.dtype}, got {tuple(out.shape)} {out.dtype}")
+    call("pero_maxpool_nhwc", ptr(x), ptr(out), ptr(a), ptr(b), n, h, w, c, ph, pw, int(bool(token_rows)), dt(x), stream())
+    return out

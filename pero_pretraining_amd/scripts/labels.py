@@ -4,15 +4,19 @@ tokenizer's nearest-code indices (VQ-VAE, scripts/produce_vqvae_labels.py:27-46)
 `scripts/convert_gt_to_lmdb.py` turns into the LMDB records the training `DatasetLMDB` reads.
 
 The search runs in the HIP argmin kernel (no (M, K) distance matrix; `models/autoencoders.py`); what travels to the
-host per line is the 8-byte index of each valid position.  The encoder that produces the features (a VGG stack in the
-reference) is the caller's: `encode(images) -> (N, D, 1, T)` or `(N, D, T)` float tensor on the device."""
+host per line is the 8-byte index of each valid position.  `encode(images) -> (N, D, 1, T)` or `(N, D, T)` float tensor on
+the device is any callable; the reference's VGG stack is `models.autoencoders.VGGEncoder` (HIP convolution kernels), so with
+`tokenizer = init_tokenizer(...)` the whole path from uint8 line images to the label file stays on the device:
+`compute_labels(tokenizer.encode, tokenizer, dataset)`, `compute_features(tokenizer.encoder, dataset)`,
+`compute_kmeans_labels(tokenizer.encoder, centroids, dataset, path)` - each with BatchCreator's uint8 batches as they are, or with
+the float batches of the reference's autoencoders.BatchOperator."""
 import json
 
 import numpy as np
 import torch
 
 from .. import ops
-from ..models.autoencoders import kmeans_labels
+from ..models.autoencoders import VGGEncoder, VQVAETokenizer, kmeans_labels
 
 
 # ---- text / record formats ------------------------------------------------------------------------------------------
@@ -61,6 +65,17 @@ def convert_labels_file(input_path, put, offset=0):
 
 
 # ---- label computation ------------------------------------------------------------------------------------------------
+def init_tokenizer(device, encoder_definition=None, num_embeddings=1024, embeddings_dim=512, path=None):
+    """autoencoders/model.py:3-19 + scripts/common.py init_model for the label-producing half of a VQ-VAE: a `VQVAETokenizer` around
+    `VGGEncoder(**encoder_definition)` (the reference's defaults when None), with the checkpoint at `path` loaded (strictly, its
+    `decoder.*` entries left out), in eval mode on `device`."""
+    encoder = VGGEncoder(**(encoder_definition or {}))
+    tokenizer = VQVAETokenizer(encoder, num_embeddings=num_embeddings, embeddings_dim=embeddings_dim)
+    if path is not None:
+        tokenizer.load(path)
+    return tokenizer.to(device).eval()
+
+
 def _valid_positions(batch, n, t):
     masks = batch["image_masks"]
     masks = masks.cpu().numpy() if isinstance(masks, torch.Tensor) else np.asarray(masks)
