@@ -2,27 +2,11 @@
 // passes around the three products, which run on pero_gemm.  Both views go through every launch (blockIdx.z / blockIdx.y = view).  Column
 // statistics are reduced without atomics: a row tile of PERO_BARLOW_TILE_ROWS rows leaves one partial per column, a finishing launch merges
 // the partials in tile order in f64 - a second run on the same input gives the same bits.
-#include "losses_common.hpp"
+#include "dispatch.hpp"
+#include "rows.hpp"
 
 #define TR PERO_BARLOW_TILE_ROWS
-
-// 8 consecutive columns col .. col + 7 of a row of d columns: one 16-byte (bf16) / two 16-byte (f32) accesses, or element by element with
-// the columns behind d left out (loads give 0 there)
-template <typename T, bool V8>
-__device__ __forceinline__ void ld8(const T* row, int col, int d, float (&v)[8]) {
-  if (V8) { load8<T>(row + col, v); return; }
-#pragma unroll
-  for (int e = 0; e < 8; e++) v[e] = col + e < d ? Elem<T>::ld(row + col + e) : 0.f;
-}
-
-template <typename T, bool V8>
-__device__ __forceinline__ void st8(T* row, int col, int d, const float (&v)[8]) {
-  if (V8) { store8<T>(row + col, v); return; }
-#pragma unroll
-  for (int e = 0; e < 8; e++)
-    if (col + e < d) Elem<T>::st(row + col + e, v[e]);
-}
-#define RB 64   // rows of a workgroup of the two row-wise kernels: 8 per lane, four in flight
+#define RB 64  // rows of a workgroup of the two row-wise kernels: 8 per lane, four in flight
 
 // --------------------------------------------------------------------------------------------
 // Column partials of a row tile.  Workgroup = 256 columns x one tile x one view; lane (cg, rl) owns 8 columns and the rows r0 + rl + 8k.
@@ -195,46 +179,28 @@ __global__ __launch_bounds__(256) void barlow_corr_k(const float* c, T* G, float
   const int i = blockIdx.x;
   const float* row = c + (long long)i * d;
   T* o = G + (long long)i * d;
+  constexpr int W = V8 ? 8 : 1;
   float on = 0.f, off = 0.f;
-  if (V8) {
-    for (int j = threadIdx.x * 8; j < d; j += 2048) {
-      float v[8];
-      load8<float>(row + j, v);
+  row_walk<W, 256>(threadIdx.x, d, [=, &on, &off](int j) {
+    float v[W];
+    load_w<W>(row + j, v);
 #pragma unroll
-      for (int e = 0; e < 8; e++) {
-        if (j + e == i) { const float t = v[e] - 1.0f; on += t * t; v[e] = g_on * t; }
-        else { off += v[e] * v[e]; v[e] = g_off * v[e]; }
-      }
-      store8<T>(o + j, v);
+    for (int e = 0; e < W; e++) {
+      if (j + e == i) { const float t = v[e] - 1.0f; on += t * t; v[e] = g_on * t; }
+      else { off += v[e] * v[e]; v[e] = g_off * v[e]; }
     }
-  } else {
-    for (int j = threadIdx.x; j < d; j += 256) {
-      const float v = row[j];
-      if (j == i) { const float t = v - 1.0f; on += t * t; Elem<T>::st(o + j, g_on * t); }
-      else { off += v * v; Elem<T>::st(o + j, g_off * v); }
-    }
-  }
-  on = wave_sum(on); off = wave_sum(off);
-  if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = on; sm[1][threadIdx.x >> 6] = off; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    rowpart[i] = (sm[0][0] + sm[0][1]) + (sm[0][2] + sm[0][3]);
-    rowpart[d + i] = (sm[1][0] + sm[1][1]) + (sm[1][2] + sm[1][3]);
-  }
+    store_w<W>(o + j, v);
+  });
+  block_sum4(on, off, sm);
+  if (threadIdx.x == 0) { rowpart[i] = on; rowpart[d + i] = off; }
 }
 // out = {on + lambda * off, on, off} from the row parts (single workgroup, fixed order)
 __global__ __launch_bounds__(256) void barlow_fold_k(const float* rowpart, float* out, int d, float lambda) {
   __shared__ float sm[2][4];
   float on = 0.f, off = 0.f;
   for (int i = threadIdx.x; i < d; i += 256) { on += rowpart[i]; off += rowpart[d + i]; }
-  on = wave_sum(on); off = wave_sum(off);
-  if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = on; sm[1][threadIdx.x >> 6] = off; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    on = (sm[0][0] + sm[0][1]) + (sm[0][2] + sm[0][3]);
-    off = (sm[1][0] + sm[1][1]) + (sm[1][2] + sm[1][3]);
-    out[0] = on + lambda * off; out[1] = on; out[2] = off;
-  }
+  block_sum4(on, off, sm);
+  if (threadIdx.x == 0) { out[0] = on + lambda * off; out[1] = on; out[2] = off; }
 }
 
 // dz = g * rstd_j * (dzh - a_j / n - zh * b_j / n), stored to dx[ix[r]] / dy[iy[r]] (the indices are unique: a store).  The layout of
@@ -289,10 +255,8 @@ extern "C" int pero_barlow_stats(const void* x, const int64_t* ix, const void* y
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((unsigned)((d + 255) / 256), (unsigned)tiles, 2), block(256);
   const bool v8 = v8_ok(d, dtype, {x, y});
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((barlow_tile_k<T, true, 0>), grid, block, 0, st, (const T*)x, ix, (const T*)y, iy, (const T*)nullptr, part, (long long)n, 0ll, (int)d); \
-                        else hipLaunchKernelGGL((barlow_tile_k<T, false, 0>), grid, block, 0, st, (const T*)x, ix, (const T*)y, iy, (const T*)nullptr, part, (long long)n, 0ll, (int)d); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((barlow_tile_k<T, decltype(V)::value, 0>), grid, block, 0, st, (const T*)x, ix, (const T*)y, iy, (const T*)nullptr, part, (long long)n, 0ll, (int)d); }); }), "bad dtype");
   hipLaunchKernelGGL((barlow_finish_k<0>), dim3((unsigned)((d + 63) / 64), 2), block, 0, st, part, mean, rstd, (long long)n, (int)d, (int)tiles, eps);
   PERO_CHECK_LAUNCH("pero_barlow_stats");
   return PERO_OK;
@@ -304,10 +268,8 @@ extern "C" int pero_barlow_standardize(const void* x, const int64_t* ix, const v
                "pero_barlow_standardize: bad arguments");
   dim3 grid((unsigned)((n_pad + RB - 1) / RB), (unsigned)((d + 255) / 256), 2), block(256);
   const bool v8 = v8_ok(d, dtype, {x, y, zh, mean, rstd});
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((barlow_standardize_k<T, true>), grid, block, 0, (hipStream_t)stream, (const T*)x, ix, (const T*)y, iy, mean, rstd, (T*)zh, (long long)n, (long long)n_pad, (int)d); \
-                        else hipLaunchKernelGGL((barlow_standardize_k<T, false>), grid, block, 0, (hipStream_t)stream, (const T*)x, ix, (const T*)y, iy, mean, rstd, (T*)zh, (long long)n, (long long)n_pad, (int)d); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((barlow_standardize_k<T, decltype(V)::value>), grid, block, 0, (hipStream_t)stream, (const T*)x, ix, (const T*)y, iy, mean, rstd, (T*)zh, (long long)n, (long long)n_pad, (int)d); }); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_barlow_standardize");
   return PERO_OK;
 }
@@ -317,10 +279,8 @@ extern "C" int pero_barlow_corr(const float* c, void* G, float* rowpart, float* 
   hipStream_t st = (hipStream_t)stream;
   const float g_on = 2.0f / (float)n, g_off = 2.0f * lambda / (float)n;
   const bool v8 = d % 8 == 0 && aligned16(c) && aligned16(G);
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((barlow_corr_k<T, true>), dim3((unsigned)d), dim3(256), 0, st, c, (T*)G, rowpart, (int)d, g_on, g_off); \
-                        else hipLaunchKernelGGL((barlow_corr_k<T, false>), dim3((unsigned)d), dim3(256), 0, st, c, (T*)G, rowpart, (int)d, g_on, g_off); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((barlow_corr_k<T, decltype(V)::value>), dim3((unsigned)d), dim3(256), 0, st, c, (T*)G, rowpart, (int)d, g_on, g_off); }); }), "bad dtype");
   hipLaunchKernelGGL(barlow_fold_k, dim3(1), dim3(256), 0, st, rowpart, out, (int)d, lambda);
   PERO_CHECK_LAUNCH("pero_barlow_corr");
   return PERO_OK;
@@ -335,10 +295,8 @@ extern "C" int pero_barlow_bwd_stats(const void* dzh, const void* zh, float* par
   dim3 grid((unsigned)((d + 255) / 256), (unsigned)tiles, 2), block(256);
   const bool v8 = v8_ok(d, dtype, {dzh, zh});
   const long long pitch = (long long)n_pad * d;
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((barlow_tile_k<T, true, 1>), grid, block, 0, st, (const T*)dzh, (const int64_t*)nullptr, (const T*)nullptr, (const int64_t*)nullptr, (const T*)zh, part, (long long)n, pitch, (int)d); \
-                        else hipLaunchKernelGGL((barlow_tile_k<T, false, 1>), grid, block, 0, st, (const T*)dzh, (const int64_t*)nullptr, (const T*)nullptr, (const int64_t*)nullptr, (const T*)zh, part, (long long)n, pitch, (int)d); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((barlow_tile_k<T, decltype(V)::value, 1>), grid, block, 0, st, (const T*)dzh, (const int64_t*)nullptr, (const T*)nullptr, (const int64_t*)nullptr, (const T*)zh, part, (long long)n, pitch, (int)d); }); }), "bad dtype");
   hipLaunchKernelGGL((barlow_finish_k<1>), dim3((unsigned)((d + 63) / 64), 2), block, 0, st, part, a, b, (long long)n, (int)d, (int)tiles, 0.f);
   PERO_CHECK_LAUNCH("pero_barlow_bwd_stats");
   return PERO_OK;
@@ -351,10 +309,8 @@ extern "C" int pero_barlow_standardize_bwd(const void* dzh, const void* zh, cons
                "pero_barlow_standardize_bwd: bad arguments");
   dim3 grid((unsigned)((n + RB - 1) / RB), (unsigned)((d + 255) / 256), 2), block(256);
   const bool v8 = v8_ok(d, dtype, {dzh, zh, dx, dy, rstd, a, b});
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((barlow_standardize_bwd_k<T, true>), grid, block, 0, (hipStream_t)stream, (const T*)dzh, (const T*)zh, rstd, a, b, ix, iy, (T*)dx, (T*)dy, g, (long long)n, (long long)n_pad, (int)d); \
-                        else hipLaunchKernelGGL((barlow_standardize_bwd_k<T, false>), grid, block, 0, (hipStream_t)stream, (const T*)dzh, (const T*)zh, rstd, a, b, ix, iy, (T*)dx, (T*)dy, g, (long long)n, (long long)n_pad, (int)d); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((barlow_standardize_bwd_k<T, decltype(V)::value>), grid, block, 0, (hipStream_t)stream, (const T*)dzh, (const T*)zh, rstd, a, b, ix, iy, (T*)dx, (T*)dy, g, (long long)n, (long long)n_pad, (int)d); }); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_barlow_standardize_bwd");
   return PERO_OK;
 }

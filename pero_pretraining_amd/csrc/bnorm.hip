@@ -4,7 +4,7 @@
 // one workgroup owns a strip of 64 columns and walks ALL rows (4 row lanes x 64 columns, 8 rows in flight per thread), so every
 // column sum is added in one fixed order (deterministic).  Training statistics are per call (per data-parallel RANK: what
 // torch.nn.BatchNorm1d does under DistributedDataParallel without SyncBatchNorm).
-#include "common.hpp"
+#include "dispatch.hpp"
 
 // mode 0: s0[c] = sum_r x[r][c]
 // mode 1: s0[c] = sum_r (x[r][c] - m[c])^2
@@ -122,9 +122,8 @@ extern "C" int pero_bn_fwd(const void* x, const float* weight, const float* bias
   PERO_REQUIRE(x && weight && bias && y && save_mean && save_rstd && work, "pero_bn_fwd: null pointer");
   PERO_REQUIRE(rows > 0 && d > 0 && d < (1LL << 30), "pero_bn_fwd: bad shape");
   PERO_REQUIRE(training || (running_mean && running_var), "pero_bn_fwd: evaluation mode needs the running statistics");
-  if (dtype == PERO_F32) bn_fwd_t<float>(x, weight, bias, running_mean, running_var, y, save_mean, save_rstd, work, rows, (int)d, eps, momentum, training != 0, relu != 0, (hipStream_t)stream);
-  else if (dtype == PERO_BF16) bn_fwd_t<bf16raw>(x, weight, bias, running_mean, running_var, y, save_mean, save_rstd, work, rows, (int)d, eps, momentum, training != 0, relu != 0, (hipStream_t)stream);
-  else PERO_REQUIRE(false, "pero_bn_fwd: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) {
+    bn_fwd_t<decltype(t)>(x, weight, bias, running_mean, running_var, y, save_mean, save_rstd, work, rows, (int)d, eps, momentum, training != 0, relu != 0, (hipStream_t)stream); }), "pero_bn_fwd: bad dtype");
   PERO_CHECK_LAUNCH("pero_bn_fwd");
   return PERO_OK;
 }
@@ -143,9 +142,8 @@ extern "C" int pero_bn_bwd(const void* dy, const void* x, const void* y, const f
                            void* dx, float* dweight, float* dbias, float* work, int64_t rows, int64_t d, int relu, int dtype, void* stream) {
   PERO_REQUIRE(dy && x && weight && save_mean && save_rstd && dx && work && (!relu || y), "pero_bn_bwd: null pointer");
   PERO_REQUIRE(rows > 0 && d > 0 && d < (1LL << 30), "pero_bn_bwd: bad shape");
-  if (dtype == PERO_F32) bn_bwd_t<float>(dy, x, y, weight, save_mean, save_rstd, dx, dweight, dbias, work, rows, (int)d, relu != 0, (hipStream_t)stream);
-  else if (dtype == PERO_BF16) bn_bwd_t<bf16raw>(dy, x, y, weight, save_mean, save_rstd, dx, dweight, dbias, work, rows, (int)d, relu != 0, (hipStream_t)stream);
-  else PERO_REQUIRE(false, "pero_bn_bwd: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) {
+    bn_bwd_t<decltype(t)>(dy, x, y, weight, save_mean, save_rstd, dx, dweight, dbias, work, rows, (int)d, relu != 0, (hipStream_t)stream); }), "pero_bn_bwd: bad dtype");
   PERO_CHECK_LAUNCH("pero_bn_bwd");
   return PERO_OK;
 }

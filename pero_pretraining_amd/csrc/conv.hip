@@ -5,7 +5,7 @@
 // are written as zeros, so the next layer finds its padding in place.  Loads are guarded (a row index is clamped into [0, R - 1]; such a row
 // only ever feeds a halo row or a row past R, whose results are not stored), so no access leaves the caller's buffers and no slack is needed.
 // No atomics; every output element is one fixed-order sum: a second run gives the same bits.
-#include "losses_common.hpp"
+#include "dispatch.hpp"
 
 // activation of pero_conv3x3's epilogue
 __device__ __forceinline__ float conv_act(float v, int act, float slope) {
@@ -329,16 +329,15 @@ extern "C" int pero_conv3x3(const void* x, const void* w, const float* bias, voi
   const int Hp = (int)H + 2, Wp = (int)W + 2;
   hipStream_t st = (hipStream_t)stream;
   if (Cin % (dtype == PERO_BF16 ? 8 : 4) == 0) {
-    const int rc = dtype == PERO_BF16 ? conv3x3_tiles<bf16raw>(x, w, bias, y, R, Hp, Wp, (int)Cin, (int)Cout, act, slope, st)
-                                      : conv3x3_tiles<float>(x, w, bias, y, R, Hp, Wp, (int)Cin, (int)Cout, act, slope, st);
+    int rc = PERO_OK;
+    with_elem(dtype, [&](auto t) { rc = conv3x3_tiles<decltype(t)>(x, w, bias, y, R, Hp, Wp, (int)Cin, (int)Cout, act, slope, st); });
     if (rc != PERO_OK) return rc;
   } else {
     const double threads = (double)R * (double)Cout;
     PERO_REQUIRE(threads / 256.0 < 2147483647.0, "pero_conv3x3: too many outputs for one launch");
     const unsigned blocks = (unsigned)((R * Cout + 255) / 256);
-#define L_(T, ...) hipLaunchKernelGGL((conv3x3_direct_k<T>), dim3(blocks), dim3(256), 0, st, (const T*)x, (const T*)w, bias, (T*)y, R, Hp, Wp, (int)Cin, (int)Cout, act, slope)
-    DISPATCH_T(dtype, L_, 0);
-#undef L_
+    with_elem(dtype, [&](auto t) { using T = decltype(t);
+      hipLaunchKernelGGL((conv3x3_direct_k<T>), dim3(blocks), dim3(256), 0, st, (const T*)x, (const T*)w, bias, (T*)y, R, Hp, Wp, (int)Cin, (int)Cout, act, slope); });
   }
   PERO_CHECK_LAUNCH("pero_conv3x3");
   return PERO_OK;
@@ -358,12 +357,8 @@ extern "C" int pero_image_to_halo(const void* src, void* dst, int64_t N, int64_t
   const dim3 grid((unsigned)((R + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
   const bool vec = C_pad * (dtype == PERO_F32 ? 4 : 2) == 16 && aligned16(dst);
-#define K_(T, S, V) hipLaunchKernelGGL((image_to_halo_k<T, S, V>), grid, block, 0, st, src, (T*)dst, R, (int)H, (int)W, (int)C, (int)C_pad)
-#define L_(T, ...) do { if (src_kind == PERO_IMAGE_U8_NHWC) { if (vec) K_(T, 0, true); else K_(T, 0, false); } \
-                        else { if (vec) K_(T, 1, true); else K_(T, 1, false); } } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
-#undef K_
+  with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(src_kind == PERO_IMAGE_F32_NCHW, [&](auto S) { with_flag(vec, [&](auto V) {
+    hipLaunchKernelGGL((image_to_halo_k<T, decltype(S)::value, decltype(V)::value>), grid, block, 0, st, src, (T*)dst, R, (int)H, (int)W, (int)C, (int)C_pad); }); }); });
   PERO_CHECK_LAUNCH("pero_image_to_halo");
   return PERO_OK;
 }
@@ -387,11 +382,8 @@ extern "C" int pero_maxpool_nhwc(const void* x, void* y, const float* a, const f
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
   const bool v8 = v8_ok(C, dtype, {x, y});
-#define K_(T, V, K) hipLaunchKernelGGL((maxpool_k<T, V, K>), grid, block, 0, st, (const T*)x, (T*)y, a, b, total, (int)H, (int)W, (int)C, ph, pw)
-#define L_(T, ...) do { if (v8) { if (token_rows) K_(T, true, 1); else K_(T, true, 0); } else { if (token_rows) K_(T, false, 1); else K_(T, false, 0); } } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
-#undef K_
+  with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) { with_flag(token_rows != 0, [&](auto K) {
+    hipLaunchKernelGGL((maxpool_k<T, decltype(V)::value, decltype(K)::value>), grid, block, 0, st, (const T*)x, (T*)y, a, b, total, (int)H, (int)W, (int)C, ph, pw); }); }); });
   PERO_CHECK_LAUNCH("pero_maxpool_nhwc");
   return PERO_OK;
 }

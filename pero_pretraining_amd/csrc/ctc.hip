@@ -210,18 +210,13 @@ int ctc_check(const char* name, int64_t N, int64_t S, int64_t C, int64_t Lmax, i
   return PERO_OK;
 }
 
-#define CTC_LAUNCH_LSE(T, ...)                                                                                                                 \
-  hipLaunchKernelGGL((ctc_row_lse_k<T>), dim3((unsigned)((rows + 3) / 4)), dim3(CTC_THREADS), 0, st, (const T*)logits, input_lengths, row_lse, \
-                     (long long)rows, (int)S, (int)C)
 int ctc_launch_row_lse(const void* logits, const int64_t* input_lengths, float* row_lse, int64_t N, int64_t S, int64_t C, int dtype, hipStream_t st) {
   const int64_t rows = N * S;
-  DISPATCH_T(dtype, CTC_LAUNCH_LSE, 0);
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ctc_row_lse_k<T>), dim3((unsigned)((rows + 3) / 4)), dim3(CTC_THREADS), 0, st, (const T*)logits, input_lengths, row_lse,
+                       (long long)rows, (int)S, (int)C); }), "bad dtype");
   return PERO_OK;
 }
-
-#define CTC_LAUNCH_ALPHA(T, ...)                                                                                                            \
-  hipLaunchKernelGGL((ctc_alpha_k<T>), dim3((unsigned)N), dim3(CTC_THREADS), lds, st, (const T*)logits, targets, input_lengths, target_lengths, \
-                     (const float*)row_lse, alpha, nll, (int)S, (int)C, (int)Lmax, (int)blank)
 
 extern "C" int pero_ctc_fwd(const void* logits, const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths, float* row_lse,
                             float* alpha, float* nll, int64_t N, int64_t S, int64_t C, int64_t Lmax, int64_t blank, int dtype, void* stream) {
@@ -232,18 +227,12 @@ extern "C" int pero_ctc_fwd(const void* logits, const int64_t* targets, const in
   ctc_launch_row_lse(logits, nullptr, row_lse, N, S, C, dtype, st);   // every row, as the header promises
   PERO_CHECK_LAUNCH("pero_ctc_fwd (row lse)");
   const size_t lds = 2 * (2 * (size_t)Lmax + 5) * sizeof(float);
-  DISPATCH_T(dtype, CTC_LAUNCH_ALPHA, 0);
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ctc_alpha_k<T>), dim3((unsigned)N), dim3(CTC_THREADS), lds, st, (const T*)logits, targets, input_lengths, target_lengths,
+                       (const float*)row_lse, alpha, nll, (int)S, (int)C, (int)Lmax, (int)blank); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_ctc_fwd (alpha)");
   return PERO_OK;
 }
-
-#define CTC_LAUNCH_BETA(T, ...)                                                                                                            \
-  hipLaunchKernelGGL((ctc_beta_k<T>), dim3((unsigned)N), dim3(CTC_THREADS), lds_b, st, (const T*)logits, targets, input_lengths, target_lengths, \
-                     row_lse, beta, chain, (int)S, (int)C, (int)Lmax, (int)blank)
-#define CTC_LAUNCH_GRAD(T, ...)                                                                                                             \
-  hipLaunchKernelGGL((ctc_grad_k<T>), dim3((unsigned)(N * S)), dim3(CTC_THREADS), lds_g, st, (const T*)logits, targets, input_lengths,          \
-                     target_lengths, row_lse, alpha, (const float*)beta, nll, g, (const int32_t*)chain, (T*)dlogits, (int)S, (int)C, (int)Lmax, \
-                     (int)blank, zero_infinity)
 
 extern "C" int pero_ctc_bwd(const void* logits, const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths,
                             const float* row_lse, const float* alpha, const float* nll, const float* g, float* beta, int32_t* chain, void* dlogits,
@@ -254,17 +243,18 @@ extern "C" int pero_ctc_bwd(const void* logits, const int64_t* targets, const in
                "pero_ctc_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const size_t lds_b = (2 * (2 * (size_t)Lmax + 5) + (size_t)Lmax) * sizeof(float);
-  DISPATCH_T(dtype, CTC_LAUNCH_BETA, 0);
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ctc_beta_k<T>), dim3((unsigned)N), dim3(CTC_THREADS), lds_b, st, (const T*)logits, targets, input_lengths, target_lengths,
+                       row_lse, beta, chain, (int)S, (int)C, (int)Lmax, (int)blank); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_ctc_bwd (beta)");
   const size_t lds_g = ((size_t)C + 2 * (size_t)Lmax + 1 + 4) * sizeof(float);
-  DISPATCH_T(dtype, CTC_LAUNCH_GRAD, 0);
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ctc_grad_k<T>), dim3((unsigned)(N * S)), dim3(CTC_THREADS), lds_g, st, (const T*)logits, targets, input_lengths,
+                       target_lengths, row_lse, alpha, (const float*)beta, nll, g, (const int32_t*)chain, (T*)dlogits, (int)S, (int)C, (int)Lmax,
+                       (int)blank, zero_infinity); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_ctc_bwd (gradient)");
   return PERO_OK;
 }
-
-#define CTC_LAUNCH_GREEDY(T, ...)                                                                                                       \
-  hipLaunchKernelGGL((ctc_greedy_k<T>), dim3((unsigned)N), dim3(CTC_THREADS), ((size_t)S + 1) * sizeof(int), st, (const T*)logits, input_lengths, out, \
-                     out_lengths, (int)S, (int)C, (int)blank)
 
 extern "C" int pero_ctc_greedy(const void* logits, const int64_t* input_lengths, int64_t* out, int64_t* out_lengths, int64_t N, int64_t S, int64_t C,
                                int64_t blank, int dtype, void* stream) {
@@ -272,7 +262,9 @@ extern "C" int pero_ctc_greedy(const void* logits, const int64_t* input_lengths,
   if (rc != PERO_OK) return rc;
   PERO_REQUIRE(logits && input_lengths && out && out_lengths, "pero_ctc_greedy: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, CTC_LAUNCH_GREEDY, 0);
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ctc_greedy_k<T>), dim3((unsigned)N), dim3(CTC_THREADS), ((size_t)S + 1) * sizeof(int), st, (const T*)logits, input_lengths, out,
+                       out_lengths, (int)S, (int)C, (int)blank); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_ctc_greedy");
   return PERO_OK;
 }

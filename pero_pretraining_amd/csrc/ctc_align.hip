@@ -132,14 +132,6 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_align_k(const T* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-#define ALIGN_LAUNCH(T, LDS_BACK)                                                                                                          \
-  do {                                                                                                                                     \
-    if (LDS_BACK) PERO_LDS_ATTR((ctc_align_k<T, LDS_BACK>), lds_max);                                                                      \
-    hipLaunchKernelGGL((ctc_align_k<T, LDS_BACK>), dim3((unsigned)N), dim3(CTC_THREADS), lds, st, (const T*)logits, targets, input_lengths, \
-                       target_lengths, (const float*)row_lse, (uint8_t*)back, states, spans, path_logit, score, label_logp, (int)S, (int)C, \
-                       (int)Lmax, (int)blank);                                                                                             \
-  } while (0)
-
 extern "C" int pero_ctc_align(const void* logits, const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths,
                               int32_t* states, int32_t* spans, float* path_logit, float* score, float* label_logp, float* row_lse, void* back,
                               int64_t N, int64_t S, int64_t C, int64_t Lmax, int64_t blank, int flags, int dtype, void* stream) {
@@ -158,8 +150,12 @@ extern "C" int pero_ctc_align(const void* logits, const int64_t* targets, const 
   const size_t fixed = (2 * ((size_t)W + 2) + (size_t)S + 2 * (size_t)Lmax) * sizeof(float);
   const size_t lds = fixed + (lds_back ? (size_t)(S * W) : 0);
   const size_t lds_max = (2 * (2 * (size_t)CTC_MAX_S + 3) + 3 * (size_t)CTC_MAX_S) * sizeof(float) + ALIGN_LDS_BACK_MAX;
-  if (lds_back) DISPATCH_T(dtype, ALIGN_LAUNCH, true);
-  else DISPATCH_T(dtype, ALIGN_LAUNCH, false);
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(lds_back, [&](auto B) {
+    constexpr bool LDS_BACK = decltype(B)::value;
+    if (LDS_BACK) PERO_LDS_ATTR((ctc_align_k<T, LDS_BACK>), lds_max);
+    hipLaunchKernelGGL((ctc_align_k<T, LDS_BACK>), dim3((unsigned)N), dim3(CTC_THREADS), lds, st, (const T*)logits, targets, input_lengths,
+                       target_lengths, (const float*)row_lse, (uint8_t*)back, states, spans, path_logit, score, label_logp, (int)S, (int)C,
+                       (int)Lmax, (int)blank); }); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_ctc_align (alignment)");
   return PERO_OK;
 }

@@ -3,7 +3,7 @@
 // piece of arithmetic that include/pero_hip.h promises to be the same between loss, decoder and aligner exists here, once.  Derivation: DESIGN.md
 // section 11 "Kernels".
 #pragma once
-#include "losses_common.hpp"
+#include "dispatch.hpp"
 
 #define CTC_THREADS 256
 #define CTC_MAX_S 512

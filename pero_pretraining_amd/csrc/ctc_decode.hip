@@ -400,14 +400,6 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_k(const T* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-#define BEAM_LAUNCH_TOP(T, ...)                                                                                                          \
-  hipLaunchKernelGGL((ctc_beam_top_k<T>), dim3((unsigned)((rows + 3) / 4)), dim3(CTC_THREADS), 0, st, (const T*)logits, input_lengths, row_lse, \
-                     top_logp, top_class, (long long)rows, (int)S, (int)C, (int)blank, (int)K)
-#define BEAM_LAUNCH(T, LM)                                                                                                                   \
-  hipLaunchKernelGGL((ctc_beam_k<T, LM>), dim3((unsigned)N), dim3(CTC_THREADS), 0, st, (const T*)logits, input_lengths, (const float*)row_lse,    \
-                     (const float*)top_logp, (const int32_t*)top_class, (unsigned long long*)hash, out, out_lengths, out_scores, out_count,      \
-                     node_parent, node_label, node_count, beam_node, beam_score, (int)S, (int)C, (int)blank, (int)W, (int)K, (int)H, lm)
-
 // Both entry points: the checks they share, then the two launches.  with_lm: ctc_beam_k<T, true> with the caller's K.
 static int beam_run(const char* name, const void* logits, const int64_t* input_lengths, int64_t* out, int64_t* out_lengths, float* out_scores,
                     int64_t* out_count, int32_t* node_parent, int32_t* node_label, int32_t* node_count, int32_t* beam_node, float* beam_score,
@@ -430,10 +422,14 @@ static int beam_run(const char* name, const void* logits, const int64_t* input_l
   }
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = N * S, H = beam_hash_slots(S, W);
-  DISPATCH_T(dtype, BEAM_LAUNCH_TOP, 0);
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ctc_beam_top_k<T>), dim3((unsigned)((rows + 3) / 4)), dim3(CTC_THREADS), 0, st, (const T*)logits, input_lengths, row_lse,
+                       top_logp, top_class, (long long)rows, (int)S, (int)C, (int)blank, (int)K); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_ctc_beam (row lse, best classes)");
-  if (with_lm) DISPATCH_T(dtype, BEAM_LAUNCH, true);
-  else DISPATCH_T(dtype, BEAM_LAUNCH, false);
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(with_lm, [&](auto LM) {
+    hipLaunchKernelGGL((ctc_beam_k<T, decltype(LM)::value>), dim3((unsigned)N), dim3(CTC_THREADS), 0, st, (const T*)logits, input_lengths, (const float*)row_lse,
+                       (const float*)top_logp, (const int32_t*)top_class, (unsigned long long*)hash, out, out_lengths, out_scores, out_count,
+                       node_parent, node_label, node_count, beam_node, beam_score, (int)S, (int)C, (int)blank, (int)W, (int)K, (int)H, lm); }); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_ctc_beam (search)");
   return PERO_OK;
 }

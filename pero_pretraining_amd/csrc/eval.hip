@@ -4,7 +4,7 @@
 // (tester.py:72-91) - 1 GiB per batch at B = 256, V = 4096.  Here the rank of the label inside its row is computed
 // where the logits live, and the top-k error counters are accumulated on the device with integer atomics
 // (deterministic), so a whole test() loop needs one 8-byte-per-counter read-back at the end.
-#include "common.hpp"
+#include "dispatch.hpp"
 
 // counters[0] += number of rows with mask == 1; counters[1 + i] += rows whose label is NOT among the top ks[i] logits.
 // Tie rules (value comparisons in f32; a bf16 -> f32 widening is exact):
@@ -71,14 +71,9 @@ extern "C" int pero_label_rank(const void* logits, int64_t ld, const int64_t* la
   PERO_REQUIRE(rows > 0 && V > 0 && V < (1LL << 31) && ld >= V && rows < (1LL << 31), "pero_label_rank: bad sizes");
   PERO_REQUIRE(nk >= 0 && nk <= PERO_MAX_TOPK && (nk == 0 || ks), "pero_label_rank: 0..%d measured errors", PERO_MAX_TOPK);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PERO_F32)
-    hipLaunchKernelGGL((label_rank_k<float>), dim3((unsigned)rows), dim3(256), 0, st, (const float*)logits, (long long)ld, labels,
-                       mask, (long long)rows, (int)V, (const int*)ks, (int)nk, (unsigned long long*)counters, (int*)ranks);
-  else if (dtype == PERO_BF16)
-    hipLaunchKernelGGL((label_rank_k<bf16raw>), dim3((unsigned)rows), dim3(256), 0, st, (const bf16raw*)logits, (long long)ld,
-                       labels, mask, (long long)rows, (int)V, (const int*)ks, (int)nk, (unsigned long long*)counters, (int*)ranks);
-  else
-    PERO_REQUIRE(false, "pero_label_rank: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((label_rank_k<T>), dim3((unsigned)rows), dim3(256), 0, st, (const T*)logits, (long long)ld, labels,
+                       mask, (long long)rows, (int)V, (const int*)ks, (int)nk, (unsigned long long*)counters, (int*)ranks); }), "pero_label_rank: bad dtype");
   PERO_CHECK_LAUNCH("pero_label_rank");
   return PERO_OK;
 }

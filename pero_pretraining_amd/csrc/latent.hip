@@ -2,6 +2,7 @@
 // the regression loss (smooth L1 / MSE) with its gradient.  All HBM-bound, no float atomics, every sum in a fixed order.  Formulas,
 // operation order and layouts: include/pero_hip.h ("latent-target self-distillation").
 #include "flat_tiles.hpp"
+#include "dispatch.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // EMA.  table[s] = {source address, destination offset, count, first tile}.
@@ -164,15 +165,15 @@ extern "C" int pero_ema_update(float* avg, void* avg_bf16, const int64_t* table,
 template <typename T>
 static void launch_targets(int nch, dim3 grid, hipStream_t st, const LatentMats& m, int K, const int64_t* index, float* y, int64_t rows,
                            int64_t n, int64_t n_pad, int d, float eps, float inv_k) {
-#define LATENT_TARGETS_CASE(N_)                                                                                                      \
-  hipLaunchKernelGGL((latent_targets_k<T, N_>), grid, dim3(256), 0, st, m, K, (const long long*)index, y, (long long)rows, (long long)n, \
-                     (long long)n_pad, d, eps, inv_k)
-  if (nch <= 1) LATENT_TARGETS_CASE(1);
-  else if (nch <= 2) LATENT_TARGETS_CASE(2);
-  else if (nch <= 4) LATENT_TARGETS_CASE(4);
-  else if (nch <= 8) LATENT_TARGETS_CASE(8);
-  else LATENT_TARGETS_CASE(16);
-#undef LATENT_TARGETS_CASE
+  auto launch = [&](auto N) {
+    hipLaunchKernelGGL((latent_targets_k<T, decltype(N)::value>), grid, dim3(256), 0, st, m, K, (const long long*)index, y, (long long)rows, (long long)n,
+                       (long long)n_pad, d, eps, inv_k);
+  };
+  if (nch <= 1) launch(std::integral_constant<int, 1>());
+  else if (nch <= 2) launch(std::integral_constant<int, 2>());
+  else if (nch <= 4) launch(std::integral_constant<int, 4>());
+  else if (nch <= 8) launch(std::integral_constant<int, 8>());
+  else launch(std::integral_constant<int, 16>());
 }
 
 extern "C" int pero_latent_targets(const void** mats, int64_t K, const int64_t* index, float* y, int64_t rows, int64_t n, int64_t n_pad,
@@ -191,8 +192,7 @@ extern "C" int pero_latent_targets(const void** mats, int64_t K, const int64_t* 
   const dim3 grid((unsigned)((n_pad + 3) / 4));
   const int nch = (int)((d + 255) / 256);
   const float inv_k = (float)(1.0 / (double)K);
-  if (dtype == PERO_F32) launch_targets<float>(nch, grid, (hipStream_t)stream, m, (int)K, index, y, rows, n, n_pad, (int)d, eps, inv_k);
-  else launch_targets<bf16raw>(nch, grid, (hipStream_t)stream, m, (int)K, index, y, rows, n, n_pad, (int)d, eps, inv_k);
+  with_elem(dtype, [&](auto t) { launch_targets<decltype(t)>(nch, grid, (hipStream_t)stream, m, (int)K, index, y, rows, n, n_pad, (int)d, eps, inv_k); });
   PERO_CHECK_LAUNCH("pero_latent_targets");
   return PERO_OK;
 }
@@ -211,11 +211,8 @@ extern "C" int pero_latent_loss_fwd(const void* pred, const float* y, float* wor
   if (n > 0) {
     const dim3 grid((unsigned)((n + 3) / 4));
     const bool mse = beta == 0.f;
-#define LATENT_ROWS(T_, M_) \
-  hipLaunchKernelGGL((latent_loss_rows_k<T_, M_>), grid, dim3(256), 0, st, (const T_*)pred, y, work, (long long)n, (int)d, beta)
-    if (dtype == PERO_F32) { if (mse) LATENT_ROWS(float, true); else LATENT_ROWS(float, false); }
-    else { if (mse) LATENT_ROWS(bf16raw, true); else LATENT_ROWS(bf16raw, false); }
-#undef LATENT_ROWS
+    with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(mse, [&](auto M) {
+      hipLaunchKernelGGL((latent_loss_rows_k<T, decltype(M)::value>), grid, dim3(256), 0, st, (const T*)pred, y, work, (long long)n, (int)d, beta); }); });
     PERO_CHECK_LAUNCH("pero_latent_loss_fwd");
   }
   hipLaunchKernelGGL(latent_loss_finish_k, dim3(1), dim3(256), 0, st, work, loss, (long long)n, (int)d);
@@ -234,12 +231,9 @@ extern "C" int pero_latent_loss_bwd(const void* pred, const float* y, const floa
   const float coef = n > 0 ? (float)(1.0 / ((double)n * (double)d)) : 0.f;
   const dim3 grid((unsigned)((n_all + 255) / 256));
   const bool mse = beta == 0.f;
-#define LATENT_BWD(T_, M_)                                                                                                            \
-  hipLaunchKernelGGL((latent_loss_bwd_k<T_, M_>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)pred, y, dloss, (T_*)dpred, n_live, \
-                     n_all, coef, beta)
-  if (dtype == PERO_F32) { if (mse) LATENT_BWD(float, true); else LATENT_BWD(float, false); }
-  else { if (mse) LATENT_BWD(bf16raw, true); else LATENT_BWD(bf16raw, false); }
-#undef LATENT_BWD
+  with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(mse, [&](auto M) {
+    hipLaunchKernelGGL((latent_loss_bwd_k<T, decltype(M)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)pred, y, dloss, (T*)dpred, n_live,
+                       n_all, coef, beta); }); });
   PERO_CHECK_LAUNCH("pero_latent_loss_bwd");
   return PERO_OK;
 }

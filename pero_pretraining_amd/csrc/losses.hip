@@ -1,7 +1,8 @@
 // Reduction kernels of the joint-embedding losses (joint_embedding_pretraining/losses.py of the reference).
 // The dense contractions (VICReg covariance SYRK, its backward, the per-line NT-Xent similarity matrices and
 // their backward products) run on pero_gemm; everything here is HBM-bound row/column work in f32 statistics.
-#include "losses_common.hpp"
+#include "dispatch.hpp"
+#include "rows.hpp"
 
 // --------------------------------------------------------------------------------------------
 // squared-difference sum of gathered rows (VICReg invariance, losses.py:14-16):
@@ -14,17 +15,14 @@ __global__ __launch_bounds__(256) void sqdiff_rows_k(const T* x, const int64_t* 
   if (row >= n) return;
   const T* a = x + ix[row] * d;
   const T* b = y + iy[row] * d;
+  constexpr int W = V8 ? 8 : 1;  // 16-byte accesses: d % 8 == 0, 16-byte aligned rows (the scalar walk moves 2 bytes per lane and instruction)
   float s = 0.f;
-  if (V8) {  // 16-byte accesses: d % 8 == 0, 16-byte aligned rows (the scalar loop moved 2 bytes per lane and instruction)
-    for (int c = (threadIdx.x & 63) * 8; c < d; c += 512) {
-      float va[8], vb[8];
-      load8<T>(a + c, va); load8<T>(b + c, vb);
+  row_walk<W>(threadIdx.x & 63, d, [=, &s](int c) {
+    float va[W], vb[W];
+    load_w<W>(a + c, va); load_w<W>(b + c, vb);
 #pragma unroll
-      for (int e = 0; e < 8; e++) { const float t = va[e] - vb[e]; s += t * t; }
-    }
-  } else {
-    for (int c = threadIdx.x & 63; c < d; c += 64) { const float t = Elem<T>::ld(a + c) - Elem<T>::ld(b + c); s += t * t; }
-  }
+    for (int e = 0; e < W; e++) { const float t = va[e] - vb[e]; s += t * t; }
+  });
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) partial[row] = s;
 }
@@ -33,10 +31,8 @@ __global__ __launch_bounds__(256) void sum_scale_k(const float* partial, float* 
   __shared__ float sm[4];
   float s = 0.f;
   for (long long i = threadIdx.x; i < n; i += 256) s += partial[i];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = ((sm[0] + sm[1]) + (sm[2] + sm[3])) * scale;
+  s = block_sum4(s, sm);
+  if (threadIdx.x == 0) out[0] = s * scale;
 }
 // dx[ix[row]] += g*coef*(x-y), dy[iy[row]] -= g*coef*(x-y)   (rows of ix / iy are unique)
 template <typename T, bool V8>
@@ -46,21 +42,14 @@ __global__ __launch_bounds__(256) void sqdiff_rows_bwd_k(const T* x, const int64
   if (row >= n) return;
   const float c0 = coef * (g ? g[0] : 1.f);
   const long long ra = ix[row], rb = iy[row];
-  if (V8) {
-    for (int c = (threadIdx.x & 63) * 8; c < d; c += 512) {
-      float vx[8], vy[8], gx[8], gy[8];
-      load8<T>(x + ra * d + c, vx); load8<T>(y + rb * d + c, vy); load8<T>(dx + ra * d + c, gx); load8<T>(dy + rb * d + c, gy);
+  constexpr int W = V8 ? 8 : 1;
+  row_walk<W>(threadIdx.x & 63, d, [=](int c) {
+    float vx[W], vy[W], gx[W], gy[W];
+    load_w<W>(x + ra * d + c, vx); load_w<W>(y + rb * d + c, vy); load_w<W>(dx + ra * d + c, gx); load_w<W>(dy + rb * d + c, gy);
 #pragma unroll
-      for (int e = 0; e < 8; e++) { const float t = c0 * (vx[e] - vy[e]); gx[e] += t; gy[e] -= t; }
-      store8<T>(dx + ra * d + c, gx); store8<T>(dy + rb * d + c, gy);
-    }
-    return;
-  }
-  for (int c = threadIdx.x & 63; c < d; c += 64) {
-    const float t = c0 * (Elem<T>::ld(x + ra * d + c) - Elem<T>::ld(y + rb * d + c));
-    Elem<T>::st(dx + ra * d + c, Elem<T>::ld(dx + ra * d + c) + t);
-    Elem<T>::st(dy + rb * d + c, Elem<T>::ld(dy + rb * d + c) - t);
-  }
+    for (int e = 0; e < W; e++) { const float t = c0 * (vx[e] - vy[e]); gx[e] += t; gy[e] -= t; }
+    store_w<W>(dx + ra * d + c, gx); store_w<W>(dy + rb * d + c, gy);
+  });
 }
 
 // --------------------------------------------------------------------------------------------
@@ -82,19 +71,11 @@ __global__ __launch_bounds__(256) void center_cols_k(const T* z, const float* co
     for (long long r = r0 + rl; r < r1; r += 8) {
       float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       if (r < m) {
-        if (V8) load8<T>(z + r * d + col, v);
-        else {
-#pragma unroll
-          for (int e = 0; e < 8; e++) v[e] = Elem<T>::ld(z + r * d + col + e);
-        }
+        ld8<T, V8>(z + r * d, (int)col, d, v);
 #pragma unroll
         for (int e = 0; e < 8; e++) v[e] -= mu[e];
       }
-      if (V8) store8<T>(zc + r * d + col, v);
-      else {
-#pragma unroll
-        for (int e = 0; e < 8; e++) Elem<T>::st(zc + r * d + col + e, v[e]);
-      }
+      st8<T, V8>(zc + r * d, (int)col, d, v);
 #pragma unroll
       for (int e = 0; e < 8; e++) acc[e] += v[e] * v[e];
     }
@@ -122,10 +103,8 @@ __global__ __launch_bounds__(256) void vicreg_var_k(const float* sumsq, float* c
     s += h > 0.f ? h : 0.f;
     cvar[j] = h > 0.f ? -1.0f / ((float)d * sd * (float)(m - 1)) : 0.f;
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) loss_var[0] = ((sm[0] + sm[1]) + (sm[2] + sm[3])) / (float)d;
+  s = block_sum4(s, sm);
+  if (threadIdx.x == 0) loss_var[0] = s / (float)d;
 }
 // One pass over cov (d x d, f32): row partial sums of the squared off-diagonal entries, and the backward
 // operand G (compute dtype):  G_ij = wc * 4 * cov_ij / (d * (m-1))  (i != j),  G_jj = wv * cvar_j,
@@ -142,10 +121,8 @@ __global__ __launch_bounds__(256) void vicreg_cov_k(const float* cov, const floa
     if (j != i) { s += c * c; Elem<T>::st(G + (long long)i * d + j, a * c); }
     else Elem<T>::st(G + (long long)i * d + j, wv * cvar[i]);
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) rowpart[i] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+  s = block_sum4(s, sm);
+  if (threadIdx.x == 0) rowpart[i] = s;
 }
 // dst[index[i]] += g * src[i]
 template <typename T, bool V8>
@@ -154,17 +131,14 @@ __global__ __launch_bounds__(256) void scatter_add_scaled_k(const T* src, const 
   if (row >= n) return;
   const float gs = g ? g[0] : 1.f;
   T* o = dst + index[row] * d;
-  if (V8) {
-    for (int c = (threadIdx.x & 63) * 8; c < d; c += 512) {
-      float a[8], b[8];
-      load8<T>(o + c, a); load8<T>(src + row * d + c, b);
+  constexpr int W = V8 ? 8 : 1;
+  row_walk<W>(threadIdx.x & 63, d, [=](int c) {
+    float a[W], b[W];
+    load_w<W>(o + c, a); load_w<W>(src + row * d + c, b);
 #pragma unroll
-      for (int e = 0; e < 8; e++) a[e] += gs * b[e];
-      store8<T>(o + c, a);
-    }
-    return;
-  }
-  for (int c = threadIdx.x & 63; c < d; c += 64) Elem<T>::st(o + c, Elem<T>::ld(o + c) + gs * Elem<T>::ld(src + row * d + c));
+    for (int e = 0; e < W; e++) a[e] += gs * b[e];
+    store_w<W>(o + c, a);
+  });
 }
 
 // --------------------------------------------------------------------------------------------
@@ -175,62 +149,15 @@ template <typename T, bool V8>
 __global__ __launch_bounds__(256) void rownorm_fwd_k(const T* x, T* xn, float* inv, long long rows, int d) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  float s = 0.f;
-  if (V8) {
-    for (int c = (threadIdx.x & 63) * 8; c < d; c += 512) {
-      float v[8];
-      load8<T>(x + row * d + c, v);
-#pragma unroll
-      for (int e = 0; e < 8; e++) s += v[e] * v[e];
-    }
-  } else {
-    for (int c = threadIdx.x & 63; c < d; c += 64) { const float v = Elem<T>::ld(x + row * d + c); s += v * v; }
-  }
-  s = wave_sum(s);
-  const float r = 1.0f / fmaxf(sqrtf(s), 1e-12f);  // F.normalize eps
+  const float r = row_l2_normalize<T, V8>(x + row * d, xn + row * d, threadIdx.x & 63, d);
   if ((threadIdx.x & 63) == 0) inv[row] = r;
-  if (V8) {
-    for (int c = (threadIdx.x & 63) * 8; c < d; c += 512) {
-      float v[8];
-      load8<T>(x + row * d + c, v);
-#pragma unroll
-      for (int e = 0; e < 8; e++) v[e] *= r;
-      store8<T>(xn + row * d + c, v);
-    }
-    return;
-  }
-  for (int c = threadIdx.x & 63; c < d; c += 64) Elem<T>::st(xn + row * d + c, Elem<T>::ld(x + row * d + c) * r);
 }
 // dx = (dxn - xn * <xn, dxn>) * inv
 template <typename T, bool V8>
 __global__ __launch_bounds__(256) void rownorm_bwd_k(const T* xn, const T* dxn, const float* inv, const float* g, T* dx, long long rows, int d) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  float s = 0.f;
-  if (V8) {
-    for (int c = (threadIdx.x & 63) * 8; c < d; c += 512) {
-      float a[8], b[8];
-      load8<T>(xn + row * d + c, a); load8<T>(dxn + row * d + c, b);
-#pragma unroll
-      for (int e = 0; e < 8; e++) s += a[e] * b[e];
-    }
-  } else {
-    for (int c = threadIdx.x & 63; c < d; c += 64) s += Elem<T>::ld(xn + row * d + c) * Elem<T>::ld(dxn + row * d + c);
-  }
-  s = wave_sum(s);
-  const float r = inv[row] * (g ? g[0] : 1.f);
-  if (V8) {
-    for (int c = (threadIdx.x & 63) * 8; c < d; c += 512) {
-      float a[8], b[8];
-      load8<T>(xn + row * d + c, a); load8<T>(dxn + row * d + c, b);
-#pragma unroll
-      for (int e = 0; e < 8; e++) b[e] = (b[e] - a[e] * s) * r;
-      store8<T>(dx + row * d + c, b);
-    }
-    return;
-  }
-  for (int c = threadIdx.x & 63; c < d; c += 64)
-    Elem<T>::st(dx + row * d + c, (Elem<T>::ld(dxn + row * d + c) - Elem<T>::ld(xn + row * d + c) * s) * r);
+  row_l2_normalize_bwd<T, V8>(xn + row * d, dxn + row * d, inv + row, g, dx + row * d, threadIdx.x & 63, d);
 }
 // sim: (lines, S, S) f32.  One block per line; thread = column j: lse_j = log sum_r exp(sim[r][j]);
 // line_loss = mean_j (lse_j - sim[j][j]);   dsim[r][j] = (exp(sim[r][j] - lse_j) - [r==j]) / (S * lines)
@@ -240,10 +167,8 @@ __global__ __launch_bounds__(256) void ntxent_cols_k(const float* sim, float* li
   const float* s = sim + (long long)blockIdx.x * S * S;
   float acc = 0.f;
   for (int j = threadIdx.x; j < S; j += 256) {
-    float mx = -INFINITY;
-    for (int r = 0; r < S; r++) mx = fmaxf(mx, s[(long long)r * S + j]);
-    float sum = 0.f;
-    for (int r = 0; r < S; r++) sum += expf(s[(long long)r * S + j] - mx);
+    float mx, sum;
+    col_max_sumexp(s, j, S, S, mx, sum);
     const float lse = logf(sum) + mx;
     acc += lse - s[(long long)j * S + j];
     if (dsim) {
@@ -252,10 +177,8 @@ __global__ __launch_bounds__(256) void ntxent_cols_k(const float* sim, float* li
       for (int r = 0; r < S; r++) Elem<T>::st(o + (long long)r * S + j, (expf(s[(long long)r * S + j] - lse) - (r == j ? 1.f : 0.f)) * w);
     }
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) line_loss[blockIdx.x] = ((sm[0] + sm[1]) + (sm[2] + sm[3])) / (float)S;
+  acc = block_sum4(acc, sm);
+  if (threadIdx.x == 0) line_loss[blockIdx.x] = acc / (float)S;
 }
 
 
@@ -314,23 +237,14 @@ __global__ __launch_bounds__(256) void ntxent_cols_cross_k(const float* sim, con
   const int own = own0 + (int)l;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int j = tid; j < S; j += 256) {
-    float mx = -INFINITY;
-    for (int r = 0; r < S; r++) mx = fmaxf(mx, s[(long long)r * S + j]);
-    float sum = 0.f;
-    for (int r = 0; r < S; r++) sum += expf(s[(long long)r * S + j] - mx);
+    float mx, sum;
+    col_max_sumexp(s, j, S, S, mx, sum);
     cmx[j] = mx; csum[j] = sum;
   }
   __syncthreads();
   for (int j = wave; j < S; j += 4) {
-    const float* row = cr + (long long)j * L;
-    float mx = -INFINITY;
-    for (int c = lane; c < L; c += 64) if (c != own) mx = fmaxf(mx, row[c]);
-    mx = wave_max(mx);
-    const float m1 = cmx[j], m = fmaxf(m1, mx);
-    float sum = 0.f;
-    for (int c = lane; c < L; c += 64) if (c != own) sum += expf(row[c] - m);
-    sum = wave_sum(sum);
-    if (lane == 0) clse[j] = logf(csum[j] * expf(m1 - m) + sum) + m;
+    const float lse = row_join_lse(cr + (long long)j * L, L, own, lane, cmx[j], csum[j]);
+    if (lane == 0) clse[j] = lse;
   }
   __syncthreads();
   const float w = 1.0f / ((float)S * (float)lines);
@@ -351,10 +265,8 @@ __global__ __launch_bounds__(256) void ntxent_cols_cross_k(const float* sim, con
       for (int c = lane; c < L; c += 64) Elem<T>::st(o + c, c == own ? 0.f : expf(row[c] - lse) * w);
     }
   }
-  acc = wave_sum(acc);
-  if (lane == 0) red[wave] = acc;
-  __syncthreads();
-  if (tid == 0) line_loss[l] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)S;
+  acc = block_sum4(acc, red);
+  if (tid == 0) line_loss[l] = acc / (float)S;
 }
 
 extern "C" int pero_sqdiff_rows(const void* x, const int64_t* ix, const void* y, const int64_t* iy, float* partial, float* out,
@@ -363,10 +275,8 @@ extern "C" int pero_sqdiff_rows(const void* x, const int64_t* ix, const void* y,
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((unsigned)((n + 3) / 4)), block(256);
   const bool v8 = v8_ok(d, dtype, {x, y});
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((sqdiff_rows_k<T, true>), grid, block, 0, st, (const T*)x, ix, (const T*)y, iy, partial, (long long)n, (int)d); \
-                        else hipLaunchKernelGGL((sqdiff_rows_k<T, false>), grid, block, 0, st, (const T*)x, ix, (const T*)y, iy, partial, (long long)n, (int)d); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((sqdiff_rows_k<T, decltype(V)::value>), grid, block, 0, st, (const T*)x, ix, (const T*)y, iy, partial, (long long)n, (int)d); }); }), "bad dtype");
   hipLaunchKernelGGL(sum_scale_k, dim3(1), dim3(256), 0, st, partial, out, (long long)n, scale);
   PERO_CHECK_LAUNCH("pero_sqdiff_rows");
   return PERO_OK;
@@ -376,10 +286,8 @@ extern "C" int pero_sqdiff_rows_bwd(const void* x, const int64_t* ix, const void
   PERO_REQUIRE(x && y && ix && iy && dx && dy && n > 0 && d > 0, "pero_sqdiff_rows_bwd: bad arguments");
   dim3 grid((unsigned)((n + 3) / 4)), block(256);
   const bool v8 = v8_ok(d, dtype, {x, y, dx, dy});
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((sqdiff_rows_bwd_k<T, true>), grid, block, 0, (hipStream_t)stream, (const T*)x, ix, (const T*)y, iy, (T*)dx, (T*)dy, g, coef, (long long)n, (int)d); \
-                        else hipLaunchKernelGGL((sqdiff_rows_bwd_k<T, false>), grid, block, 0, (hipStream_t)stream, (const T*)x, ix, (const T*)y, iy, (T*)dx, (T*)dy, g, coef, (long long)n, (int)d); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((sqdiff_rows_bwd_k<T, decltype(V)::value>), grid, block, 0, (hipStream_t)stream, (const T*)x, ix, (const T*)y, iy, (T*)dx, (T*)dy, g, coef, (long long)n, (int)d); }); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_sqdiff_rows_bwd");
   return PERO_OK;
 }
@@ -394,10 +302,8 @@ extern "C" int pero_center_cols(const void* z, const float* colsum, void* zc, fl
   PERO_REQUIRE(z && colsum && zc && sumsq && m > 1 && m_pad >= m && d > 0 && d % 8 == 0, "pero_center_cols: bad arguments (d %% 8 == 0)");
   dim3 grid((unsigned)((d + 255) / 256), (unsigned)((m_pad + 127) / 128)), block(256);
   const bool v8 = v8_ok(d, dtype, {z, zc});
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((center_cols_k<T, true>), grid, block, 0, (hipStream_t)stream, (const T*)z, colsum, (T*)zc, sumsq, (long long)m, (long long)m_pad, (int)d); \
-                        else hipLaunchKernelGGL((center_cols_k<T, false>), grid, block, 0, (hipStream_t)stream, (const T*)z, colsum, (T*)zc, sumsq, (long long)m, (long long)m_pad, (int)d); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((center_cols_k<T, decltype(V)::value>), grid, block, 0, (hipStream_t)stream, (const T*)z, colsum, (T*)zc, sumsq, (long long)m, (long long)m_pad, (int)d); }); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_center_cols");
   return PERO_OK;
 }
@@ -412,9 +318,8 @@ extern "C" int pero_vicreg_cov(const float* cov, const float* cvar, void* G, flo
                                float wv, float wc, int dtype, void* stream) {
   PERO_REQUIRE(cov && cvar && G && rowpart && loss_cov && d > 0 && m > 1, "pero_vicreg_cov: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-#define L_(T, ...) hipLaunchKernelGGL((vicreg_cov_k<T>), dim3((unsigned)d), dim3(256), 0, st, cov, cvar, (T*)G, rowpart, (int)d, (long long)m, wv, wc)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((vicreg_cov_k<T>), dim3((unsigned)d), dim3(256), 0, st, cov, cvar, (T*)G, rowpart, (int)d, (long long)m, wv, wc); }), "bad dtype");
   hipLaunchKernelGGL(sum_scale_k, dim3(1), dim3(256), 0, st, rowpart, loss_cov, (long long)d, 1.0f / (float)d);
   PERO_CHECK_LAUNCH("pero_vicreg_cov");
   return PERO_OK;
@@ -424,10 +329,8 @@ extern "C" int pero_scatter_add_rows_scaled(const void* src, const int64_t* inde
   PERO_REQUIRE(src && index && dst && n > 0 && d > 0, "pero_scatter_add_rows_scaled: bad arguments");
   dim3 grid((unsigned)((n + 3) / 4)), block(256);
   const bool v8 = v8_ok(d, dtype, {src, dst});
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((scatter_add_scaled_k<T, true>), grid, block, 0, (hipStream_t)stream, (const T*)src, index, (T*)dst, g, (long long)n, (int)d); \
-                        else hipLaunchKernelGGL((scatter_add_scaled_k<T, false>), grid, block, 0, (hipStream_t)stream, (const T*)src, index, (T*)dst, g, (long long)n, (int)d); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((scatter_add_scaled_k<T, decltype(V)::value>), grid, block, 0, (hipStream_t)stream, (const T*)src, index, (T*)dst, g, (long long)n, (int)d); }); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_scatter_add_rows_scaled");
   return PERO_OK;
 }
@@ -435,10 +338,8 @@ extern "C" int pero_rownorm_fwd(const void* x, void* xn, float* inv, int64_t row
   PERO_REQUIRE(x && xn && inv && rows > 0 && d > 0, "pero_rownorm_fwd: bad arguments");
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   const bool v8 = v8_ok(d, dtype, {x, xn});
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((rownorm_fwd_k<T, true>), grid, block, 0, (hipStream_t)stream, (const T*)x, (T*)xn, inv, (long long)rows, (int)d); \
-                        else hipLaunchKernelGGL((rownorm_fwd_k<T, false>), grid, block, 0, (hipStream_t)stream, (const T*)x, (T*)xn, inv, (long long)rows, (int)d); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((rownorm_fwd_k<T, decltype(V)::value>), grid, block, 0, (hipStream_t)stream, (const T*)x, (T*)xn, inv, (long long)rows, (int)d); }); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_rownorm_fwd");
   return PERO_OK;
 }
@@ -447,10 +348,8 @@ extern "C" int pero_rownorm_bwd(const void* xn, const void* dxn, const float* in
   PERO_REQUIRE(xn && dxn && inv && dx && rows > 0 && d > 0, "pero_rownorm_bwd: bad arguments");
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   const bool v8 = v8_ok(d, dtype, {xn, dxn, dx});
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((rownorm_bwd_k<T, true>), grid, block, 0, (hipStream_t)stream, (const T*)xn, (const T*)dxn, inv, g, (T*)dx, (long long)rows, (int)d); \
-                        else hipLaunchKernelGGL((rownorm_bwd_k<T, false>), grid, block, 0, (hipStream_t)stream, (const T*)xn, (const T*)dxn, inv, g, (T*)dx, (long long)rows, (int)d); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((rownorm_bwd_k<T, decltype(V)::value>), grid, block, 0, (hipStream_t)stream, (const T*)xn, (const T*)dxn, inv, g, (T*)dx, (long long)rows, (int)d); }); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_rownorm_bwd");
   return PERO_OK;
 }
@@ -458,9 +357,8 @@ extern "C" int pero_ntxent_cols(const float* sim, float* line_loss, float* loss_
                                 void* stream) {
   PERO_REQUIRE(sim && line_loss && loss_out && lines > 0 && S > 0, "pero_ntxent_cols: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-#define L_(T, ...) hipLaunchKernelGGL((ntxent_cols_k<T>), dim3((unsigned)lines), dim3(256), 0, st, sim, line_loss, (T*)dsim, (int)S, (int)lines)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ntxent_cols_k<T>), dim3((unsigned)lines), dim3(256), 0, st, sim, line_loss, (T*)dsim, (int)S, (int)lines); }), "bad dtype");
   hipLaunchKernelGGL(sum_scale_k, dim3(1), dim3(256), 0, st, line_loss, loss_out, (long long)lines, 1.0f / (float)lines);
   PERO_CHECK_LAUNCH("pero_ntxent_cols");
   return PERO_OK;
@@ -470,9 +368,8 @@ extern "C" int pero_line_mean(const void* x, float* out, int64_t lines, int64_t 
   PERO_REQUIRE(x && out && lines > 0 && S > 0 && d > 0 && d % 8 == 0 && lines < 65536, "pero_line_mean: bad arguments (d %% 8 == 0)");
   PERO_REQUIRE(v8_ok(d, dtype, {x}) && aligned16(out), "pero_line_mean: 16-byte aligned rows");
   dim3 grid((unsigned)((d / 8 + 255) / 256), (unsigned)lines), block(256);
-#define L_(T, ...) hipLaunchKernelGGL((line_mean_k<T>), grid, block, 0, (hipStream_t)stream, (const T*)x, out, (int)S, (int)d)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((line_mean_k<T>), grid, block, 0, (hipStream_t)stream, (const T*)x, out, (int)S, (int)d); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_line_mean");
   return PERO_OK;
 }
@@ -480,9 +377,8 @@ extern "C" int pero_add_line_rows(void* dst, const float* src, int64_t lines, in
   PERO_REQUIRE(dst && src && lines > 0 && S > 0 && d > 0 && d % 8 == 0 && lines < 65536, "pero_add_line_rows: bad arguments (d %% 8 == 0)");
   PERO_REQUIRE(v8_ok(d, dtype, {dst}) && aligned16(src), "pero_add_line_rows: 16-byte aligned rows");
   dim3 grid((unsigned)((d / 8 + 255) / 256), (unsigned)lines), block(256);
-#define L_(T, ...) hipLaunchKernelGGL((add_line_rows_k<T>), grid, block, 0, (hipStream_t)stream, (T*)dst, src, (int)S, (int)d, scale)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((add_line_rows_k<T>), grid, block, 0, (hipStream_t)stream, (T*)dst, src, (int)S, (int)d, scale); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_add_line_rows");
   return PERO_OK;
 }
@@ -491,10 +387,8 @@ extern "C" int pero_ntxent_cols_cross(const float* sim, const float* cross, floa
   PERO_REQUIRE(sim && cross && line_loss && loss_out && lines > 0 && S > 0 && L > 0 && own0 >= 0 && own0 + lines <= L && S <= 4096,
                "pero_ntxent_cols_cross: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-#define L_(T, ...) hipLaunchKernelGGL((ntxent_cols_cross_k<T>), dim3((unsigned)lines), dim3(256), (size_t)(3 * S * sizeof(float)), st, sim, cross, line_loss, \
-                                      (T*)dsim, (T*)dcross, (int)S, (int)L, (int)lines, (int)own0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ntxent_cols_cross_k<T>), dim3((unsigned)lines), dim3(256), (size_t)(3 * S * sizeof(float)), st, sim, cross, line_loss, (T*)dsim, (T*)dcross, (int)S, (int)L, (int)lines, (int)own0); }), "bad dtype");
   hipLaunchKernelGGL(sum_scale_k, dim3(1), dim3(256), 0, st, line_loss, loss_out, (long long)lines, 1.0f / (float)lines);
   PERO_CHECK_LAUNCH("pero_ntxent_cols_cross");
   return PERO_OK;

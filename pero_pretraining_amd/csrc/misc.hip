@@ -1,5 +1,7 @@
 // Front end (u8 line images -> patch rows), casts, Adam, row gather / scatter.  All HBM-bound.
 #include "flat_tiles.hpp"
+#include "dispatch.hpp"
+#include "rows.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // patch rows from u8 NHWC line images.  One block = one line x 16 consecutive patches: the
@@ -168,9 +170,8 @@ extern "C" int pero_patches_from_u8(const uint8_t* images, const int64_t* mask, 
   const size_t lds = (size_t)H * ((((PT_TOK * P * C + 3) >> 2) | 1) << 2) + PT_TOK * sizeof(int);
   PERO_REQUIRE(lds <= 65536, "pero_patches_from_u8: H*16*P*C = %zu bytes exceeds the LDS staging budget", lds);
   dim3 grid((unsigned)((S + PT_TOK - 1) / PT_TOK), (unsigned)N), block(256);
-  if (dtype == PERO_F32) hipLaunchKernelGGL((patches_u8_k<float>), grid, block, lds, (hipStream_t)stream, images, mask, tile, (float*)patches, (int)H, (int)W, (int)C, (int)P, S, (int)ld_out);
-  else if (dtype == PERO_BF16) hipLaunchKernelGGL((patches_u8_k<bf16raw>), grid, block, lds, (hipStream_t)stream, images, mask, tile, (bf16raw*)patches, (int)H, (int)W, (int)C, (int)P, S, (int)ld_out);
-  else PERO_REQUIRE(false, "pero_patches_from_u8: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((patches_u8_k<T>), grid, block, lds, (hipStream_t)stream, images, mask, tile, (T*)patches, (int)H, (int)W, (int)C, (int)P, S, (int)ld_out); }), "pero_patches_from_u8: bad dtype");
   PERO_CHECK_LAUNCH("pero_patches_from_u8");
   return PERO_OK;
 }
@@ -180,9 +181,8 @@ extern "C" int pero_patches_from_f32(const float* images, const int64_t* mask, c
   PERO_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && P > 0 && W % P == 0 && ld_out >= C * H * P, "pero_patches_from_f32: bad sizes");
   const long long total = (long long)N * (W / P) * ld_out;
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == PERO_F32) hipLaunchKernelGGL((patches_f32_k<float>), grid, block, 0, (hipStream_t)stream, images, mask, tile, (float*)patches, total, (int)H, (int)W, (int)C, (int)P, (int)(W / P), (int)ld_out);
-  else if (dtype == PERO_BF16) hipLaunchKernelGGL((patches_f32_k<bf16raw>), grid, block, 0, (hipStream_t)stream, images, mask, tile, (bf16raw*)patches, total, (int)H, (int)W, (int)C, (int)P, (int)(W / P), (int)ld_out);
-  else PERO_REQUIRE(false, "pero_patches_from_f32: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((patches_f32_k<T>), grid, block, 0, (hipStream_t)stream, images, mask, tile, (T*)patches, total, (int)H, (int)W, (int)C, (int)P, (int)(W / P), (int)ld_out); }), "pero_patches_from_f32: bad dtype");
   PERO_CHECK_LAUNCH("pero_patches_from_f32");
   return PERO_OK;
 }
@@ -269,9 +269,8 @@ extern "C" int pero_zero_fill(void* p, int64_t nbytes, void* stream) {
 }
 extern "C" int pero_scale(void* x, int64_t n, float scale, int dtype, void* stream) {
   PERO_REQUIRE(x && n > 0, "pero_scale: bad arguments");
-  if (dtype == PERO_F32) hipLaunchKernelGGL((scale_k<float>), dim3(grid_for(n, 1)), dim3(256), 0, (hipStream_t)stream, (float*)x, (long long)n, scale);
-  else if (dtype == PERO_BF16) hipLaunchKernelGGL((scale_k<bf16raw>), dim3(grid_for(n, 1)), dim3(256), 0, (hipStream_t)stream, (bf16raw*)x, (long long)n, scale);
-  else PERO_REQUIRE(false, "pero_scale: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((scale_k<T>), dim3(grid_for(n, 1)), dim3(256), 0, (hipStream_t)stream, (T*)x, (long long)n, scale); }), "pero_scale: bad dtype");
   PERO_CHECK_LAUNCH("pero_scale");
   return PERO_OK;
 }
@@ -352,40 +351,31 @@ __global__ __launch_bounds__(256) void scatter_add_rows_k(const T* src, const in
   if (row >= n_idx) return;
   const int lane = threadIdx.x & 63;
   T* o = dst + index[row] * d;
-  if (V16) {
-    for (int c = lane * 8; c < d; c += 512) {
-      float a[8], b[8];
-      load8<T>(o + c, a); load8<T>(src + row * d + c, b);
+  constexpr int W = V16 ? 8 : 1;
+  row_walk<W>(lane, d, [=](int c) {
+    float a[W], b[W];
+    load_w<W>(o + c, a); load_w<W>(src + row * d + c, b);
 #pragma unroll
-      for (int e = 0; e < 8; e++) a[e] += b[e];
-      store8<T>(o + c, a);
-    }
-    return;
-  }
-  for (int c = lane; c < d; c += 64) Elem<T>::st(o + c, Elem<T>::ld(o + c) + Elem<T>::ld(src + row * d + c));
+    for (int e = 0; e < W; e++) a[e] += b[e];
+    store_w<W>(o + c, a);
+  });
 }
 extern "C" int pero_gather_rows(const void* src, const int64_t* index, void* dst, int64_t n_idx, int64_t n_rows_out, int64_t d,
                                 int dtype, void* stream) {
   PERO_REQUIRE(src && dst && (index || n_idx == 0) && n_rows_out >= n_idx && n_rows_out > 0 && d > 0, "pero_gather_rows: bad arguments");
   dim3 grid((unsigned)((n_rows_out + 3) / 4)), block(256);
-  const bool v16 = d % 8 == 0 && aligned16(src) && aligned16(dst);
-#define G_(T, V) hipLaunchKernelGGL((gather_rows_k<T, V>), grid, block, 0, (hipStream_t)stream, (const T*)src, index, (T*)dst, (long long)n_idx, (long long)n_rows_out, (int)d)
-  if (dtype == PERO_F32) { if (v16) G_(float, true); else G_(float, false); }
-  else if (dtype == PERO_BF16) { if (v16) G_(bf16raw, true); else G_(bf16raw, false); }
-  else PERO_REQUIRE(false, "pero_gather_rows: bad dtype");
-#undef G_
+  const bool v16 = v8_ok(d, dtype, {src, dst});
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v16, [&](auto V) {
+    hipLaunchKernelGGL((gather_rows_k<T, decltype(V)::value>), grid, block, 0, (hipStream_t)stream, (const T*)src, index, (T*)dst, (long long)n_idx, (long long)n_rows_out, (int)d); }); }), "pero_gather_rows: bad dtype");
   PERO_CHECK_LAUNCH("pero_gather_rows");
   return PERO_OK;
 }
 extern "C" int pero_scatter_add_rows(const void* src, const int64_t* index, void* dst, int64_t n_idx, int64_t d, int dtype, void* stream) {
   PERO_REQUIRE(src && dst && index && n_idx > 0 && d > 0, "pero_scatter_add_rows: bad arguments");
   dim3 grid((unsigned)((n_idx + 3) / 4)), block(256);
-  const bool v16 = d % 8 == 0 && aligned16(src) && aligned16(dst);
-#define S_(T, V) hipLaunchKernelGGL((scatter_add_rows_k<T, V>), grid, block, 0, (hipStream_t)stream, (const T*)src, index, (T*)dst, (long long)n_idx, (int)d)
-  if (dtype == PERO_F32) { if (v16) S_(float, true); else S_(float, false); }
-  else if (dtype == PERO_BF16) { if (v16) S_(bf16raw, true); else S_(bf16raw, false); }
-  else PERO_REQUIRE(false, "pero_scatter_add_rows: bad dtype");
-#undef S_
+  const bool v16 = v8_ok(d, dtype, {src, dst});
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v16, [&](auto V) {
+    hipLaunchKernelGGL((scatter_add_rows_k<T, decltype(V)::value>), grid, block, 0, (hipStream_t)stream, (const T*)src, index, (T*)dst, (long long)n_idx, (int)d); }); }), "pero_scatter_add_rows: bad dtype");
   PERO_CHECK_LAUNCH("pero_scatter_add_rows");
   return PERO_OK;
 }

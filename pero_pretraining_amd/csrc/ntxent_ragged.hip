@@ -2,8 +2,10 @@
 // mark with 1.  The selected rows of a line are compacted to the front of a block of Sp >= S rows (Sp a multiple of 128 in bf16, so
 // that the three per-line products meet pero_gemm's tile conditions at every S); rows behind the line's count m are zero, and the
 // column kernel writes zeros outside the m x m block of its gradient, so the products may read whole padded blocks.
-// Everything here is HBM-bound row / column work in f32 statistics, with the arithmetic of the dense kernels of losses.hip.
-#include "losses_common.hpp"
+// Everything here is HBM-bound row / column work in f32 statistics; the row arithmetic and the halves of the column log-sum-exp are the
+// functions of rows.hpp that the dense kernels of losses.hip call too.
+#include "dispatch.hpp"
+#include "rows.hpp"
 
 // One wave per line: rank of every selected position among the line's selected positions (ballot + popcount prefix over chunks of 64
 // positions), -1 elsewhere; count[l] = the number of selected positions, -1 when the two views select different numbers.
@@ -30,8 +32,8 @@ __global__ __launch_bounds__(256) void ntxent_slots_k(const unsigned char* im1, 
   if (lane == 0) count[l] = c1 == c2 ? c1 : -1;
 }
 
-// One wave per (line, r), r < Sp.  Position r of the line, when selected (slot k >= 0), is L2-normalised into compact row k (rownorm_fwd_k's
-// arithmetic); compact row r >= m is written as zeros (inv 0).  A line with count <= 0 becomes an all-zero block.
+// One wave per (line, r), r < Sp.  Position r of the line, when selected (slot k >= 0), is L2-normalised into compact row k
+// (row_l2_normalize, as in rownorm_fwd_k); compact row r >= m is written as zeros (inv 0).  A line with count <= 0 becomes an all-zero block.
 template <typename T, bool V8>
 __global__ __launch_bounds__(256) void ntxent_rows_fwd_k(const T* x, const int* slot, const int* count, T* xn, float* inv, long long lines,
                                                          int ncount, int S, int Sp, int d) {
@@ -42,49 +44,18 @@ __global__ __launch_bounds__(256) void ntxent_rows_fwd_k(const T* x, const int* 
   const int cnt = count[l % ncount];
   const int m = cnt > 0 ? (cnt < Sp ? cnt : Sp) : 0;
   if (r >= m) {
-    T* o = xn + idx * d;
-    if (V8) {
-      const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      for (int c = lane * 8; c < d; c += 512) store8<T>(o + c, z);
-    } else {
-      for (int c = lane; c < d; c += 64) Elem<T>::st(o + c, 0.f);
-    }
+    row_zero<T, V8>(xn + idx * d, lane, d);
     if (lane == 0) inv[idx] = 0.f;
   }
   if (r >= S) return;
   const int k = slot[l * S + r];
   if (k < 0 || k >= m) return;
-  const T* src = x + (l * S + r) * d;
-  T* dst = xn + (l * Sp + k) * d;
-  float s = 0.f;
-  if (V8) {
-    for (int c = lane * 8; c < d; c += 512) {
-      float v[8];
-      load8<T>(src + c, v);
-#pragma unroll
-      for (int e = 0; e < 8; e++) s += v[e] * v[e];
-    }
-  } else {
-    for (int c = lane; c < d; c += 64) { const float v = Elem<T>::ld(src + c); s += v * v; }
-  }
-  s = wave_sum(s);
-  const float rn = 1.0f / fmaxf(sqrtf(s), 1e-12f);  // F.normalize eps
+  const float rn = row_l2_normalize<T, V8>(x + (l * S + r) * d, xn + (l * Sp + k) * d, lane, d);
   if (lane == 0) inv[l * Sp + k] = rn;
-  if (V8) {
-    for (int c = lane * 8; c < d; c += 512) {
-      float v[8];
-      load8<T>(src + c, v);
-#pragma unroll
-      for (int e = 0; e < 8; e++) v[e] *= rn;
-      store8<T>(dst + c, v);
-    }
-    return;
-  }
-  for (int c = lane; c < d; c += 64) Elem<T>::st(dst + c, Elem<T>::ld(src + c) * rn);
 }
 
-// One wave per (line, position): a selected position reads its compact row k: dx = (dxn_k - xn_k <xn_k, dxn_k>) inv_k g (rownorm_bwd_k);
-// every other position, and every position of a line with count <= 0, is written as zeros.
+// One wave per (line, position): a selected position reads its compact row k: dx = (dxn_k - xn_k <xn_k, dxn_k>) inv_k g
+// (row_l2_normalize_bwd, as in rownorm_bwd_k); every other position, and every position of a line with count <= 0, is written as zeros.
 template <typename T, bool V8>
 __global__ __launch_bounds__(256) void ntxent_rows_bwd_k(const T* xn, const T* dxn, const float* inv, const int* slot, const int* count,
                                                          const float* g, T* dx, long long lines, int ncount, int S, int Sp, int d) {
@@ -94,42 +65,9 @@ __global__ __launch_bounds__(256) void ntxent_rows_bwd_k(const T* xn, const T* d
   const int lane = threadIdx.x & 63;
   const int k = slot[idx], m = count[l % ncount];
   T* o = dx + idx * d;
-  if (k < 0 || k >= m || k >= Sp) {
-    if (V8) {
-      const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      for (int c = lane * 8; c < d; c += 512) store8<T>(o + c, z);
-    } else {
-      for (int c = lane; c < d; c += 64) Elem<T>::st(o + c, 0.f);
-    }
-    return;
-  }
+  if (k < 0 || k >= m || k >= Sp) { row_zero<T, V8>(o, lane, d); return; }
   const long long row = l * Sp + k;
-  const T* a_ = xn + row * d;
-  const T* b_ = dxn + row * d;
-  float s = 0.f;
-  if (V8) {
-    for (int c = lane * 8; c < d; c += 512) {
-      float a[8], b[8];
-      load8<T>(a_ + c, a); load8<T>(b_ + c, b);
-#pragma unroll
-      for (int e = 0; e < 8; e++) s += a[e] * b[e];
-    }
-  } else {
-    for (int c = lane; c < d; c += 64) s += Elem<T>::ld(a_ + c) * Elem<T>::ld(b_ + c);
-  }
-  s = wave_sum(s);
-  const float r = inv[row] * (g ? g[0] : 1.f);
-  if (V8) {
-    for (int c = lane * 8; c < d; c += 512) {
-      float a[8], b[8];
-      load8<T>(a_ + c, a); load8<T>(b_ + c, b);
-#pragma unroll
-      for (int e = 0; e < 8; e++) b[e] = (b[e] - a[e] * s) * r;
-      store8<T>(o + c, b);
-    }
-    return;
-  }
-  for (int c = lane; c < d; c += 64) Elem<T>::st(o + c, (Elem<T>::ld(b_ + c) - Elem<T>::ld(a_ + c) * s) * r);
+  row_l2_normalize_bwd<T, V8>(xn + row * d, dxn + row * d, inv + row, g, o, lane, d);
 }
 
 // One workgroup per line; m = count[l].  ntxent_cols_k / ntxent_cols_cross_k (losses.hip) restricted to the leading m x m block of the line's
@@ -158,25 +96,16 @@ __global__ __launch_bounds__(256) void ntxent_cols_ragged_k(const float* sim, co
     return;
   }
   for (int j = tid; j < m; j += 256) {
-    float mx = -INFINITY;
-    for (int r = 0; r < m; r++) mx = fmaxf(mx, s[(long long)r * Sp + j]);
-    float sum = 0.f;
-    for (int r = 0; r < m; r++) sum += expf(s[(long long)r * Sp + j] - mx);
+    float mx, sum;
+    col_max_sumexp(s, j, m, Sp, mx, sum);
     cmx[j] = mx; csum[j] = sum;
     if (!cr) clse[j] = logf(sum) + mx;
   }
   __syncthreads();
   if (cr) {
     for (int j = wave; j < m; j += 4) {
-      const float* row = cr + (long long)j * L;
-      float mx = -INFINITY;
-      for (int c = lane; c < L; c += 64) if (c != own) mx = fmaxf(mx, row[c]);
-      mx = wave_max(mx);
-      const float m1 = cmx[j], mm = fmaxf(m1, mx);
-      float sum = 0.f;
-      for (int c = lane; c < L; c += 64) if (c != own) sum += expf(row[c] - mm);
-      sum = wave_sum(sum);
-      if (lane == 0) clse[j] = logf(csum[j] * expf(m1 - mm) + sum) + mm;
+      const float lse = row_join_lse(cr + (long long)j * L, L, own, lane, cmx[j], csum[j]);
+      if (lane == 0) clse[j] = lse;
     }
     __syncthreads();
   }
@@ -204,10 +133,8 @@ __global__ __launch_bounds__(256) void ntxent_cols_ragged_k(const float* sim, co
       }
     }
   }
-  acc = wave_sum(acc);
-  if (lane == 0) red[wave] = acc;
-  __syncthreads();
-  if (tid == 0) line_loss[l] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)m;
+  acc = block_sum4(acc, red);
+  if (tid == 0) line_loss[l] = acc / (float)m;
 }
 
 // pooled[l][c] = mean over the first count[l] rows of the line's compact block (f32 out; zeros for count <= 0)
@@ -267,10 +194,8 @@ extern "C" int pero_ntxent_rows_fwd(const void* x, const int* slot, const int* c
                d > 0 && d < (1ll << 31) && lines * Sp < (1ll << 32), "pero_ntxent_rows_fwd: bad arguments (S <= Sp <= 4096, lines a multiple of count_lines)");
   dim3 grid((unsigned)((lines * Sp + 3) / 4)), block(256);
   const bool v8 = v8_ok(d, dtype, {x, xn});
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((ntxent_rows_fwd_k<T, true>), grid, block, 0, (hipStream_t)stream, (const T*)x, slot, count, (T*)xn, inv, (long long)lines, (int)count_lines, (int)S, (int)Sp, (int)d); \
-                        else hipLaunchKernelGGL((ntxent_rows_fwd_k<T, false>), grid, block, 0, (hipStream_t)stream, (const T*)x, slot, count, (T*)xn, inv, (long long)lines, (int)count_lines, (int)S, (int)Sp, (int)d); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((ntxent_rows_fwd_k<T, decltype(V)::value>), grid, block, 0, (hipStream_t)stream, (const T*)x, slot, count, (T*)xn, inv, (long long)lines, (int)count_lines, (int)S, (int)Sp, (int)d); }); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_ntxent_rows_fwd");
   return PERO_OK;
 }
@@ -280,10 +205,8 @@ extern "C" int pero_ntxent_rows_bwd(const void* xn, const void* dxn, const float
                Sp <= 4096 && d > 0 && d < (1ll << 31) && lines * S < (1ll << 32), "pero_ntxent_rows_bwd: bad arguments (S <= Sp <= 4096, lines a multiple of count_lines)");
   dim3 grid((unsigned)((lines * S + 3) / 4)), block(256);
   const bool v8 = v8_ok(d, dtype, {xn, dxn, dx});
-#define L_(T, ...) do { if (v8) hipLaunchKernelGGL((ntxent_rows_bwd_k<T, true>), grid, block, 0, (hipStream_t)stream, (const T*)xn, (const T*)dxn, inv, slot, count, g, (T*)dx, (long long)lines, (int)count_lines, (int)S, (int)Sp, (int)d); \
-                        else hipLaunchKernelGGL((ntxent_rows_bwd_k<T, false>), grid, block, 0, (hipStream_t)stream, (const T*)xn, (const T*)dxn, inv, slot, count, g, (T*)dx, (long long)lines, (int)count_lines, (int)S, (int)Sp, (int)d); } while (0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(v8, [&](auto V) {
+    hipLaunchKernelGGL((ntxent_rows_bwd_k<T, decltype(V)::value>), grid, block, 0, (hipStream_t)stream, (const T*)xn, (const T*)dxn, inv, slot, count, g, (T*)dx, (long long)lines, (int)count_lines, (int)S, (int)Sp, (int)d); }); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_ntxent_rows_bwd");
   return PERO_OK;
 }
@@ -292,10 +215,9 @@ extern "C" int pero_ntxent_cols_ragged(const float* sim, const int* count, const
   PERO_REQUIRE(sim && count && line_loss && loss_out && lines > 0 && lines < (1ll << 31) && Sp > 0 && Sp <= 4096, "pero_ntxent_cols_ragged: bad arguments (Sp <= 4096)");
   PERO_REQUIRE(cross ? (L > 0 && own0 >= 0 && own0 + lines <= L) : (dcross == nullptr), "pero_ntxent_cols_ragged: cross needs 0 <= own0, own0 + lines <= L; dcross needs cross");
   hipStream_t st = (hipStream_t)stream;
-#define L_(T, ...) hipLaunchKernelGGL((ntxent_cols_ragged_k<T>), dim3((unsigned)lines), dim3(256), (size_t)(3 * Sp * sizeof(float)), st, sim, count, cross, \
-                                      line_loss, (T*)dsim, (T*)dcross, (int)Sp, (int)(cross ? L : 0), (int)lines, (int)own0)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ntxent_cols_ragged_k<T>), dim3((unsigned)lines), dim3(256), (size_t)(3 * Sp * sizeof(float)), st, sim, count, cross,
+                       line_loss, (T*)dsim, (T*)dcross, (int)Sp, (int)(cross ? L : 0), (int)lines, (int)own0); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_ntxent_cols_ragged");
   return pero_sum_scale(line_loss, loss_out, lines, 1.0f / (float)lines, stream);
 }
@@ -303,9 +225,8 @@ extern "C" int pero_line_mean_ragged(const void* x, const int* count, float* out
   PERO_REQUIRE(x && count && out && lines > 0 && Sp > 0 && d > 0 && d % 8 == 0 && lines < 65536, "pero_line_mean_ragged: bad arguments (d %% 8 == 0)");
   PERO_REQUIRE(v8_ok(d, dtype, {x}) && aligned16(out), "pero_line_mean_ragged: 16-byte aligned rows");
   dim3 grid((unsigned)((d / 8 + 255) / 256), (unsigned)lines), block(256);
-#define L_(T, ...) hipLaunchKernelGGL((line_mean_ragged_k<T>), grid, block, 0, (hipStream_t)stream, (const T*)x, count, out, (int)Sp, (int)d)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((line_mean_ragged_k<T>), grid, block, 0, (hipStream_t)stream, (const T*)x, count, out, (int)Sp, (int)d); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_line_mean_ragged");
   return PERO_OK;
 }
@@ -313,9 +234,8 @@ extern "C" int pero_add_line_rows_ragged(void* dst, const float* src, const int*
   PERO_REQUIRE(dst && src && count && lines > 0 && Sp > 0 && d > 0 && d % 8 == 0 && lines < 65536, "pero_add_line_rows_ragged: bad arguments (d %% 8 == 0)");
   PERO_REQUIRE(v8_ok(d, dtype, {dst}) && aligned16(src), "pero_add_line_rows_ragged: 16-byte aligned rows");
   dim3 grid((unsigned)((d / 8 + 255) / 256), (unsigned)lines), block(256);
-#define L_(T, ...) hipLaunchKernelGGL((add_line_rows_ragged_k<T>), grid, block, 0, (hipStream_t)stream, (T*)dst, src, count, (int)Sp, (int)d)
-  DISPATCH_T(dtype, L_, 0);
-#undef L_
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((add_line_rows_ragged_k<T>), grid, block, 0, (hipStream_t)stream, (T*)dst, src, count, (int)Sp, (int)d); }), "bad dtype");
   PERO_CHECK_LAUNCH("pero_add_line_rows_ragged");
   return PERO_OK;
 }

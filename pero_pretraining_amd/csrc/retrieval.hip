@@ -9,7 +9,7 @@
 // split, 128 keys at a time, 128 bytes of depth per stage (32 f32 / 64 bf16: the LDS image is the same bytes for both, only the MFMA that
 // eats a 16-byte fragment differs).  Tiles are fetched into registers one stage ahead (zero-filled past M, N and D: ragged edges are
 // predication, there is no second kernel) and stored into a two-stage LDS ring with the 16-byte chunk index XORed with (row & 7).
-#include "common.hpp"
+#include "dispatch.hpp"
 
 #define RT_BQ 64                       // queries per workgroup
 #define RT_BN 128                      // keys per tile (32 per wave)
@@ -325,13 +325,8 @@ extern "C" int pero_sim_topk(const void* q, int64_t ldq, const void* keys, int64
   const int splits = key_splits == 0 ? pero_sim_topk_key_splits(M, N) : (int)key_splits;
   PERO_REQUIRE(splits == 1 || work, "pero_sim_topk: %d key splits need the work buffer", splits);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PERO_F32) {
-    if (k <= 4) rt_launch<float, 4>(q, keys, ldq, ldk, q_scale, key_scale, key_valid, skip, idx, val, work, M, N, D, k, splits, st);
-    else rt_launch<float, 16>(q, keys, ldq, ldk, q_scale, key_scale, key_valid, skip, idx, val, work, M, N, D, k, splits, st);
-  } else {
-    if (k <= 4) rt_launch<bf16raw, 4>(q, keys, ldq, ldk, q_scale, key_scale, key_valid, skip, idx, val, work, M, N, D, k, splits, st);
-    else rt_launch<bf16raw, 16>(q, keys, ldq, ldk, q_scale, key_scale, key_valid, skip, idx, val, work, M, N, D, k, splits, st);
-  }
+  with_elem(dtype, [&](auto t) { using T = decltype(t); with_flag(k <= 4, [&](auto small) {
+    rt_launch<T, decltype(small)::value ? 4 : 16>(q, keys, ldq, ldk, q_scale, key_scale, key_valid, skip, idx, val, work, M, N, D, k, splits, st); }); });
   PERO_CHECK_LAUNCH("pero_sim_topk");
   return PERO_OK;
 }
@@ -354,8 +349,8 @@ extern "C" int pero_inv_rownorm(const void* x, int64_t ld, float* inv, int64_t r
   const int64_t es = dtype == PERO_F32 ? 4 : 2;
   PERO_REQUIRE(ld >= D && (ld * es) % 16 == 0 && aligned16(x), "pero_inv_rownorm: rows must be 16-byte aligned (base pointer and pitch), pitch >= D");
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  if (dtype == PERO_F32) hipLaunchKernelGGL((inv_rownorm_k<float>), grid, block, 0, (hipStream_t)stream, (const float*)x, (long long)ld, inv, (long long)rows, (int)D);
-  else hipLaunchKernelGGL((inv_rownorm_k<bf16raw>), grid, block, 0, (hipStream_t)stream, (const bf16raw*)x, (long long)ld, inv, (long long)rows, (int)D);
+  with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((inv_rownorm_k<T>), grid, block, 0, (hipStream_t)stream, (const T*)x, (long long)ld, inv, (long long)rows, (int)D); });
   PERO_CHECK_LAUNCH("pero_inv_rownorm");
   return PERO_OK;
 }

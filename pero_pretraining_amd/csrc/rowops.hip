@@ -2,6 +2,8 @@
 // cross entropy, column sums.  One 64-lane wave per row (shuffle reductions, no LDS for the row
 // statistics), 16-byte global accesses, f32 statistics whatever the storage dtype.
 #include "gemm_common.hpp"
+#include "dispatch.hpp"
+#include "rows.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm forward.  d % 8 == 0, d <= 512 * NCH.  4 waves per block, one row per wave.
@@ -373,9 +375,8 @@ extern "C" int pero_layernorm_fwd(const void* x, const float* gamma, const float
   PERO_REQUIRE(rows > 0 && d > 0 && d % 8 == 0 && d <= 4096, "pero_layernorm_fwd: need d %% 8 == 0 and d <= 4096 (d=%lld)", (long long)d);
   PERO_REQUIRE(!pe || S > 0, "pero_layernorm_fwd: S must be > 0 with a positional table");
   PERO_REQUIRE(aligned16(x) && aligned16(y) && aligned16(gamma) && aligned16(beta) && (!pe || aligned16(pe)), "pero_layernorm_fwd: 16-byte alignment");
-  if (dtype == PERO_F32) ln_dispatch_fwd<float>(x, gamma, beta, pe, offsets, y, mean, rstd, rows, d, S, eps, (hipStream_t)stream);
-  else if (dtype == PERO_BF16) ln_dispatch_fwd<bf16raw>(x, gamma, beta, pe, offsets, y, mean, rstd, rows, d, S, eps, (hipStream_t)stream);
-  else PERO_REQUIRE(false, "pero_layernorm_fwd: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) {
+    ln_dispatch_fwd<decltype(t)>(x, gamma, beta, pe, offsets, y, mean, rstd, rows, d, S, eps, (hipStream_t)stream); }), "pero_layernorm_fwd: bad dtype");
   PERO_CHECK_LAUNCH("pero_layernorm_fwd");
   return PERO_OK;
 }
@@ -386,9 +387,8 @@ extern "C" int pero_layernorm_bwd(const void* dy, const void* x, const float* me
   PERO_REQUIRE(dy && x && mean && rstd && gamma && dx && dgamma && dbeta && work, "pero_layernorm_bwd: null pointer");
   PERO_REQUIRE(rows > 0 && d > 0 && d % 8 == 0 && d <= 2048, "pero_layernorm_bwd: need d %% 8 == 0 and d <= 2048 (d=%lld)", (long long)d);
   PERO_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(dx) && aligned16(gamma), "pero_layernorm_bwd: 16-byte alignment");
-  if (dtype == PERO_F32) ln_dispatch_bwd<float, false>(dy, x, mean, rstd, gamma, dx, dgamma, dbeta, dxsum, work, rows, d, (hipStream_t)stream);
-  else if (dtype == PERO_BF16) ln_dispatch_bwd<bf16raw, false>(dy, x, mean, rstd, gamma, dx, dgamma, dbeta, dxsum, work, rows, d, (hipStream_t)stream);
-  else PERO_REQUIRE(false, "pero_layernorm_bwd: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) {
+    ln_dispatch_bwd<decltype(t), false>(dy, x, mean, rstd, gamma, dx, dgamma, dbeta, dxsum, work, rows, d, (hipStream_t)stream); }), "pero_layernorm_bwd: bad dtype");
   PERO_CHECK_LAUNCH("pero_layernorm_bwd");
   return PERO_OK;
 }
@@ -399,9 +399,8 @@ extern "C" int pero_layernorm_bwd_out(const void* dy, const void* t, const float
   PERO_REQUIRE(dy && t && rstd && gamma && beta && dx && dgamma && dbeta && work, "pero_layernorm_bwd_out: null pointer");
   PERO_REQUIRE(rows > 0 && d > 0 && d % 8 == 0 && d <= 2048, "pero_layernorm_bwd_out: need d %% 8 == 0 and d <= 2048 (d=%lld)", (long long)d);
   PERO_REQUIRE(aligned16(dy) && aligned16(t) && aligned16(dx) && aligned16(gamma) && aligned16(beta), "pero_layernorm_bwd_out: 16-byte alignment");
-  if (dtype == PERO_F32) ln_dispatch_bwd<float, true>(dy, t, beta, rstd, gamma, dx, dgamma, dbeta, dxsum, work, rows, d, (hipStream_t)stream);
-  else if (dtype == PERO_BF16) ln_dispatch_bwd<bf16raw, true>(dy, t, beta, rstd, gamma, dx, dgamma, dbeta, dxsum, work, rows, d, (hipStream_t)stream);
-  else PERO_REQUIRE(false, "pero_layernorm_bwd_out: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto e) {
+    ln_dispatch_bwd<decltype(e), true>(dy, t, beta, rstd, gamma, dx, dgamma, dbeta, dxsum, work, rows, d, (hipStream_t)stream); }), "pero_layernorm_bwd_out: bad dtype");
   PERO_CHECK_LAUNCH("pero_layernorm_bwd_out");
   return PERO_OK;
 }
@@ -438,9 +437,8 @@ __global__ __launch_bounds__(256) void softmax_bwd_k(const T* p, const float* dp
 extern "C" int pero_softmax_fwd(const float* s, void* p, int64_t rows, int64_t cols, float scale, int dtype, void* stream) {
   PERO_REQUIRE(s && p && rows > 0 && cols > 0, "pero_softmax_fwd: bad arguments");
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  if (dtype == PERO_F32) hipLaunchKernelGGL((softmax_fwd_k<float>), grid, block, 0, (hipStream_t)stream, s, (float*)p, (long long)rows, (int)cols, scale);
-  else if (dtype == PERO_BF16) hipLaunchKernelGGL((softmax_fwd_k<bf16raw>), grid, block, 0, (hipStream_t)stream, s, (bf16raw*)p, (long long)rows, (int)cols, scale);
-  else PERO_REQUIRE(false, "pero_softmax_fwd: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((softmax_fwd_k<T>), grid, block, 0, (hipStream_t)stream, s, (T*)p, (long long)rows, (int)cols, scale); }), "pero_softmax_fwd: bad dtype");
   PERO_CHECK_LAUNCH("pero_softmax_fwd");
   return PERO_OK;
 }
@@ -469,20 +467,16 @@ extern "C" int pero_softmax_fwd_keys(const float* s, const int* key_ranges, void
                                      void* stream) {
   PERO_REQUIRE(s && key_ranges && p && rows > 0 && cols > 0 && rows_per_line > 0, "pero_softmax_fwd_keys: bad arguments");
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  if (dtype == PERO_F32)
-    hipLaunchKernelGGL((softmax_fwd_keys_k<float>), grid, block, 0, (hipStream_t)stream, s, key_ranges, (float*)p, (long long)rows, (int)cols, (long long)rows_per_line, scale);
-  else if (dtype == PERO_BF16)
-    hipLaunchKernelGGL((softmax_fwd_keys_k<bf16raw>), grid, block, 0, (hipStream_t)stream, s, key_ranges, (bf16raw*)p, (long long)rows, (int)cols, (long long)rows_per_line, scale);
-  else PERO_REQUIRE(false, "pero_softmax_fwd_keys: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((softmax_fwd_keys_k<T>), grid, block, 0, (hipStream_t)stream, s, key_ranges, (T*)p, (long long)rows, (int)cols, (long long)rows_per_line, scale); }), "pero_softmax_fwd_keys: bad dtype");
   PERO_CHECK_LAUNCH("pero_softmax_fwd_keys");
   return PERO_OK;
 }
 extern "C" int pero_softmax_bwd(const void* p, const float* dp, void* ds, int64_t rows, int64_t cols, float scale, int dtype, void* stream) {
   PERO_REQUIRE(p && dp && ds && rows > 0 && cols > 0, "pero_softmax_bwd: bad arguments");
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  if (dtype == PERO_F32) hipLaunchKernelGGL((softmax_bwd_k<float>), grid, block, 0, (hipStream_t)stream, (const float*)p, dp, (float*)ds, (long long)rows, (int)cols, scale);
-  else if (dtype == PERO_BF16) hipLaunchKernelGGL((softmax_bwd_k<bf16raw>), grid, block, 0, (hipStream_t)stream, (const bf16raw*)p, dp, (bf16raw*)ds, (long long)rows, (int)cols, scale);
-  else PERO_REQUIRE(false, "pero_softmax_bwd: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((softmax_bwd_k<T>), grid, block, 0, (hipStream_t)stream, (const T*)p, dp, (T*)ds, (long long)rows, (int)cols, scale); }), "pero_softmax_bwd: bad dtype");
   PERO_CHECK_LAUNCH("pero_softmax_bwd");
   return PERO_OK;
 }
@@ -531,11 +525,8 @@ __global__ __launch_bounds__(256) void ce_rows_k(const T* logits, const int64_t*
     for (int i = 0; i < 2; i++)
 #pragma unroll
       for (int e = 0; e < 8; e++) sum += expf(v[i][e] - mx);
-    sum = wave_sum(sum);
     __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = sum;
-    __syncthreads();
-    sum = (red[0] + red[1]) + (red[2] + red[3]);
+    sum = block_sum4(sum, red);
     const float lse = logf(sum) + mx;
     if (tid == 0) { work[row] = lse - Elem<T>::ld(lr + lab); work[rows + 8 + row] = lse; }
     return;
@@ -549,10 +540,7 @@ __global__ __launch_bounds__(256) void ce_rows_k(const T* logits, const int64_t*
   __syncthreads();
   float sum = 0.f;
   for (int c = tid; c < V; c += 256) sum += expf(Elem<T>::ld(lr + c) - mx);
-  sum = wave_sum(sum);
-  if ((tid & 63) == 0) red[tid >> 6] = sum;
-  __syncthreads();
-  sum = (red[0] + red[1]) + (red[2] + red[3]);
+  sum = block_sum4(sum, red);
   const float lse = logf(sum) + mx;
   if (tid == 0) { work[row] = lse - Elem<T>::ld(lr + lab); work[rows + 8 + row] = lse; }
 }
@@ -667,9 +655,8 @@ extern "C" int pero_masked_ce_fwd(const void* logits, const int64_t* labels, con
   PERO_REQUIRE(logits && labels && mask && loss_out && work, "pero_masked_ce_fwd: null pointer");
   PERO_REQUIRE(rows > 0 && V > 0 && rows < 16777216, "pero_masked_ce_fwd: bad sizes");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PERO_F32) hipLaunchKernelGGL((ce_rows_k<float>), dim3((unsigned)rows), dim3(256), 0, st, (const float*)logits, labels, mask, unmasked_weight, work, (long long)rows, (int)V, (const int64_t*)nullptr);
-  else if (dtype == PERO_BF16) hipLaunchKernelGGL((ce_rows_k<bf16raw>), dim3((unsigned)rows), dim3(256), 0, st, (const bf16raw*)logits, labels, mask, unmasked_weight, work, (long long)rows, (int)V, (const int64_t*)nullptr);
-  else PERO_REQUIRE(false, "pero_masked_ce_fwd: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ce_rows_k<T>), dim3((unsigned)rows), dim3(256), 0, st, (const T*)logits, labels, mask, unmasked_weight, work, (long long)rows, (int)V, (const int64_t*)nullptr); }), "pero_masked_ce_fwd: bad dtype");
   hipMemsetAsync(work + rows + 2, 0, sizeof(float), st);  // the reduction's ticket
   hipLaunchKernelGGL(ce_final_k, dim3(CE_PARTS), dim3(256), 0, st, labels, mask, unmasked_weight, work, loss_out, (long long)rows);
   PERO_CHECK_LAUNCH("pero_masked_ce_fwd");
@@ -681,9 +668,8 @@ extern "C" int pero_masked_ce_fwd_rows(const void* logits, const int64_t* labels
   PERO_REQUIRE(rows > 0 && V > 0 && rows < 16777216 && n_idx > 0 && n_idx <= rows, "pero_masked_ce_fwd_rows: bad sizes");
   hipStream_t st = (hipStream_t)stream;
   // ce_final_k reads work[r] of every row with mask == 1 (all listed) and, into a sum this mode never uses, of the rows with mask == 0
-  if (dtype == PERO_F32) hipLaunchKernelGGL((ce_rows_k<float>), dim3((unsigned)n_idx), dim3(256), 0, st, (const float*)logits, labels, mask, -1.0f, work, (long long)rows, (int)V, index);
-  else if (dtype == PERO_BF16) hipLaunchKernelGGL((ce_rows_k<bf16raw>), dim3((unsigned)n_idx), dim3(256), 0, st, (const bf16raw*)logits, labels, mask, -1.0f, work, (long long)rows, (int)V, index);
-  else PERO_REQUIRE(false, "pero_masked_ce_fwd_rows: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ce_rows_k<T>), dim3((unsigned)n_idx), dim3(256), 0, st, (const T*)logits, labels, mask, -1.0f, work, (long long)rows, (int)V, index); }), "pero_masked_ce_fwd_rows: bad dtype");
   hipMemsetAsync(work + rows + 2, 0, sizeof(float), st);  // the reduction's ticket
   hipLaunchKernelGGL(ce_final_k, dim3(CE_PARTS), dim3(256), 0, st, labels, mask, -1.0f, work, loss_out, (long long)rows);
   PERO_CHECK_LAUNCH("pero_masked_ce_fwd_rows");
@@ -699,9 +685,8 @@ extern "C" int pero_masked_ce_bwd(const void* logits, const int64_t* labels, con
     pero_set_error("pero_masked_ce_bwd: zero fill failed");
     return PERO_E_LAUNCH;
   }
-  if (dtype == PERO_F32) hipLaunchKernelGGL((ce_bwd_k<float>), dim3((unsigned)rows), dim3(256), 0, st, (const float*)logits, labels, mask, unmasked_weight, dloss, work, (float*)dlogits, (long long)rows, (int)V, (const int64_t*)nullptr, 0LL);
-  else if (dtype == PERO_BF16) hipLaunchKernelGGL((ce_bwd_k<bf16raw>), dim3((unsigned)rows), dim3(256), 0, st, (const bf16raw*)logits, labels, mask, unmasked_weight, dloss, work, (bf16raw*)dlogits, (long long)rows, (int)V, (const int64_t*)nullptr, 0LL);
-  else PERO_REQUIRE(false, "pero_masked_ce_bwd: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ce_bwd_k<T>), dim3((unsigned)rows), dim3(256), 0, st, (const T*)logits, labels, mask, unmasked_weight, dloss, work, (T*)dlogits, (long long)rows, (int)V, (const int64_t*)nullptr, 0LL); }), "pero_masked_ce_bwd: bad dtype");
   PERO_CHECK_LAUNCH("pero_masked_ce_bwd");
   return PERO_OK;
 }
@@ -713,9 +698,8 @@ extern "C" int pero_masked_ce_bwd_rows(const void* logits, const int64_t* labels
   hipStream_t st = (hipStream_t)stream;
   // (index == null with n_idx == 0: every output row is padding; the kernel needs a non-null pointer to take the compact form)
   const int64_t* ix = index ? index : labels;
-  if (dtype == PERO_F32) hipLaunchKernelGGL((ce_bwd_k<float>), dim3((unsigned)n_rows_out), dim3(256), 0, st, (const float*)logits, labels, mask, unmasked_weight, dloss, work, (float*)dlogits_rows, (long long)rows, (int)V, ix, (long long)n_idx);
-  else if (dtype == PERO_BF16) hipLaunchKernelGGL((ce_bwd_k<bf16raw>), dim3((unsigned)n_rows_out), dim3(256), 0, st, (const bf16raw*)logits, labels, mask, unmasked_weight, dloss, work, (bf16raw*)dlogits_rows, (long long)rows, (int)V, ix, (long long)n_idx);
-  else PERO_REQUIRE(false, "pero_masked_ce_bwd_rows: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((ce_bwd_k<T>), dim3((unsigned)n_rows_out), dim3(256), 0, st, (const T*)logits, labels, mask, unmasked_weight, dloss, work, (T*)dlogits_rows, (long long)rows, (int)V, ix, (long long)n_idx); }), "pero_masked_ce_bwd_rows: bad dtype");
   PERO_CHECK_LAUNCH("pero_masked_ce_bwd_rows");
   return PERO_OK;
 }
@@ -766,17 +750,15 @@ extern "C" int pero_colsum(const void* x, float* out, int64_t rows, int64_t cols
   const int esz = dtype == PERO_F32 ? 4 : 2;
   if (cols % 8 == 0 && (ld * esz) % 16 == 0 && aligned16(x) && (rows + 127) / 128 < 65536) {
     dim3 grid((unsigned)((cols + 255) / 256), (unsigned)((rows + 127) / 128)), block(256);
-    if (dtype == PERO_F32) hipLaunchKernelGGL((colsum8_k<float>), grid, block, 0, (hipStream_t)stream, (const float*)x, out, (long long)rows, (long long)cols, (long long)ld);
-    else if (dtype == PERO_BF16) hipLaunchKernelGGL((colsum8_k<bf16raw>), grid, block, 0, (hipStream_t)stream, (const bf16raw*)x, out, (long long)rows, (long long)cols, (long long)ld);
-    else PERO_REQUIRE(false, "pero_colsum: bad dtype");
+    PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+      hipLaunchKernelGGL((colsum8_k<T>), grid, block, 0, (hipStream_t)stream, (const T*)x, out, (long long)rows, (long long)cols, (long long)ld); }), "pero_colsum: bad dtype");
     PERO_CHECK_LAUNCH("pero_colsum");
     return PERO_OK;
   }
   long long gy = rows < 128 ? rows : 128;
   dim3 grid((unsigned)((cols + 255) / 256), (unsigned)gy), block(256);
-  if (dtype == PERO_F32) hipLaunchKernelGGL((colsum_k<float>), grid, block, 0, (hipStream_t)stream, (const float*)x, out, (long long)rows, (long long)cols, (long long)ld);
-  else if (dtype == PERO_BF16) hipLaunchKernelGGL((colsum_k<bf16raw>), grid, block, 0, (hipStream_t)stream, (const bf16raw*)x, out, (long long)rows, (long long)cols, (long long)ld);
-  else PERO_REQUIRE(false, "pero_colsum: bad dtype");
+  PERO_REQUIRE(with_elem(dtype, [&](auto t) { using T = decltype(t);
+    hipLaunchKernelGGL((colsum_k<T>), grid, block, 0, (hipStream_t)stream, (const T*)x, out, (long long)rows, (long long)cols, (long long)ld); }), "pero_colsum: bad dtype");
   PERO_CHECK_LAUNCH("pero_colsum");
   return PERO_OK;
 }
